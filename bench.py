@@ -9,7 +9,11 @@ already resident in HBM: FRAMES frames of BASELINE configs[1]
 launch through the C-ABI (rawspeed_amd/librsx.so).  The batch is larger than
 the 256 MiB Infinity Cache on purpose, so the rate is an HBM rate.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, what the last of them decoded -- a fixed, seeded
+sample of rows of the u16 output frames, as float32, and the per-frame statuses -- goes to
+DIR/*.npy (see dump_outputs), so that two builds can be compared output for output.
 
 N > 1: one process per GPU.  Started under a launcher (torchrun: WORLD_SIZE set) the
 process is one rank; started bare, `--gpus N` re-executes itself under
@@ -71,6 +75,8 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=8, help="frames per GPU per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-cfg5", action="store_true",
@@ -83,7 +89,10 @@ def parse():
                     help="cfg 5: rank 0 holds the packed batch and broadcasts it over RCCL")
     ap.add_argument("--scatter", action="store_true",
                     help="cfg 5: rank 0 holds the packed batch and sends every rank its shard")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -143,6 +152,31 @@ def frame_of(out_t, cfg, f):
     op = out_pitch(w)
     return out_t[f * h * op:(f + 1) * h * op].cpu().numpy().view(np.uint16) \
         .reshape(h, op // 2)[:, :w]
+
+
+DUMP_ROWS = 1536  # sampled output rows: 1536 x 8192 px x 4 B = 48 MiB of float32 at most
+
+
+def dump_outputs(d, out_t, cfg, frames, plan, n_sample=DUMP_ROWS, suffix=""):
+    """What a caller of the timed path receives after its last step: the decoded frames
+    (a sample of n_sample of their F*h rows, chosen by a fixed seed, every pixel of a
+    sampled row; float32) and the per-frame status and consumed-bytes arrays (float64)."""
+    import torch
+    w, h = cfg["w"], cfg["h"]
+    op = out_pitch(w)
+    n_rows = frames * h
+    rows = np.sort(np.random.default_rng(20240).choice(n_rows, min(n_sample, n_rows),
+                                                       replace=False))
+    idx = torch.from_numpy(rows).to(out_t.device)
+    sample = out_t.view(n_rows, op).index_select(0, idx).cpu().numpy()
+    px = sample.view(np.uint16)[:, :w].astype(np.float32)
+    rc, st, cons = plan.results()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "unpack_rows%s.npy" % suffix), px)
+    np.save(os.path.join(d, "unpack_row_index%s.npy" % suffix), rows.astype(np.float64))
+    np.save(os.path.join(d, "unpack_status%s.npy" % suffix),
+            np.array([rc] + st, dtype=np.float64))
+    np.save(os.path.join(d, "unpack_consumed%s.npy" % suffix), np.array(cons, dtype=np.float64))
 
 
 def profile_rounds():
@@ -556,6 +590,10 @@ def main():
     ktime = plan.kernel_time()
     plan.set_timing(False)
     elapsed = grp.max_over_ranks(my_elapsed)
+    if args.dump_outputs:
+        # (every rank its own frames; the sample budget is shared out over the ranks)
+        dump_outputs(args.dump_outputs, out, CFG2, F, plan, max(1, DUMP_ROWS // n_gpus),
+                     "_rank%d" % rank if grp.enabled else "")
     per_rank = grp.gather_objects(round(F * w * h * args.steps / my_elapsed / 1e6, 1), dst=0)
     # copy ceiling for the same read:write mix (outside the timed region): a plain
     # streaming kernel over the very same buffers

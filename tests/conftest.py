@@ -24,7 +24,19 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref():
+    """The compiled reference where oracle/_ref is built (with RSX_REF_RECORD=<file.npz>
+    its answers are recorded into that file); elsewhere its stored answers
+    (tests/ref_vectors.py, tests/golden/ref_vectors.json.gz)."""
     from oracle_lib import Ref
+    import ref_vectors
     if not Ref.available():
-        pytest.skip("oracle/_ref/librawspeed_ref.so not built (no /root/reference here)")
-    return Ref()
+        yield ref_vectors.StoredRef()
+        return
+    r = Ref()
+    path = os.environ.get("RSX_REF_RECORD")
+    if not path:
+        yield r
+        return
+    rec = ref_vectors.RecordingRef(r, path)
+    yield rec
+    rec.save()

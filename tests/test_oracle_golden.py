@@ -1,6 +1,7 @@
 """Oracle (oracle/rsx_oracle.c) vs the golden hashes the reference produced
-(tests/golden/golden_hashes.json, generator tests/golden/make_golden.py) and,
-where oracle/_ref is present, vs the reference itself, full-buffer compare."""
+(tests/golden/golden_hashes.json, generator tests/golden/make_golden.py) and vs the
+reference itself, full-buffer compare: live where oracle/_ref is built, elsewhere its
+stored answers (tests/ref_vectors.py)."""
 import json
 import os
 
