@@ -173,3 +173,158 @@ def pentax_encode(img, tree):
     """NikonDecompressor's predictor with all four pUp = 0 is PentaxDecompressor's
     (rows 0 and 1 start from 0, later rows from the pixels two rows up)."""
     return synth.nikon_encode(img, [0, 0, 0, 0], tree)
+
+
+# ---- streams of INT images, and the reconstruction they decode to ----------------------
+
+def _codes(code):
+    """{difference length: (code, code length)} of a canonical tree (Nikon / Pentax), or of
+    SamsungV1's (encLen, diffLen) pairs in table-fill order (SamsungV1Decompressor.cpp:
+    110-117: entry i fills 1024 >> encLen slots of the 10-bit table from where the last one
+    stopped, so its code is that slot's top encLen bits)."""
+    if len(code) == 2 and len(code[0]) == 16:
+        return {v: (c, l) for (c, l, v) in _canonical(code)}
+    out, n = {}, 0
+    for enc, dif in code:
+        out.setdefault(dif, (n >> (10 - enc), enc))
+        n += 1024 >> enc
+    assert n == 1024
+    return out
+
+
+def prefix_diffs(src, p_up):
+    """The differences NikonDecompressor.cpp:518-560 (and, with all four p_up = 0,
+    PentaxDecompressor.cpp:155-177 / SamsungV1Decompressor.cpp:123-137) decode `src` -- given
+    as INTS, whatever the decoder does with values outside its range -- from: the first pair
+    of a row from the row two above, the others from the sample two to the left."""
+    src = np.asarray(src, np.int64)
+    h, w = src.shape
+    pred = np.empty_like(src)
+    pred[:, 2:] = src[:, :-2]
+    up = np.array(p_up, np.int64).reshape(2, 2)
+    for y in range(h):
+        pred[y, :2] = up[y & 1]
+        up[y & 1] = src[y, :2]
+    return src - pred
+
+
+def prefix_symbols(diff, code):
+    """Per difference (row-major) its symbol as (bits, length): the code of its length, then
+    the length's low bits of the difference (ones' complement below zero)."""
+    diff = np.asarray(diff, np.int64).ravel()
+    mag = np.abs(diff)
+    ssss = np.where(mag == 0, 0, np.floor(np.log2(np.maximum(mag, 1))).astype(np.int64) + 1)
+    by_len = _codes(code)
+    missing = set(np.unique(ssss).tolist()) - set(by_len)
+    if missing:
+        raise ValueError("no code for difference lengths %s" % sorted(missing))
+    lut_c = np.zeros(17, np.int64)
+    lut_l = np.zeros(17, np.int64)
+    for v, (c, l) in by_len.items():
+        lut_c[v], lut_l[v] = c, l
+    extra = np.where(diff >= 0, diff, diff + (1 << ssss) - 1)
+    return (lut_c[ssss] << ssss) | extra, lut_l[ssss] + ssss
+
+
+def symbol_bits(val, ln):
+    """The symbols as one MSB-first bit per byte (np.uint8 of 0 / 1)."""
+    out = []
+    for k in range(0, val.size, 1 << 20):
+        v, l = val[k:k + (1 << 20)], ln[k:k + (1 << 20)]
+        assert l.size == 0 or (l.min() >= 1 and l.max() <= 32)
+        m = np.unpackbits((v << (32 - l)).astype(">u4").view(np.uint8)).reshape(-1, 32)
+        out.append(m[np.arange(32)[None, :] < l[:, None]])
+    return np.concatenate(out) if out else np.zeros(0, np.uint8)
+
+
+def encode_ints(src, p_up, code):
+    """The stream of an image given as INTS (values outside the decoder's range are what its
+    sums reach before clampBits(., 15) / the range check), `code` a canonical tree or
+    SamsungV1's pairs; p_up all zeros for Pentax and SamsungV1."""
+    val, ln = prefix_symbols(prefix_diffs(src, p_up), code)
+    return np.concatenate([np.packbits(np.concatenate([symbol_bits(val, ln), np.zeros(8, np.uint8)])),
+                           np.zeros(16, np.uint8)])
+
+
+def prefix_model(diff, bits):
+    """PentaxDecompressor::decompress (bits = 16) / SamsungV1Decompressor::decompress
+    (bits = 12) in plain int64: the running predictor per column parity, rows from 2 on
+    starting from out(row - 2, 0 / 1), every value checked with isIntN(value, bits) and stored
+    as uint16.  Returns (image, None) or, at the first value out of range, (the image so far
+    -- the rows and columns in front of it --, (row, col))."""
+    diff = np.asarray(diff, np.int64)
+    h, w = diff.shape
+    out = np.zeros((h, w), np.uint16)
+    for row in range(h):
+        pred = np.zeros(2, np.int64) if row < 2 else out[row - 2, :2].astype(np.int64)
+        value = np.empty(w, np.int64)
+        for c in (0, 1):
+            value[c::2] = pred[c] + np.cumsum(diff[row, c::2])
+        bad = np.flatnonzero((value < 0) | (value >= (1 << bits)))
+        if bad.size:
+            col = int(bad[0])
+            out[row, :col] = value[:col]
+            return out, (row, col)
+        out[row] = value
+    return out, None
+
+
+# ---- value edges of the Pentax / SamsungV1 range checks --------------------------------
+
+# name: (code, isIntN bits, the largest difference the code has a length for, base image maxv
+# -- the first sample of each parity in rows 0 and 1 is a whole difference from 0)
+PREFIX_FAMILY = {
+    "pentax_legacy": (synth.PENTAX_TREE, 16, 4095, 4095),
+    "pentax_modern": (PENTAX_MODERN, 16, 16383, 16383),
+    "samsung_v1": (synth.SAMSUNG_V1_TAB, 12, 8191, 4095),
+}
+# valid values at both ends of the range (and Pentax's around bit 15), then the first ones out
+EDGE_VALUES = {16: (0, 32767, 32768, 65535, 65536, -1), 12: (0, 4095, 4096, -1)}
+EDGE_PLACES = ("r0c0", "r1c1", "c0", "c1", "late", "last")
+SLOPE = 1700  # per pixel (L1) of a planted peak: same-colour neighbours differ by 2 x SLOPE
+
+
+def edge_cases(family):
+    """(value, place) of a family; a value at the first sample of a parity in rows 0 and 1 (the
+    predictor is 0) only if the code has a difference that long."""
+    _, bits, reach, _ = PREFIX_FAMILY[family]
+    return [(v, p) for v in EDGE_VALUES[bits] for p in EDGE_PLACES
+            if p not in ("r0c0", "r1c1") or abs(v) <= reach]
+
+
+def edge_position(place, value, reach, h, w):
+    """Rows 0 and 1 start from 0, a row from 2 on from the row two above: col 0 / 1 of row 2
+    where the peak's slope reaches rows 0 and 1 within the code's differences, of a middle row
+    otherwise; "late": mid-row near the end of the stream; "last": the frame's last sample."""
+    r = 2 if abs(value) <= reach else 2 * (h // 4)
+    return {"r0c0": (0, 0), "r1c1": (1, 1), "c0": (r, 0), "c1": (r, 1),
+            "late": (h - 3, w // 2 + 1), "last": (h - 1, w - 1)}[place]
+
+
+def plant(base, y, x, value, slope=SLOPE):
+    """`base` (ints) with ONE sample at `value`: a peak (or pit) whose sides fall by `slope` per
+    pixel until they meet the base, so every other sample stays on the base's side of `value`
+    and no difference is longer than the base's or 2 x slope."""
+    yy, xx = np.indices(base.shape)
+    d = np.abs(yy - y) + np.abs(xx - x)
+    if value >= base[y, x]:
+        return np.maximum(base, value - slope * d)
+    return np.minimum(base, value + slope * d)
+
+
+def plateau(base, y, value, slope=SLOPE):
+    """Rows y .. y + 2 at `value` (+ 7 on odd columns), falling by `slope` per row above and below:
+    rows y + 2 and y + 4 start from a value that large."""
+    yy, xx = np.indices(base.shape)
+    ridge = value + 7 * (xx & 1) - slope * np.maximum(0, np.abs(yy - (y + 1)) - 1)
+    return np.maximum(base, ridge)
+
+
+def edge_image(family, base, value, place):
+    """(image as ints, the planted (row, col) or None for the plateau)."""
+    _, _, reach, _ = PREFIX_FAMILY[family]
+    h, w = base.shape
+    if place == "plateau":
+        return plateau(base, 2 * (h // 4), value), None
+    y, x = edge_position(place, value, reach, h, w)
+    return plant(base, y, x, value), (y, x)

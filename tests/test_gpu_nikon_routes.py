@@ -13,7 +13,6 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from rawspeed_amd import abi, synth
 
@@ -34,74 +33,9 @@ def gpu():
     return gpu_util.ctx()
 
 
-def _encode_ints(src, p_up, tree):
-    """NikonDecompressor's stream (no split) of an image given as INTS -- values below 0 or above
-    32767 are what the decoder's sums reach before clampBits(., 15) -- by the predictor of
-    NikonDecompressor.cpp:518-560: the first pair of a row from the row two above, the others from
-    the sample two to the left."""
-    h, w = src.shape
-    pred = np.empty_like(src)
-    pred[:, 2:] = src[:, :-2]
-    up = np.array(p_up, np.int64).reshape(2, 2)
-    for y in range(h):
-        pred[y, :2] = up[y & 1]
-        up[y & 1] = src[y, :2]
-    diff = (src - pred).ravel()
-    mag = np.abs(diff)
-    ssss = np.where(mag == 0, 0, np.floor(np.log2(np.maximum(mag, 1))).astype(np.int64) + 1)
-    assert ssss.max() <= 15
-    by_len = {v: (c, l) for (c, l, v) in N._canonical(tree)}
-    code = np.array([by_len[int(v)][0] for v in ssss], np.int64)
-    clen = np.array([by_len[int(v)][1] for v in ssss], np.int64)
-    extra = np.where(diff >= 0, diff, diff + (1 << ssss) - 1)
-    val, ln = (code << ssss) | extra, clen + ssss
-    start = np.concatenate([[0], np.cumsum(ln)[:-1]])
-    bits = np.zeros(int(ln.sum()) + 8, np.uint8)
-    for k in range(int(ln.max())):
-        m = k < ln
-        bits[start[m] + k] = (val[m] >> (ln[m] - 1 - k)) & 1
-    return np.concatenate([np.packbits(bits), np.zeros(16, np.uint8)])
-
-
-class _env:
-    def __init__(self, names):
-        self.names = names
-
-    def __enter__(self):
-        for n in self.names:
-            os.environ[n] = "1"
-
-    def __exit__(self, *a):
-        for n in self.names:
-            os.environ.pop(n, None)
-
-
 def _run(gpu, make_plan, jobs, in_host, out_bytes, route):
     import gpu_util
-    with _env(route):
-        plan = make_plan(jobs)
-    d_in = gpu_util.to_dev(in_host)
-    d_out = torch.full((out_bytes + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-    plan.set_timing(True)
-    plan.run(d_in.data_ptr(), d_out.data_ptr())
-    rc, status, _ = plan.results()
-    tab = plan.kernel_table()
-    plan.kernel_time()  # (resets the totals: the next table is the next run's)
-    names = [n for n, _ in tab[0]] if tab else []
-    # a second run of the same plan: the steady-state instantiation, the cached level -- and the pass
-    # that redoes what the single-pass kernel gave up on is launched by the run itself (the first
-    # run's is launched when the results are fetched, outside the timed launches): its kernels are
-    # in THIS run's table
-    d_out2 = torch.full((out_bytes + 16,), 0xA5, dtype=torch.uint8, device="cuda")
-    plan.run(d_in.data_ptr(), d_out2.data_ptr())
-    rc2, status2, _ = plan.results()
-    tab = plan.kernel_table()
-    names += ["run 2: " + n for n, _ in tab[0]] if tab else []
-    plan.set_timing(False)
-    plan.close()
-    assert rc == rc2 and status == status2  # (rc: the first failing job's status)
-    a, b = d_out.cpu().numpy(), d_out2.cpu().numpy()
-    return status, a, b, names
+    return gpu_util.run_plan(make_plan, jobs, in_host, out_bytes, route)[:4]
 
 
 def _nikon_job(gpu_util, d, data, w, h, pitch, in_off, out_off):
@@ -180,7 +114,7 @@ def test_nikon_values_at_the_edges(gpu, oracle):
         if val > 16383:  # (the tree's largest difference has 14 bits: a ramp of same-colour neighbours)
             src[y, x - 4] = src[y, x + 4] = 16000
             src[y, x - 2] = src[y, x + 2] = 24000
-        data = _encode_ints(src, [pu[0][0], pu[0][1], pu[1][0], pu[1][1]], tree)
+        data = N.encode_ints(src, [pu[0][0], pu[0][1], pu[1][0], pu[1][1]], tree)
         d = N.desc(P, bits, True)
         want = HostImage(w, h)
         assert oracle.nikon(d, data, want) == 0
