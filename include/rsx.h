@@ -440,6 +440,51 @@ int rsx_sony_arw1_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
                              const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 3h. PhaseOneDecompressor                                                  */
+/*    replaces PhaseOneDecompressor::decompress()                            */
+/*    (decompressors/PhaseOneDecompressor.cpp:156-170 -> decompressStrip     */
+/*    :85-136 for every strip).  IiqDecoder keeps its host work: container   */
+/*    parsing, computeSripes (IiqDecoder.cpp:75-118: a strip runs from its   */
+/*    offset to the next larger one, the last to the end of raw_data) and    */
+/*    CorrectPhaseOneC.  One strip per image row; each is a BitStreamerMSB32 */
+/*    over exactly its own bytes (bytes behind the strip read as zero, not   */
+/*    as the next row).  Per row: pred[2] = {0, 0}; for col < (w & ~7),      */
+/*    col % 8 == 0, a header for len[0] then len[1] (up to five 0-bits up to */
+/*    a 1-bit; j zeros > 0: one more bit b, len = {8,7,6,9,11,10,5,12,14,13} */
+/*    [2 (j - 1) + b]; j == 0: len kept); the last w % 8 pixels have len 14; */
+/*    len 14 = a raw 16-bit value that resets pred[col & 1], else            */
+/*    pred += bits(len) + 1 - (1 << (len - 1)); pixel = uint16(pred).        */
+/*    rsx_phase_one_validate = the constructor's checks (:43-84: cpp 1,      */
+/*    dim > 0, dim_x even, dim_x <= 11976, dim_y <= 8854, exactly one strip  */
+/*    per row 0 .. dim_y - 1) plus: every strip lies inside [0, in_bytes)    */
+/*    -> RSX_ERR_INVALID_ARG.  Per-row statuses (the first that applies):    */
+/*      RSX_ERR_IO               strip shorter than 4 bytes ("Bit stream     */
+/*                               size is smaller than MaxProcessBytes",      */
+/*                               bitstreams/BitStreamer.h:58-59)             */
+/*      RSX_ERR_BAD_HUFFMAN_CODE a 1-bit inside a length prefix at col 0     */
+/*                               ("Can not initialize lengths", :107-108)    */
+/*      RSX_ERR_INPUT_OVERFLOW   a refill more than 8 bytes past the strip   */
+/*                               (BitStreamer.h:124-127): with c the start   */
+/*                               bit of pixel w - 1, 4 ceil(c / 32) > size+8 */
+/*    Any failing row fails the decode ("Too many errors", :156-170); the    */
+/*    call returns the status of the lowest-numbered failing row, and        */
+/*    through host pointers leaves the caller's image untouched then.        */
+/*    `strip_status` (may be NULL) gets one status per image row.            */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_phase_one_strip {
+  uint32_t n;        /* image row */
+  uint32_t reserved;
+  uint64_t offset;   /* byte offset of the strip inside `in` */
+  uint64_t bytes;    /* strip size (next larger offset - offset) */
+} rsx_phase_one_strip;
+
+int rsx_phase_one_validate(int n_strips, const rsx_phase_one_strip* strips, size_t in_bytes,
+                           const rsx_image* img);
+int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes, int n_strips,
+                             const rsx_phase_one_strip* strips, const rsx_image* img,
+                             int32_t* strip_status);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -579,6 +624,17 @@ typedef struct rsx_sony_arw1_job {
   rsx_image img; /* .data ignored */
 } rsx_sony_arw1_job;
 
+/* strip offsets are relative to in_offset; jobs of different geometry may share a plan */
+typedef struct rsx_phase_one_job {
+  const rsx_phase_one_strip* strips; /* host pointer, copied at plan creation */
+  int32_t n_strips;
+  int32_t reserved;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_phase_one_job;
+
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */
@@ -606,6 +662,8 @@ int rsx_sraw_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sraw_job* jobs,
 int rsx_hasselblad_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_hasselblad_job* jobs,
                                rsx_plan** out_plan);
 int rsx_sony_arw1_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw1_job* jobs,
+                              rsx_plan** out_plan);
+int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs,
                               rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,

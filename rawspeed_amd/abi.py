@@ -192,6 +192,25 @@ class SonyArw1Job(C.Structure):
                 ("img_offset", C.c_uint64), ("img", Image)]
 
 
+class PhaseOneStrip(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64),
+                ("bytes", C.c_uint64)]
+
+
+class PhaseOneJob(C.Structure):
+    _fields_ = [("strips", C.POINTER(PhaseOneStrip)), ("n_strips", C.c_int32),
+                ("reserved", C.c_int32), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def phase_one_strips(table):
+    """[(row, offset, bytes)] -> a ctypes array of rsx_phase_one_strip"""
+    arr = (PhaseOneStrip * max(1, len(table)))()
+    for i, (n, off, size) in enumerate(table):
+        arr[i].n, arr[i].offset, arr[i].bytes = n, off, size
+    return arr
+
+
 class SrawDesc(C.Structure):
     _fields_ = [("version", C.c_int32), ("subsampling_y", C.c_int32),
                 ("sraw_coeffs", C.c_int32 * 3), ("hue", C.c_int32)]

@@ -30,6 +30,7 @@ EXPORTS = [
     "rsx_samsung_v1_validate", "rsx_samsung_v1_decompress", "rsx_samsung_v1_plan_create",
     "rsx_samsung_v2_validate", "rsx_samsung_v2_decompress", "rsx_samsung_v2_plan_create",
     "rsx_sony_arw1_validate", "rsx_sony_arw1_decompress", "rsx_sony_arw1_plan_create",
+    "rsx_phase_one_validate", "rsx_phase_one_decompress", "rsx_phase_one_plan_create",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
@@ -91,6 +92,9 @@ def lib():
         L.rsx_sony_arw1_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.c_void_p]
         L.rsx_samsung_v1_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_phase_one_validate.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_phase_one_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -110,7 +114,7 @@ def lib():
                      "rsx_pentax_plan_create", "rsx_samsung_v1_plan_create",
                      "rsx_samsung_v2_plan_create",
                      "rsx_sraw_plan_create", "rsx_hasselblad_plan_create",
-                     "rsx_sony_arw1_plan_create"):
+                     "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -131,6 +135,12 @@ def lib():
 
 def status_string(st):
     return lib().rsx_status_string(st).decode()
+
+
+def phase_one_validate(strips, in_bytes, img_view):
+    """rsx_phase_one_validate; strips: [(row, offset, bytes)]"""
+    arr = abi.phase_one_strips(strips)
+    return lib().rsx_phase_one_validate(len(strips), arr, in_bytes, C.byref(img_view))
 
 
 def _u8(a):
@@ -274,6 +284,15 @@ class Context:
         return lib().rsx_sony_arw1_decompress(self._h, a.ctypes.data, a.size,
                                               C.byref(img_view))
 
+    def phase_one_decompress(self, data, strips, img_view):
+        """strips: [(row, offset, bytes)] into `data`.  Returns (status, per-row statuses)."""
+        a = _u8(data)
+        arr = abi.phase_one_strips(strips)
+        rows = (C.c_int32 * max(1, img_view.dim_y))()
+        st = lib().rsx_phase_one_decompress(self._h, a.ctypes.data, a.size, len(strips), arr,
+                                            C.byref(img_view), rows)
+        return st, list(rows)[:img_view.dim_y]
+
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
@@ -328,6 +347,10 @@ class Context:
 
     def sony_arw1_plan(self, jobs):
         return Plan(self, "rsx_sony_arw1_plan_create", abi.SonyArw1Job, jobs)
+
+    def phase_one_plan(self, jobs):
+        """jobs: abi.PhaseOneJob (their strip arrays are copied at plan creation)"""
+        return Plan(self, "rsx_phase_one_plan_create", abi.PhaseOneJob, jobs)
 
     def pentax_plan(self, jobs):
         return Plan(self, "rsx_pentax_plan_create", abi.PentaxJob, jobs)

@@ -7,6 +7,7 @@
 #include "rsx_internal.h"
 #include "rsx_ljpeg.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_phase_one.h"
 #include "rsx_samsung_v2.h"
 
 #include <algorithm>
@@ -22,7 +23,7 @@ using namespace rsx;
 // ---------------------------------------------------------------------------
 namespace {
 
-enum PlanKind { PLAN_UNPACK = 0, PLAN_LJPEG = 1, PLAN_SRAW = 2, PLAN_SV2 = 3 };
+enum PlanKind { PLAN_UNPACK = 0, PLAN_LJPEG = 1, PLAN_SRAW = 2, PLAN_SV2 = 3, PLAN_P1 = 4 };
 
 struct UnpackLaunch {
   int mode = UNPACK_MODE_PACKED;
@@ -48,6 +49,7 @@ struct rsx_plan {
   std::vector<UnpackLaunch> unpack;
   std::unique_ptr<LJpegPlan, LJpegPlanDeleter> ljpeg;
   Sv2Plan* sv2 = nullptr; // PLAN_SV2
+  P1Plan* p1 = nullptr;   // PLAN_P1
   // PLAN_SRAW
   DeviceBuffer d_sraw_jobs, d_sraw_starts;
   int n_sraw = 0;
@@ -915,14 +917,19 @@ extern "C" int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
   }
   (void)ev;
   const bool sv2 = plan->kind == PLAN_SV2;
-  if (!plan->timing)
+  if (!plan->timing) {
+    if (plan->kind == PLAN_P1)
+      return phase_one_plan_run(plan->p1, in_dev, out_dev, s, nullptr);
     return sv2 ? samsung_v2_plan_run(plan->sv2, in_dev, out_dev, s, nullptr)
                : ljpeg_plan_run(plan->ljpeg.get(), in_dev, out_dev, s, nullptr);
+  }
   if (int st = fold_kernel_timer(plan)) // (waits for the previous timed run)
     return st;
   if (!plan->ktimer)
     plan->ktimer = std::make_unique<KernelTimer>();
   plan->ktimer_pending = true;
+  if (plan->kind == PLAN_P1)
+    return phase_one_plan_run(plan->p1, in_dev, out_dev, s, plan->ktimer.get());
   return sv2 ? samsung_v2_plan_run(plan->sv2, in_dev, out_dev, s, plan->ktimer.get())
              : ljpeg_plan_run(plan->ljpeg.get(), in_dev, out_dev, s, plan->ktimer.get());
 }
@@ -954,6 +961,12 @@ extern "C" int rsx_plan_results(rsx_plan* plan, int32_t* job_status,
         job_consumed[i] = 0;
     return samsung_v2_plan_results(plan->sv2, plan->last_stream, plan->ran, job_status);
   }
+  if (plan->kind == PLAN_P1) {
+    if (job_consumed)
+      for (int i = 0; i < plan->n_jobs; ++i)
+        job_consumed[i] = 0;
+    return phase_one_plan_results(plan->p1, plan->last_stream, plan->ran, job_status);
+  }
   return ljpeg_plan_results(plan->ljpeg.get(), plan->last_stream, plan->ran,
                             job_status, job_consumed);
 }
@@ -966,7 +979,7 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
   plan->ktotals.clear();
   plan->kruns = 0;
   plan->ktimer_pending = false;
-  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2)
+  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1)
     return RSX_OK; // its events are created on the first timed run
   if (plan->timing && plan->events.size() < 64) {
     // event creation is slow on ROCm: pre-create the pool outside timed regions
@@ -985,7 +998,8 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
 
 extern "C" int rsx_plan_kernel_table(rsx_plan* plan, int cap, const char** names,
                                      double* avg_ms, int* n_kernels, int* n_runs) {
-  if (!plan || (plan->kind != PLAN_LJPEG && plan->kind != PLAN_SV2) || !plan->timing)
+  if (!plan || (plan->kind != PLAN_LJPEG && plan->kind != PLAN_SV2 && plan->kind != PLAN_P1) ||
+      !plan->timing)
     return RSX_ERR_INVALID_ARG;
   rsx_ctx* ctx = plan->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
@@ -1018,7 +1032,7 @@ extern "C" int rsx_plan_kernel_time(rsx_plan* plan, const char** kernel_name,
   rsx_ctx* ctx = plan->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2) {
+  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1) {
     // the dominant kernel = the one with the largest share of the timed runs
     if (int st = fold_kernel_timer(plan))
       return st;
@@ -1086,6 +1100,7 @@ extern "C" void rsx_plan_destroy(rsx_plan* plan) {
         (void)hipEventDestroy(plan->ktimer->ev[i]);
     plan->ljpeg.reset();
     samsung_v2_plan_destroy(plan->sv2);
+    phase_one_plan_destroy(plan->p1);
   }
   delete plan;
 }
@@ -2889,6 +2904,119 @@ extern "C" int rsx_dng_decompress_ljpeg(rsx_ctx* ctx, int n_tiles,
     if (st[i] != RSX_OK)
       return RSX_ERR_TILE_ERRORS; // AbstractDngDecompressor.cpp:247-251
   return RSX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// PhaseOneDecompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_phase_one_validate(int n_strips, const rsx_phase_one_strip* strips,
+                                      size_t in_bytes, const rsx_image* img) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return phase_one_validate(n_strips, strips, in_bytes, *img);
+}
+
+extern "C" int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs,
+                                         rsx_plan** out_plan) {
+  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  auto plan = std::make_unique<rsx_plan>();
+  plan->ctx = ctx;
+  plan->kind = PLAN_P1;
+  plan->n_jobs = n_jobs;
+  plan->job_status.assign(n_jobs, RSX_OK);
+  if (int st = phase_one_plan_create(ctx, n_jobs, jobs, &plan->p1))
+    return st;
+  *out_plan = plan.release();
+  return RSX_OK;
+}
+
+// The host-pointer call: the bytes the strips cover go up as one copy, the image comes back
+// through download_rects -- only when every row decoded (the reference throws otherwise, and
+// the caller's image stays as it was).  The lane keeps the plan; its key holds the strip table.
+extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                        int n_strips, const rsx_phase_one_strip* strips,
+                                        const rsx_image* img, int32_t* strip_status) {
+  if (!ctx || !in || !strips || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = phase_one_validate(n_strips, strips, in_bytes, *img))
+    return st;
+  uint64_t lo = ~uint64_t(0), hi = 0;
+  for (int i = 0; i < n_strips; ++i) {
+    lo = std::min<uint64_t>(lo, strips[i].offset);
+    hi = std::max<uint64_t>(hi, strips[i].offset + strips[i].bytes);
+  }
+  std::vector<rsx_phase_one_strip> local(strips, strips + n_strips);
+  for (rsx_phase_one_strip& s : local)
+    s.offset -= lo;
+  const size_t span = size_t(hi - lo);
+  rsx_phase_one_job job;
+  std::memset(&job, 0, sizeof job);
+  job.n_strips = n_strips;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  {
+    const void* fn = reinterpret_cast<const void*>(rsx_phase_one_plan_create);
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(&fn);
+    key.insert(key.end(), p, p + sizeof fn);
+    p = reinterpret_cast<const uint8_t*>(&job);
+    key.insert(key.end(), p, p + sizeof job);
+    p = reinterpret_cast<const uint8_t*>(local.data());
+    key.insert(key.end(), p, p + local.size() * sizeof(rsx_phase_one_strip));
+  }
+  job.strips = local.data();
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  LaneGuard lane(ctx, &key);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t out_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y);
+  if (int e = lane.lane->d_in.ensure(span + 64))
+    return e;
+  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  if (span) {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, in + lo, span, hipMemcpyHostToDevice, s));
+  }
+  rsx_plan* plan = nullptr;
+  if (lane.lane->cached_plan && lane.lane->cached_key == key) {
+    plan = lane.lane->cached_plan;
+  } else {
+    if (lane.lane->cached_plan)
+      rsx_plan_destroy(lane.lane->cached_plan);
+    lane.lane->cached_plan = nullptr;
+    if (int st = rsx_phase_one_plan_create(ctx, 1, &job, &plan))
+      return st;
+    lane.lane->cached_plan = plan;
+    lane.lane->cached_key = std::move(key);
+  }
+  int32_t st = RSX_OK;
+  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
+  if (rc == RSX_OK)
+    rc = rsx_plan_results(plan, &st, nullptr);
+  if (rc == RSX_OK || rc == st) {
+    if (strip_status)
+      if (int e = phase_one_plan_row_status(plan->p1, s, 0, strip_status))
+        rc = e;
+  }
+  if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
+    rsx_plan_destroy(lane.lane->cached_plan);
+    lane.lane->cached_plan = nullptr;
+    return rc;
+  }
+  if (rc != RSX_OK)
+    return rc; // (a failing row: nothing goes back into the caller's image)
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
+              size_t(img->dim_x) * 2, size_t(img->dim_y)};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  return download_rects(ctx, lane.lane, s, &dr, 1);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

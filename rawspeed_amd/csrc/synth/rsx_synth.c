@@ -578,3 +578,106 @@ size_t rsx_synth_ljpeg_header(uint8_t* out, int prec, int frame_w, int frame_h,
   *p++ = 0; /* Ah/Al: Pt = 0 */
   return (size_t)(p - out);
 }
+
+/* PhaseOneDecompressor rows (PhaseOneDecompressor.cpp:85-136): one BitStreamerMSB32
+ * stream per row (MSB-first bits stored as little-endian 32-bit words, each row
+ * padded with zeros to a whole word).  A group of 8 pixels (col < w & ~7) starts
+ * with a length header for the even and one for the odd columns: j zeros, a 1 if
+ * j < 5, then bit b selects {8,7,6,9,11,10,5,12,14,13}[2 (j - 1) + b]; a single 1
+ * keeps the length (never at col 0, where any 1 in the prefix is the decoder's
+ * "Can not initialize lengths").  Length 14 stores the 16-bit value; any other L
+ * stores d - 1 + 2^(L-1) in L bits, d = value - previous value of the parity
+ * (mod 2^16).  The last w % 8 pixels are raw 16-bit values.  Per header, drawn
+ * with the seeded generator: keep the length (p_keep / 65536, if it still fits),
+ * 14 (p_raw / 65536), a random fitting length (p_wide / 65536), else the shortest
+ * that fits.  Rows go back to back into `out`; row_off[r] .. row_off[r + 1] is row
+ * r.  Returns the bytes written, 0 on overflow. */
+static const uint8_t p1_lengths[10] = {8, 7, 6, 9, 11, 10, 5, 12, 14, 13};
+
+static int p1_fits(int len, int d) {
+  return len == 14 || (d >= 1 - (1 << (len - 1)) && d <= (1 << (len - 1)));
+}
+
+size_t rsx_synth_phase_one_encode(const uint16_t* samples, size_t row_stride, int w, int h,
+                                  uint32_t p_keep, uint32_t p_raw, uint32_t p_wide,
+                                  uint64_t seed, uint8_t* out, size_t cap, uint64_t* row_off) {
+  uint64_t rs = seed * 0x2545F4914F6CDD1Dull + 7;
+  size_t n = 0;
+  const int gw = w & ~7;
+  for (int row = 0; row < h; ++row) {
+    const uint16_t* v = samples + (size_t)row * row_stride;
+    uint32_t acc = 0;
+    int nacc = 0;
+    row_off[row] = n;
+#define P1_PUT(val, nb)                                                        \
+  do {                                                                         \
+    for (int _i = (nb)-1; _i >= 0; --_i) {                                     \
+      acc = (acc << 1) | (((uint32_t)(val) >> _i) & 1u);                       \
+      if (++nacc == 32) {                                                      \
+        if (n + 4 > cap)                                                       \
+          return 0;                                                            \
+        out[n] = (uint8_t)acc;                                                 \
+        out[n + 1] = (uint8_t)(acc >> 8);                                      \
+        out[n + 2] = (uint8_t)(acc >> 16);                                     \
+        out[n + 3] = (uint8_t)(acc >> 24);                                     \
+        n += 4;                                                                \
+        acc = 0;                                                               \
+        nacc = 0;                                                              \
+      }                                                                        \
+    }                                                                          \
+  } while (0)
+    int pred[2] = {0, 0}, len[2] = {0, 0};
+    for (int col = 0; col < w; ++col) {
+      if (col < gw && (col & 7) == 0) {
+        for (int p = 0; p < 2; ++p) {
+          /* the shortest length that holds the group's four differences of parity p */
+          int need = 5, prev = pred[p];
+          for (int k = p; k < 8; k += 2) {
+            const int d = (int16_t)(uint16_t)(v[col + k] - prev);
+            prev = v[col + k];
+            while (!p1_fits(need, d))
+              ++need;
+          }
+          const uint64_t r = splitmix64(&rs);
+          const uint32_t rk = r & 0xFFFFu, rr = (r >> 16) & 0xFFFFu, rw = (r >> 32) & 0xFFFFu;
+          int L;
+          if (col == 0) {
+            L = need <= 13 && rr >= p_raw ? 13 : 14;
+          } else if (len[p] >= need && rk < p_keep) {
+            P1_PUT(1, 1);
+            continue;
+          } else if (rr < p_raw) {
+            L = 14;
+          } else if (rw < p_wide) {
+            L = need + (int)((r >> 48) % (uint32_t)(15 - need));
+          } else {
+            L = need;
+          }
+          int idx = 0;
+          while (p1_lengths[idx] != L)
+            ++idx;
+          const int j = idx / 2 + 1;
+          P1_PUT(0, j);
+          if (j < 5)
+            P1_PUT(1, 1);
+          P1_PUT(idx & 1, 1);
+          len[p] = L;
+        }
+      }
+      const int L = col >= gw ? 14 : len[col & 1];
+      const int cur = v[col];
+      if (L == 14) {
+        P1_PUT(cur, 16);
+      } else {
+        const int d = (int16_t)(uint16_t)(cur - pred[col & 1]);
+        P1_PUT((uint32_t)(d - 1 + (1 << (L - 1))), L);
+      }
+      pred[col & 1] = cur;
+    }
+    if (nacc)
+      P1_PUT(0, 32 - nacc);
+#undef P1_PUT
+  }
+  row_off[h] = n;
+  return n;
+}

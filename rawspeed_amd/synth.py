@@ -55,6 +55,10 @@ def lib():
         _lib.rsx_synth_sony_arw1_encode.restype = C.c_size_t
         _lib.rsx_synth_sony_arw1_encode.argtypes = [
             C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        _lib.rsx_synth_phase_one_encode.restype = C.c_size_t
+        _lib.rsx_synth_phase_one_encode.argtypes = [
+            C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
+            C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
         _lib.rsx_synth_ljpeg_header.restype = C.c_size_t
         _lib.rsx_synth_ljpeg_header.argtypes = [
             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -292,6 +296,24 @@ def sony_arw1_encode(img):
     if n == 0:
         raise ValueError("Sony ARW1 encode failed")
     return out[:n].copy(), bits.value
+
+
+def phase_one_encode(img, choices=(0.0, 0.0, 0.0), seed=0):
+    """img: (h, w) uint16; PhaseOneDecompressor.cpp:85-136 rows, one byte string per row.
+    choices = (p_keep, p_raw, p_wide): per length header the probability of keeping the
+    previous length (if it still fits), of a raw 16-bit group, and of a random length among
+    those that fit; otherwise the shortest that fits.  (0, 0, 0) is a plain encoder."""
+    img = np.ascontiguousarray(img, dtype=np.uint16)
+    h, w = img.shape
+    p = [min(65536, max(0, int(round(c * 65536)))) for c in choices]
+    cap = h * (w * 18 // 8 + 64) + 64
+    out = np.empty(cap, dtype=np.uint8)
+    off = np.zeros(h + 1, dtype=np.uint64)
+    n = lib().rsx_synth_phase_one_encode(img.ctypes.data, w, w, h, p[0], p[1], p[2], seed,
+                                         out.ctypes.data, cap, off.ctypes.data)
+    if n == 0:
+        raise ValueError("Phase One encode failed")
+    return [out[int(off[r]):int(off[r + 1])].tobytes() for r in range(h)]
 
 
 def huff_tables(*pairs, fix16=False):

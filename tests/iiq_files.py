@@ -1,0 +1,273 @@
+"""TEST INFRASTRUCTURE: synthetic Phase One IIQ files and a model of the GPU decode.
+
+  iiq_file()       a whole IIQ "L" file that goes through the reference's front door
+                   (RawParser -> TiffParser -> IiqDecoder::decodeRawInternal,
+                   decoders/IiqDecoder.cpp:130-280 -> PhaseOneDecompressor): a TIFF root IFD
+                   with Make / Model, "IIII" at byte 8, the entries offset at byte 16 (relative
+                   to byte 8), entries 0x107 (white balance, read after the decode), 0x108,
+                   0x109, 0x10e = 3, 0x10f (raw data) and 0x21c (row offsets, shuffled)
+  iiq_strips()     (raw_data, strips) exactly as IiqDecoder::computeSripes cuts them
+                   (IiqDecoder.cpp:75-118): a strip runs from its offset to the next larger
+                   one, the last to the end of raw_data -- what the drop-in hunk hands over
+  model_row()      the kernel's decomposition in numpy terms: the header walk with a
+                   checkpoint every 8 groups, 64-pixel chunks decoded from their checkpoint,
+                   a segmented scan mod 2^16 per column parity, the over-read closed form,
+                   zeros behind the strip
+"""
+import struct
+
+import numpy as np
+
+from rawspeed_amd import synth
+
+LENGTHS = (8, 7, 6, 9, 11, 10, 5, 12, 14, 13)  # PhaseOneDecompressor.cpp:93-94
+MAX_W, MAX_H = 11976, 8854
+RSX_OK, RSX_ERR_IO, RSX_ERR_BAD_HUFFMAN_CODE, RSX_ERR_INPUT_OVERFLOW = 0, 2, 3, 5
+
+
+# ---------------------------------------------------------------------------------------
+# images and rows
+# ---------------------------------------------------------------------------------------
+def sample_image(rng, w, h):
+    """Rows whose differences change scale every few pixels (every length gets used), with
+    the odd jump that only a raw group can hold."""
+    img = np.empty((h, w), dtype=np.uint16)
+    for r in range(h):
+        scale = 2 ** rng.integers(0, 14, size=(w + 7) // 8 + 1)
+        d = rng.integers(-1, 2, size=w) * (rng.random(w) * np.repeat(scale, 8)[:w]).astype(np.int64)
+        row = (int(rng.integers(0, 65536)) + np.cumsum(d)) & 0xFFFF
+        img[r] = row
+    return img
+
+
+def encode(img, seed, choices=(0.25, 0.1, 0.4)):
+    return synth.phase_one_encode(img, choices, seed)
+
+
+# ---------------------------------------------------------------------------------------
+# the file
+# ---------------------------------------------------------------------------------------
+def _ifd(entries, base):
+    """TIFF IFD at file offset `base`: [(tag, type, count, payload bytes)]"""
+    out = bytearray(struct.pack("<H", len(entries)))
+    extra = base + 2 + 12 * len(entries) + 4
+    tail = bytearray()
+    for tag, typ, count, data in sorted(entries):
+        if len(data) <= 4:
+            out += struct.pack("<HHI", tag, typ, count) + data.ljust(4, b"\0")
+        else:
+            out += struct.pack("<HHII", tag, typ, count, extra + len(tail))
+            tail += data + (b"\0" if len(data) & 1 else b"")
+    out += struct.pack("<I", 0)
+    return bytes(out + tail)
+
+
+def iiq_file(rows, width, rng=None, shuffle=True, gap_max=0, tail_gap=0, height=None,
+             make="Phase One A/S", model="IQ180", wb=(2.0, 1.0, 1.5), fmt=3):
+    """rows: one byte string per image row.  The rows go into raw_data in a random order
+    (shuffle), each followed by 0 .. gap_max padding bytes (part of its strip), raw_data
+    ends with tail_gap more.  `height` (default len(rows)) is what tag 0x109 says."""
+    h = len(rows) if height is None else height
+    order = list(range(len(rows)))
+    if shuffle and rng is not None:
+        rng.shuffle(order)
+    raw = bytearray()
+    offsets = [0] * len(rows)
+    for r in order:
+        offsets[r] = len(raw)
+        raw += rows[r]
+        if gap_max and rng is not None:
+            raw += rng.integers(0, 256, size=int(rng.integers(0, gap_max + 1)), dtype=np.uint8).tobytes()
+    raw += b"\xA5" * tail_gap
+    tiff = _ifd([(271, 2, len(make) + 1, make.encode() + b"\0"),
+                 (272, 2, len(model) + 1, model.encode() + b"\0")], 24)
+    pos = 24 + len(tiff)
+    pos += -pos % 4
+    n_entries = 6
+    ent_abs = pos
+    wb_abs = ent_abs + 8 + 16 * n_entries
+    off_abs = wb_abs + 12
+    raw_abs = off_abs + 4 * len(offsets)
+    rel = lambda a: a - 8  # noqa: E731  (IIQ offsets are relative to byte 8)
+    entries = [(0x107, 12, rel(wb_abs)), (0x108, 4, width), (0x109, 4, h), (0x10E, 4, fmt),
+               (0x10F, len(raw), rel(raw_abs)), (0x21C, 4 * len(offsets), rel(off_abs))]
+    out = bytearray(raw_abs + len(raw))
+    out[0:8] = b"II" + struct.pack("<HI", 42, 24)
+    out[8:12] = b"IIII"
+    struct.pack_into("<II", out, 16, rel(ent_abs), 0)
+    out[24:24 + len(tiff)] = tiff
+    struct.pack_into("<II", out, ent_abs, n_entries, 0)
+    for i, (tag, length, data) in enumerate(entries):
+        struct.pack_into("<IIII", out, ent_abs + 8 + 16 * i, tag, 0, length, data)
+    struct.pack_into("<3f", out, wb_abs, *wb)
+    struct.pack_into("<%dI" % len(offsets), out, off_abs, *offsets)
+    out[raw_abs:] = raw
+    return np.frombuffer(bytes(out), dtype=np.uint8).copy()
+
+
+def iiq_strips(blob):
+    """(raw_data bytes, [(row, offset, bytes)], width, height), the strips sorted by row --
+    IiqDecoder::decodeRawInternal's parse (:130-260) and computeSripes (:75-118)."""
+    b = bytes(blob)
+    base = 8
+    ent = base + struct.unpack_from("<I", b, 16)[0]
+    count = struct.unpack_from("<I", b, ent)[0]
+    width = height = 0
+    raw = offs = None
+    for i in range(count):
+        tag, _, length, data = struct.unpack_from("<IIII", b, ent + 8 + 16 * i)
+        if tag == 0x108:
+            width = data
+        elif tag == 0x109:
+            height = data
+        elif tag == 0x10F:
+            raw = b[base + data:base + data + length]
+        elif tag == 0x21C:
+            offs = (base + data, length)
+    row_off = list(struct.unpack_from("<%dI" % height, b, offs[0]))
+    pts = sorted([(o, r) for r, o in enumerate(row_off)] + [(len(raw), height)])
+    if len({o for o, _ in pts}) != len(pts):
+        raise ValueError("Two identical offsets found")
+    strips = [(r, o, pts[i + 1][0] - o) for i, (o, r) in enumerate(pts[:-1])]
+    return raw, sorted(strips), width, height
+
+
+def damage(rows, row, how, rng):
+    """A copy of `rows` with row `row` damaged: 'truncate' (cut to a few bytes more than its
+    first pixels need: the over-read), 'col0' (the first bit set: a 1 inside the col-0
+    length prefix), 'short' (1 to 3 bytes; a strip only if no padding follows it)."""
+    rows = list(rows)
+    r = bytearray(rows[row])
+    if how == "truncate":
+        r = r[:max(4, len(r) // 3 // 4 * 4)]
+    elif how == "col0":
+        r[3] |= 0x80  # (the first bit of the stream: the top bit of the first LE word)
+    elif how == "short":
+        r = r[:int(rng.integers(1, 4))]
+    else:
+        raise ValueError(how)
+    rows[row] = bytes(r)
+    return rows
+
+
+# ---------------------------------------------------------------------------------------
+# the model of the kernel
+# ---------------------------------------------------------------------------------------
+def row_words(width):
+    """p1_row_words: the most bits a row can read, in words, + 2"""
+    return ((width >> 3) * 140 + (width & 7) * 16) // 32 + 2
+
+
+def _words(strip, width):
+    n = row_words(width)
+    b = bytes(strip[:4 * n]).ljust(4 * n, b"\0")  # zeros behind the strip
+    return [int(x) for x in np.frombuffer(b, dtype="<u4")]
+
+
+def _peek(W, q):
+    k = q >> 5
+    v = (W[k] << 32) | W[k + 1]
+    return ((v << (q & 31)) >> 32) & 0xFFFFFFFF
+
+
+def _len(w, cur):
+    """(bits taken, new length, a 1 inside the five-bit prefix)"""
+    z = 32 - w.bit_length()
+    if z == 0:
+        return 1, cur, True
+    j = min(z, 5)
+    used = j + 1 if z < 5 else 5
+    b = ((w << used) >> 31) & 1
+    return used + 1, LENGTHS[2 * (j - 1) + b], z < 5
+
+
+def _bits(L):
+    return 16 if L == 14 else L
+
+
+def model_walk(strip, width):
+    """The header walk of a row: (status, checkpoints [(bit offset, len0, len1)] per 64
+    pixels, start bit of the last pixel)."""
+    W = _words(strip, width)
+    ng, tail = width >> 3, width & 7
+    st = RSX_ERR_IO if len(strip) < 4 else RSX_OK
+    pos, l0, l1 = 0, 8, 8
+    cps = []
+    c_last = 16 * (width - 1)
+    for g in range(ng):
+        if g % 8 == 0:
+            cps.append((pos, l0, l1))
+        w = _peek(W, pos)
+        h0, l0, o0 = _len(w, l0)
+        h1, l1, o1 = _len((w << h0) & 0xFFFFFFFF, l1)
+        h = h0 + h1
+        if g == 0 and (o0 or o1) and st == RSX_OK:
+            st = RSX_ERR_BAD_HUFFMAN_CODE
+        c_last = pos + h + 4 * _bits(l0) + 3 * _bits(l1)
+        pos += h + 4 * (_bits(l0) + _bits(l1))
+    if tail:
+        if ng % 8 == 0:
+            cps.append((pos, 14, 14))
+        c_last = pos + 16 * (tail - 1)
+    # fill(32) before every pixel; the refill at byte 4 ceil(c / 32) throws past size + 8
+    if st == RSX_OK and 4 * ((c_last + 31) // 32) > len(strip) + 8:
+        st = RSX_ERR_INPUT_OVERFLOW
+    return st, cps, c_last
+
+
+def _combine(a, b):
+    return b if b & 0x10000 else (a & 0x10000) | ((a + b) & 0xFFFF)
+
+
+def model_row(strip, width):
+    """(status, pixels) of one row, computed the way p1_row_kernel does."""
+    st, cps, _ = model_walk(strip, width)
+    W = _words(strip, width)
+    gw = width & ~7
+    local, firsts, aggs = [], [], []
+    for i, (pos, l0, l1) in enumerate(cps):
+        c0 = 64 * i
+        acc, first, vals = [0, 0], [64, 64], []
+        for k in range(min(64, width - c0)):
+            col = c0 + k
+            w = _peek(W, pos)
+            h = 0
+            if col >= gw:
+                l0 = l1 = 14
+            elif k % 8 == 0:
+                h0, l0, _ = _len(w, l0)
+                h1, l1, _ = _len((w << h0) & 0xFFFFFFFF, l1)
+                h = h0 + h1
+                w = (w << h) & 0xFFFFFFFF
+            L = l1 if k & 1 else l0
+            p = k & 1
+            if L == 14:
+                acc[p] = w >> 16
+                first[p] = min(first[p], k)
+                pos += h + 16
+            else:
+                acc[p] = (acc[p] + (w >> (32 - L)) + 1 - (1 << (L - 1))) & 0xFFFFFFFF
+                pos += h + L
+            vals.append(acc[p] & 0xFFFF)
+        local.append(vals)
+        firsts.append(first)
+        aggs.append([(acc[p] & 0xFFFF) | (0x10000 if first[p] < 64 else 0) for p in (0, 1)])
+    out = np.zeros(width, dtype=np.uint16)
+    carry = [0, 0]  # exclusive segmented scan over the chunks
+    for i, vals in enumerate(local):
+        for k, v in enumerate(vals):
+            p = k & 1
+            out[64 * i + k] = (v + (carry[p] & 0xFFFF if k < firsts[i][p] else 0)) & 0xFFFF
+        carry = [_combine(carry[p], aggs[i][p]) for p in (0, 1)]
+    return st, out
+
+
+def model_file(blob):
+    """(status of the lowest failing row or RSX_OK, image (h, w), per-row statuses)"""
+    raw, strips, width, height = iiq_strips(blob)
+    img = np.zeros((height, width), dtype=np.uint16)
+    rows = [RSX_OK] * height
+    for r, off, size in strips:
+        rows[r], img[r] = model_row(raw[off:off + size], width)
+    bad = [s for s in rows if s != RSX_OK]
+    return (bad[0] if bad else RSX_OK), img, rows

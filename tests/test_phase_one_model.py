@@ -1,0 +1,158 @@
+"""PhaseOneDecompressor: the model of the GPU decomposition (tests/iiq_files.py) against the
+unmodified reference's whole-file decode (RawParser -> IiqDecoder -> PhaseOneDecompressor),
+and rsx_phase_one_validate against the reference's outcome at the constructor's edges.  No
+GPU needed; the reference comparisons need oracle/_ref (the stored answers of the `ref`
+fixture cannot decode new files)."""
+import numpy as np
+import pytest
+
+import iiq_files as I
+from oracle_lib import Ref
+from rawspeed_amd import abi, capi, synth
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return Ref()
+
+
+def _random_file(seed):
+    rng = np.random.default_rng([0x1119, seed])
+    w = int(rng.choice([2, 4, 6, 8, 10, 12, 14, 16, 18, 22, 30, 64, 66, 126, 128, 130, 134,
+                        2 * int(rng.integers(1, 200))]))
+    h = int(rng.integers(1, 6))
+    img = I.sample_image(rng, w, h)
+    choices = [(0.0, 0.0, 0.0), (0.25, 0.1, 0.4), (0.6, 0.3, 0.9), (0.0, 1.0, 0.0)][seed % 4]
+    rows = synth.phase_one_encode(img, choices, seed)
+    blob = I.iiq_file(rows, w, rng, shuffle=True, gap_max=int(rng.choice([0, 3, 17])),
+                      tail_gap=int(rng.choice([0, 5])))
+    return img, rows, blob, rng
+
+
+@pytest.mark.parametrize("chunk", range(6))
+@pytest.mark.ref
+@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built")
+def test_model_matches_reference_on_random_files(ref, chunk):
+    residues = set()
+    for seed in range(60 * chunk, 60 * chunk + 60):
+        img, rows, blob, _ = _random_file(seed)
+        h, w = img.shape
+        residues.add(w % 8 if w >= 8 else -w)
+        st, dec = ref.decode_file(blob)
+        assert st == 0, (seed, w, h, ref.last_error())
+        got = dec.u16()[:h, :w]
+        assert np.array_equal(got, img), seed
+        mst, mimg, mrows = I.model_file(blob)
+        assert mst == 0 and mrows == [0] * h, (seed, mrows)
+        assert np.array_equal(mimg, img), seed
+    assert {0, 2, 4, 6} <= residues
+
+
+def _headers(rows, width):
+    """(length codes used, 'keep' headers, raw groups) over the rows' group headers"""
+    used, keeps, raws = set(), 0, 0
+    for r in rows:
+        W = I._words(r, width)
+        pos, l0, l1 = 0, 8, 8
+        for g in range(width >> 3):
+            w = I._peek(W, pos)
+            h0, l0, _ = I._len(w, l0)
+            h1, l1, _ = I._len((w << h0) & 0xFFFFFFFF, l1)
+            keeps += (h0 == 1) + (h1 == 1)
+            used |= {l0, l1}
+            raws += (l0 == 14) + (l1 == 14)
+            pos += h0 + h1 + 4 * (I._bits(l0) + I._bits(l1))
+    return used, keeps, raws
+
+
+def test_encoder_exercises_every_length_keep_and_raw():
+    rng = np.random.default_rng(44)
+    img = I.sample_image(rng, 512, 8)
+    used, keeps, raws = _headers(synth.phase_one_encode(img, (0.3, 0.1, 0.6), 3), 512)
+    assert used == set(I.LENGTHS) and keeps > 0 and raws > 0
+    # a plain encoder: shortest lengths, never a keep; lossless either way (the model)
+    rows = synth.phase_one_encode(img, (0.0, 0.0, 0.0), 3)
+    assert _headers(rows, 512)[1] == 0
+    for r in range(8):
+        assert np.array_equal(I.model_row(rows[r], 512)[1], img[r])
+
+
+@pytest.mark.parametrize("how,status,text", [
+    ("truncate", I.RSX_ERR_INPUT_OVERFLOW, "Buffer overflow read in BitStreamer"),
+    ("col0", I.RSX_ERR_BAD_HUFFMAN_CODE, "Can not initialize lengths"),
+    ("short", I.RSX_ERR_IO, "smaller than MaxProcessBytes"),
+])
+@pytest.mark.ref
+@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built")
+def test_damaged_rows_fail_like_the_reference(ref, how, status, text):
+    for seed in range(12):
+        rng = np.random.default_rng([0x1DA, seed])
+        w, h = 2 * int(rng.integers(24, 300)), int(rng.integers(2, 7))
+        img = I.sample_image(rng, w, h)
+        bad = int(rng.integers(0, h))
+        rows = I.damage(synth.phase_one_encode(img, (0.25, 0.1, 0.4), seed), bad, how, rng)
+        blob = I.iiq_file(rows, w, rng, gap_max=0 if how == "short" else int(rng.choice([0, 6])))
+        st, _ = ref.decode_file(blob)
+        assert st != 0 and text in ref.last_error(), (seed, ref.last_error())
+        mst, _, mrows = I.model_file(blob)
+        want = [0] * h
+        want[bad] = status
+        assert (mst, mrows) == (status, want), seed
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built")
+def test_over_read_closed_form_at_every_size(ref):
+    """A row cut to every size from 4 bytes up: the reference fails iff
+    4 * ceil(c_last / 32) > size + 8 (c_last: the start bit of the last pixel)."""
+    for w, seed in ((2, 1), (6, 2), (8, 3), (16, 4), (70, 5), (136, 6)):
+        rng = np.random.default_rng([0x0C1, seed])
+        img = I.sample_image(rng, w, 1)
+        row = synth.phase_one_encode(img, (0.2, 0.2, 0.3), seed)[0]
+        _, _, c_last = I.model_walk(row, w)
+        for size in range(4, len(row) + 1):
+            cut = row[:size]
+            st, _ = ref.decode_file(I.iiq_file([cut], w))
+            mst, mimg, _ = I.model_file(I.iiq_file([cut], w))
+            assert (st != 0) == (4 * ((c_last + 31) // 32) > size + 8), (w, size)
+            assert (st != 0) == (mst != 0), (w, size)
+            if size == len(row):
+                assert st == 0 and np.array_equal(mimg[0], img[0])
+
+
+def _view(w, h):
+    return abi.Image(None, max(2, 2 * w), w, h, 1, 1)
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("w,h", [(101, 2), (11976, 2), (11977, 2), (2, 8854), (2, 8855)])
+def test_validate_agrees_with_the_reference_at_the_edges(ref, w, h):
+    rng = np.random.default_rng([0x7A1, w, h])
+    img = I.sample_image(rng, w, h) if w * h < 50000 else rng.integers(0, 65536, (h, w)).astype(np.uint16)
+    blob = I.iiq_file(synth.phase_one_encode(img, (0.0, 0.0, 0.0), 1), w, rng)
+    st, _ = ref.decode_file(blob)
+    raw, strips, fw, fh = I.iiq_strips(blob)
+    v = capi.phase_one_validate(strips, len(raw), _view(fw, fh))
+    assert (st == 0) == (v == abi.RSX_OK), (w, h, st, v, ref.last_error())
+    if v != abi.RSX_OK:
+        assert v == abi.RSX_ERR_INVALID_ARG
+
+
+def test_validate_rejects_bad_strip_tables():
+    view = _view(16, 3)
+    good = [(0, 0, 10), (1, 10, 10), (2, 20, 10)]
+    assert capi.phase_one_validate(good, 30, view) == abi.RSX_OK
+    assert capi.phase_one_validate(good[::-1], 30, view) == abi.RSX_OK  # (any order)
+    assert capi.phase_one_validate(good, 29, view) == abi.RSX_ERR_INVALID_ARG  # outside the input
+    assert capi.phase_one_validate(good[:2], 30, view) == abi.RSX_ERR_INVALID_ARG  # a row missing
+    assert capi.phase_one_validate([(0, 0, 10), (0, 10, 10), (2, 20, 10)], 30, view) \
+        == abi.RSX_ERR_INVALID_ARG  # a row twice
+    assert capi.phase_one_validate([(0, 0, 10), (1, 10, 10), (3, 20, 10)], 30, view) \
+        == abi.RSX_ERR_INVALID_ARG  # no such row
+    assert capi.phase_one_validate(good, 30, abi.Image(None, 32, 16, 3, 3, 1)) \
+        == abi.RSX_ERR_INVALID_ARG  # cpp 3
+    assert capi.phase_one_validate(good, 30, abi.Image(None, 30, 16, 3, 1, 1)) \
+        == abi.RSX_ERR_INVALID_ARG  # pitch < width
+    # (short strips are a per-row status of the decode, not a validation error)
+    assert capi.phase_one_validate([(0, 0, 0), (1, 0, 2), (2, 2, 28)], 30, view) == abi.RSX_OK
