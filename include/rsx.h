@@ -485,6 +485,61 @@ int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes, i
                              int32_t* strip_status);
 
 /* ------------------------------------------------------------------------ */
+/* 3i. SonyArw2Decompressor                                                  */
+/*    replaces SonyArw2Decompressor::decompress()                            */
+/*    (decompressors/SonyArw2Decompressor.cpp:136-148 -> decompressRow       */
+/*    :57-120 for every row).  ArwDecoder keeps its host work: the container */
+/*    (ArwDecoder.cpp:165-260), decodeCurve (:147-162) and the curve guard   */
+/*    (common/RawImage.h:355-383) that installs mRaw->table before the call. */
+/*    Row y is exactly the bytes [y w, (y + 1) w) (a BitStreamerLSB); its    */
+/*    first 24 bits seed the dither generator.  16-byte blocks of 16 pixels; */
+/*    block b holds the columns 32 (b >> 1) + (b & 1) + 2 i, i = 0..15:      */
+/*    bits 0-10 max, 11-21 min, 22-25 imax, 26-29 imin, fourteen 7-bit       */
+/*    fields from bit 30, taken in order by the pixels i != imax, imin:      */
+/*    p = min(0x7ff, (field << sh) + min), sh = the least s in 0..4 with     */
+/*    s == 4 or (0x80 << s) > max - min; pixel imax = max, pixel imin = min. */
+/*    The value stored is setWithLookUp(p << 1) (RawImage.h:335-353) with    */
+/*    the table `desc` describes -- mRaw->table as TableLookUp holds it      */
+/*    (common/TableLookUp.cpp), compare decode8BitRaw<false>'s lut in 1b:    */
+/*      RSX_ARW2_TABLE_NONE    no table (uncorrectedRawValues): p << 1       */
+/*      RSX_ARW2_TABLE_PLAIN   table[p << 1] (4096 entries read)             */
+/*      RSX_ARW2_TABLE_DITHER  base = table[2 v], delta = table[2 v + 1],    */
+/*                             v = p << 1 (8192 entries read): base + ((delta */
+/*                             (r & 2047) + 1024) >> 12), then r = 15700     */
+/*                             (r & 65535) + (r >> 16), once a pixel in      */
+/*                             decode order (pixel i of block b: step 16 b+i)*/
+/*    The table is copied during the call (or at plan creation).             */
+/*    rsx_sony_arw2_validate: desc NULL, an unknown table_mode, or a NULL    */
+/*    table with a mode other than NONE -> RSX_ERR_INVALID_ARG; then the     */
+/*    constructor's checks in its order (:40-54): cpp 1, dim > 0,            */
+/*    dim_x % 32 == 0, dim_x <= 9600, dim_y <= 6376 (and pitch_bytes >=      */
+/*    2 dim_x) -> RSX_ERR_INVALID_ARG; in_bytes < dim_x dim_y                */
+/*    (input.peekStream) -> RSX_ERR_IO.  Bytes behind dim_x dim_y are not    */
+/*    read; a job consumes exactly dim_x dim_y bytes.                        */
+/*    A block with imax == imin fails its row ("ARW2 invariant failed",      */
+/*    :85-86; row status RSX_ERR_INVALID_ARG), and any failing row fails the */
+/*    call ("Too many errors", :143-147 -> RSX_ERR_TILE_ERRORS).  Through    */
+/*    host pointers the caller's image is then left untouched.               */
+/*    `row_status` (may be NULL) gets one status per image row.              */
+/* ------------------------------------------------------------------------ */
+enum {
+  RSX_ARW2_TABLE_NONE = 0,
+  RSX_ARW2_TABLE_PLAIN = 1,
+  RSX_ARW2_TABLE_DITHER = 2
+};
+
+typedef struct rsx_sony_arw2_desc {
+  int32_t table_mode;    /* RSX_ARW2_TABLE_* */
+  int32_t reserved;
+  const uint16_t* table; /* TableLookUp::tables: 4096 (PLAIN) / 8192 (DITHER) entries */
+} rsx_sony_arw2_desc;
+
+int rsx_sony_arw2_validate(const rsx_sony_arw2_desc* desc, const rsx_image* img,
+                           size_t in_bytes);
+int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* desc, const uint8_t* in,
+                             size_t in_bytes, const rsx_image* img, int32_t* row_status);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -635,6 +690,15 @@ typedef struct rsx_phase_one_job {
   rsx_image img; /* .data ignored */
 } rsx_phase_one_job;
 
+/* row y of a job starts at in_offset + y dim_x; its table is copied at plan creation */
+typedef struct rsx_sony_arw2_job {
+  rsx_sony_arw2_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_sony_arw2_job;
+
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */
@@ -664,6 +728,8 @@ int rsx_hasselblad_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_hasselblad_jo
 int rsx_sony_arw1_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw1_job* jobs,
                               rsx_plan** out_plan);
 int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs,
+                              rsx_plan** out_plan);
+int rsx_sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* jobs,
                               rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,

@@ -203,6 +203,30 @@ class PhaseOneJob(C.Structure):
                 ("img_offset", C.c_uint64), ("img", Image)]
 
 
+ARW2_TABLE_NONE, ARW2_TABLE_PLAIN, ARW2_TABLE_DITHER = 0, 1, 2
+
+
+class SonyArw2Desc(C.Structure):
+    _fields_ = [("table_mode", C.c_int32), ("reserved", C.c_int32),
+                ("table", C.POINTER(C.c_uint16))]
+
+
+class SonyArw2Job(C.Structure):
+    _fields_ = [("desc", SonyArw2Desc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def sony_arw2_desc(mode, table=None):
+    """(desc, keep-alive array): `table` as TableLookUp holds it (uint16; None for NONE)"""
+    d = SonyArw2Desc()
+    d.table_mode = mode
+    arr = None
+    if table is not None:
+        arr = np.ascontiguousarray(table, dtype=np.uint16)
+        d.table = arr.ctypes.data_as(C.POINTER(C.c_uint16))
+    return d, arr
+
+
 def phase_one_strips(table):
     """[(row, offset, bytes)] -> a ctypes array of rsx_phase_one_strip"""
     arr = (PhaseOneStrip * max(1, len(table)))()

@@ -31,6 +31,7 @@ EXPORTS = [
     "rsx_samsung_v2_validate", "rsx_samsung_v2_decompress", "rsx_samsung_v2_plan_create",
     "rsx_sony_arw1_validate", "rsx_sony_arw1_decompress", "rsx_sony_arw1_plan_create",
     "rsx_phase_one_validate", "rsx_phase_one_decompress", "rsx_phase_one_plan_create",
+    "rsx_sony_arw2_validate", "rsx_sony_arw2_decompress", "rsx_sony_arw2_plan_create",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
@@ -95,6 +96,9 @@ def lib():
         L.rsx_phase_one_validate.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsx_phase_one_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_sony_arw2_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_sony_arw2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -114,7 +118,8 @@ def lib():
                      "rsx_pentax_plan_create", "rsx_samsung_v1_plan_create",
                      "rsx_samsung_v2_plan_create",
                      "rsx_sraw_plan_create", "rsx_hasselblad_plan_create",
-                     "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create"):
+                     "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
+                     "rsx_sony_arw2_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -141,6 +146,14 @@ def phase_one_validate(strips, in_bytes, img_view):
     """rsx_phase_one_validate; strips: [(row, offset, bytes)]"""
     arr = abi.phase_one_strips(strips)
     return lib().rsx_phase_one_validate(len(strips), arr, in_bytes, C.byref(img_view))
+
+
+def sony_arw2_validate(mode, table, img_view, in_bytes):
+    """rsx_sony_arw2_validate; mode None passes a NULL desc"""
+    if mode is None:
+        return lib().rsx_sony_arw2_validate(None, C.byref(img_view), in_bytes)
+    d, keep = abi.sony_arw2_desc(mode, table)
+    return lib().rsx_sony_arw2_validate(C.byref(d), C.byref(img_view), in_bytes)
 
 
 def _u8(a):
@@ -293,6 +306,15 @@ class Context:
                                             C.byref(img_view), rows)
         return st, list(rows)[:img_view.dim_y]
 
+    def sony_arw2_decompress(self, mode, table, data, img_view, rows=True):
+        """Returns (status, per-row statuses or None)."""
+        a = _u8(data)
+        d, keep = abi.sony_arw2_desc(mode, table)
+        rs = (C.c_int32 * max(1, img_view.dim_y))() if rows else None
+        st = lib().rsx_sony_arw2_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
+                                            C.byref(img_view), rs)
+        return st, (list(rs)[:img_view.dim_y] if rows else None)
+
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
@@ -351,6 +373,10 @@ class Context:
     def phase_one_plan(self, jobs):
         """jobs: abi.PhaseOneJob (their strip arrays are copied at plan creation)"""
         return Plan(self, "rsx_phase_one_plan_create", abi.PhaseOneJob, jobs)
+
+    def sony_arw2_plan(self, jobs):
+        """jobs: abi.SonyArw2Job (their tables are copied at plan creation)"""
+        return Plan(self, "rsx_sony_arw2_plan_create", abi.SonyArw2Job, jobs)
 
     def pentax_plan(self, jobs):
         return Plan(self, "rsx_pentax_plan_create", abi.PentaxJob, jobs)

@@ -9,6 +9,7 @@
 #include "rsx_ljpeg_dev.h"
 #include "rsx_phase_one.h"
 #include "rsx_samsung_v2.h"
+#include "rsx_sony_arw2.h"
 
 #include <algorithm>
 #include <atomic>
@@ -23,7 +24,8 @@ using namespace rsx;
 // ---------------------------------------------------------------------------
 namespace {
 
-enum PlanKind { PLAN_UNPACK = 0, PLAN_LJPEG = 1, PLAN_SRAW = 2, PLAN_SV2 = 3, PLAN_P1 = 4 };
+enum PlanKind { PLAN_UNPACK = 0, PLAN_LJPEG = 1, PLAN_SRAW = 2, PLAN_SV2 = 3, PLAN_P1 = 4,
+               PLAN_A2 = 5 };
 
 struct UnpackLaunch {
   int mode = UNPACK_MODE_PACKED;
@@ -50,6 +52,8 @@ struct rsx_plan {
   std::unique_ptr<LJpegPlan, LJpegPlanDeleter> ljpeg;
   Sv2Plan* sv2 = nullptr; // PLAN_SV2
   P1Plan* p1 = nullptr;   // PLAN_P1
+  Arw2Plan* a2 = nullptr; // PLAN_A2
+  std::vector<uint32_t> a2_consumed;
   // PLAN_SRAW
   DeviceBuffer d_sraw_jobs, d_sraw_starts;
   int n_sraw = 0;
@@ -920,6 +924,8 @@ extern "C" int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
   if (!plan->timing) {
     if (plan->kind == PLAN_P1)
       return phase_one_plan_run(plan->p1, in_dev, out_dev, s, nullptr);
+    if (plan->kind == PLAN_A2)
+      return sony_arw2_plan_run(plan->a2, in_dev, out_dev, s, nullptr);
     return sv2 ? samsung_v2_plan_run(plan->sv2, in_dev, out_dev, s, nullptr)
                : ljpeg_plan_run(plan->ljpeg.get(), in_dev, out_dev, s, nullptr);
   }
@@ -930,6 +936,8 @@ extern "C" int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
   plan->ktimer_pending = true;
   if (plan->kind == PLAN_P1)
     return phase_one_plan_run(plan->p1, in_dev, out_dev, s, plan->ktimer.get());
+  if (plan->kind == PLAN_A2)
+    return sony_arw2_plan_run(plan->a2, in_dev, out_dev, s, plan->ktimer.get());
   return sv2 ? samsung_v2_plan_run(plan->sv2, in_dev, out_dev, s, plan->ktimer.get())
              : ljpeg_plan_run(plan->ljpeg.get(), in_dev, out_dev, s, plan->ktimer.get());
 }
@@ -967,6 +975,12 @@ extern "C" int rsx_plan_results(rsx_plan* plan, int32_t* job_status,
         job_consumed[i] = 0;
     return phase_one_plan_results(plan->p1, plan->last_stream, plan->ran, job_status);
   }
+  if (plan->kind == PLAN_A2) {
+    if (job_consumed) // (a job reads exactly its dim_x * dim_y bytes, when it was accepted)
+      for (int i = 0; i < plan->n_jobs; ++i)
+        job_consumed[i] = plan->a2_consumed[i];
+    return sony_arw2_plan_results(plan->a2, plan->last_stream, plan->ran, job_status);
+  }
   return ljpeg_plan_results(plan->ljpeg.get(), plan->last_stream, plan->ran,
                             job_status, job_consumed);
 }
@@ -979,7 +993,8 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
   plan->ktotals.clear();
   plan->kruns = 0;
   plan->ktimer_pending = false;
-  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1)
+  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1 ||
+      plan->kind == PLAN_A2)
     return RSX_OK; // its events are created on the first timed run
   if (plan->timing && plan->events.size() < 64) {
     // event creation is slow on ROCm: pre-create the pool outside timed regions
@@ -998,7 +1013,8 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
 
 extern "C" int rsx_plan_kernel_table(rsx_plan* plan, int cap, const char** names,
                                      double* avg_ms, int* n_kernels, int* n_runs) {
-  if (!plan || (plan->kind != PLAN_LJPEG && plan->kind != PLAN_SV2 && plan->kind != PLAN_P1) ||
+  if (!plan || (plan->kind != PLAN_LJPEG && plan->kind != PLAN_SV2 && plan->kind != PLAN_P1 &&
+                plan->kind != PLAN_A2) ||
       !plan->timing)
     return RSX_ERR_INVALID_ARG;
   rsx_ctx* ctx = plan->ctx;
@@ -1032,7 +1048,8 @@ extern "C" int rsx_plan_kernel_time(rsx_plan* plan, const char** kernel_name,
   rsx_ctx* ctx = plan->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1) {
+  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1 ||
+      plan->kind == PLAN_A2) {
     // the dominant kernel = the one with the largest share of the timed runs
     if (int st = fold_kernel_timer(plan))
       return st;
@@ -1101,6 +1118,7 @@ extern "C" void rsx_plan_destroy(rsx_plan* plan) {
     plan->ljpeg.reset();
     samsung_v2_plan_destroy(plan->sv2);
     phase_one_plan_destroy(plan->p1);
+    sony_arw2_plan_destroy(plan->a2);
   }
   delete plan;
 }
@@ -3003,6 +3021,117 @@ extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t 
   if (rc == RSX_OK || rc == st) {
     if (strip_status)
       if (int e = phase_one_plan_row_status(plan->p1, s, 0, strip_status))
+        rc = e;
+  }
+  if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
+    rsx_plan_destroy(lane.lane->cached_plan);
+    lane.lane->cached_plan = nullptr;
+    return rc;
+  }
+  if (rc != RSX_OK)
+    return rc; // (a failing row: nothing goes back into the caller's image)
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
+              size_t(img->dim_x) * 2, size_t(img->dim_y)};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  return download_rects(ctx, lane.lane, s, &dr, 1);
+}
+
+// ---------------------------------------------------------------------------
+// SonyArw2Decompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_sony_arw2_validate(const rsx_sony_arw2_desc* desc, const rsx_image* img,
+                                      size_t in_bytes) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return sony_arw2_validate(desc, *img, in_bytes);
+}
+
+extern "C" int rsx_sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* jobs,
+                                         rsx_plan** out_plan) {
+  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  auto plan = std::make_unique<rsx_plan>();
+  plan->ctx = ctx;
+  plan->kind = PLAN_A2;
+  plan->n_jobs = n_jobs;
+  plan->job_status.assign(n_jobs, RSX_OK);
+  plan->a2_consumed.assign(n_jobs, 0);
+  for (int i = 0; i < n_jobs; ++i)
+    if (sony_arw2_validate(&jobs[i].desc, jobs[i].img, size_t(jobs[i].in_bytes)) == RSX_OK)
+      plan->a2_consumed[i] = uint32_t(jobs[i].img.dim_x) * uint32_t(jobs[i].img.dim_y);
+  if (int st = sony_arw2_plan_create(ctx, n_jobs, jobs, &plan->a2))
+    return st;
+  *out_plan = plan.release();
+  return RSX_OK;
+}
+
+// The host-pointer call: the w * h bytes go up as one copy, the image comes back as one
+// rectangle through download_rects -- only when every row decoded (the reference throws
+// otherwise, and the caller's image stays as it was).  The lane keeps the plan, keyed by the
+// geometry and the table mode; the table itself is call data and goes up on every call.
+extern "C" int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* desc,
+                                        const uint8_t* in, size_t in_bytes, const rsx_image* img,
+                                        int32_t* row_status) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = sony_arw2_validate(desc, *img, in_bytes))
+    return st;
+  const size_t span = size_t(img->dim_x) * size_t(img->dim_y);
+  rsx_sony_arw2_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc.table_mode = desc->table_mode;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  {
+    const void* fn = reinterpret_cast<const void*>(rsx_sony_arw2_plan_create);
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(&fn);
+    key.insert(key.end(), p, p + sizeof fn);
+    p = reinterpret_cast<const uint8_t*>(&job); // (desc.table is NULL here: not in the key)
+    key.insert(key.end(), p, p + sizeof job);
+  }
+  job.desc.table = desc->table;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  LaneGuard lane(ctx, &key);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t out_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y);
+  if (int e = lane.lane->d_in.ensure(span + 64))
+    return e;
+  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, in, span, hipMemcpyHostToDevice, s));
+  }
+  rsx_plan* plan = nullptr;
+  if (lane.lane->cached_plan && lane.lane->cached_key == key) {
+    plan = lane.lane->cached_plan;
+    // this call's table, ordered before the run on the lane's stream
+    if (int st = sony_arw2_plan_set_table(plan->a2, 0, desc, s))
+      return st;
+  } else {
+    if (lane.lane->cached_plan)
+      rsx_plan_destroy(lane.lane->cached_plan);
+    lane.lane->cached_plan = nullptr;
+    if (int st = rsx_sony_arw2_plan_create(ctx, 1, &job, &plan))
+      return st;
+    lane.lane->cached_plan = plan;
+    lane.lane->cached_key = std::move(key);
+  }
+  int32_t st = RSX_OK;
+  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
+  if (rc == RSX_OK)
+    rc = rsx_plan_results(plan, &st, nullptr);
+  if (rc == RSX_OK || rc == st) {
+    if (row_status)
+      if (int e = sony_arw2_plan_row_status(plan->a2, s, 0, row_status))
         rc = e;
   }
   if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {

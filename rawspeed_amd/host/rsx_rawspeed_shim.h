@@ -21,6 +21,7 @@
 #include "adt/Point.h"
 #include "codes/PrefixCodeDecoder.h"
 #include "common/RawImage.h"
+#include "common/TableLookUp.h"
 #include "decoders/RawDecoderException.h"
 #include "io/IOException.h"
 
@@ -62,6 +63,16 @@ inline rsx_image view(const RawImage& img) {
   v.cpp = implicit_cast<int32_t>(img->getCpp());
   v.is_cfa = img->isCFA ? 1 : 0;
   return v;
+}
+
+// SonyArw2Decompressor::decompress(): the table setWithLookUp would use
+// (mRaw->table; RawImageData keeps it protected, so the hunk reads it through an accessor)
+inline rsx_sony_arw2_desc arw2_desc(const TableLookUp* t) {
+  rsx_sony_arw2_desc d{};
+  d.table_mode = !t ? RSX_ARW2_TABLE_NONE
+                    : (t->dither ? RSX_ARW2_TABLE_DITHER : RSX_ARW2_TABLE_PLAIN);
+  d.table = t ? t->tables.data() : nullptr; // (table 0; the call reads its first 4096 / 8192)
+  return d;
 }
 
 // status -> the exception the reference would have thrown
