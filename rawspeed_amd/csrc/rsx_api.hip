@@ -16,6 +16,7 @@
 #include <thread>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 using namespace rsx;
 
@@ -24,8 +25,7 @@ using namespace rsx;
 // ---------------------------------------------------------------------------
 namespace {
 
-enum PlanKind { PLAN_UNPACK = 0, PLAN_LJPEG = 1, PLAN_SRAW = 2, PLAN_SV2 = 3, PLAN_P1 = 4,
-               PLAN_A2 = 5 };
+enum PlanKind { PLAN_UNPACK, PLAN_SRAW, PLAN_DECODER };
 
 struct UnpackLaunch {
   int mode = UNPACK_MODE_PACKED;
@@ -49,11 +49,7 @@ struct rsx_plan {
   int n_jobs = 0;
   std::vector<int32_t> job_status; // host-side validation result per job
   std::vector<UnpackLaunch> unpack;
-  std::unique_ptr<LJpegPlan, LJpegPlanDeleter> ljpeg;
-  Sv2Plan* sv2 = nullptr; // PLAN_SV2
-  P1Plan* p1 = nullptr;   // PLAN_P1
-  Arw2Plan* a2 = nullptr; // PLAN_A2
-  std::vector<uint32_t> a2_consumed;
+  std::unique_ptr<DecoderPlan> dec; // PLAN_DECODER
   // PLAN_SRAW
   DeviceBuffer d_sraw_jobs, d_sraw_starts;
   int n_sraw = 0;
@@ -65,7 +61,7 @@ struct rsx_plan {
   bool timing = false;
   std::vector<EventPair> events;
   size_t events_used = 0;
-  // LJPEG plans: an event after every kernel of a timed run; the totals per kernel
+  // decoder plans: an event after every kernel of a timed run; the totals per kernel
   // name are folded in before the events are reused
   std::unique_ptr<KernelTimer> ktimer;
   bool ktimer_pending = false;
@@ -164,7 +160,7 @@ rsx_ctx::HostLane* rsx_ctx::acquire_lane(const std::vector<uint8_t>* want_key) {
       size_t pick = lanes_free.size() - 1;
       if (want_key)
         for (size_t k = 0; k < lanes_free.size(); ++k)
-          if (lanes_free[k]->cached_plan && lanes_free[k]->cached_key == *want_key) {
+          if (lanes_free[k]->holds_plan(*want_key)) {
             pick = k;
             break;
           }
@@ -920,26 +916,14 @@ extern "C" int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
     return RSX_OK;
   }
   (void)ev;
-  const bool sv2 = plan->kind == PLAN_SV2;
-  if (!plan->timing) {
-    if (plan->kind == PLAN_P1)
-      return phase_one_plan_run(plan->p1, in_dev, out_dev, s, nullptr);
-    if (plan->kind == PLAN_A2)
-      return sony_arw2_plan_run(plan->a2, in_dev, out_dev, s, nullptr);
-    return sv2 ? samsung_v2_plan_run(plan->sv2, in_dev, out_dev, s, nullptr)
-               : ljpeg_plan_run(plan->ljpeg.get(), in_dev, out_dev, s, nullptr);
-  }
+  if (!plan->timing)
+    return plan->dec->run(in_dev, out_dev, s, nullptr);
   if (int st = fold_kernel_timer(plan)) // (waits for the previous timed run)
     return st;
   if (!plan->ktimer)
     plan->ktimer = std::make_unique<KernelTimer>();
   plan->ktimer_pending = true;
-  if (plan->kind == PLAN_P1)
-    return phase_one_plan_run(plan->p1, in_dev, out_dev, s, plan->ktimer.get());
-  if (plan->kind == PLAN_A2)
-    return sony_arw2_plan_run(plan->a2, in_dev, out_dev, s, plan->ktimer.get());
-  return sv2 ? samsung_v2_plan_run(plan->sv2, in_dev, out_dev, s, plan->ktimer.get())
-             : ljpeg_plan_run(plan->ljpeg.get(), in_dev, out_dev, s, plan->ktimer.get());
+  return plan->dec->run(in_dev, out_dev, s, plan->ktimer.get());
 }
 
 extern "C" int rsx_plan_results(rsx_plan* plan, int32_t* job_status,
@@ -963,26 +947,7 @@ extern "C" int rsx_plan_results(rsx_plan* plan, int32_t* job_status,
     }
     return rc;
   }
-  if (plan->kind == PLAN_SV2) {
-    if (job_consumed)
-      for (int i = 0; i < plan->n_jobs; ++i)
-        job_consumed[i] = 0;
-    return samsung_v2_plan_results(plan->sv2, plan->last_stream, plan->ran, job_status);
-  }
-  if (plan->kind == PLAN_P1) {
-    if (job_consumed)
-      for (int i = 0; i < plan->n_jobs; ++i)
-        job_consumed[i] = 0;
-    return phase_one_plan_results(plan->p1, plan->last_stream, plan->ran, job_status);
-  }
-  if (plan->kind == PLAN_A2) {
-    if (job_consumed) // (a job reads exactly its dim_x * dim_y bytes, when it was accepted)
-      for (int i = 0; i < plan->n_jobs; ++i)
-        job_consumed[i] = plan->a2_consumed[i];
-    return sony_arw2_plan_results(plan->a2, plan->last_stream, plan->ran, job_status);
-  }
-  return ljpeg_plan_results(plan->ljpeg.get(), plan->last_stream, plan->ran,
-                            job_status, job_consumed);
+  return plan->dec->results(plan->last_stream, plan->ran, job_status, job_consumed);
 }
 
 extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
@@ -993,8 +958,7 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
   plan->ktotals.clear();
   plan->kruns = 0;
   plan->ktimer_pending = false;
-  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1 ||
-      plan->kind == PLAN_A2)
+  if (plan->kind == PLAN_DECODER)
     return RSX_OK; // its events are created on the first timed run
   if (plan->timing && plan->events.size() < 64) {
     // event creation is slow on ROCm: pre-create the pool outside timed regions
@@ -1013,9 +977,7 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
 
 extern "C" int rsx_plan_kernel_table(rsx_plan* plan, int cap, const char** names,
                                      double* avg_ms, int* n_kernels, int* n_runs) {
-  if (!plan || (plan->kind != PLAN_LJPEG && plan->kind != PLAN_SV2 && plan->kind != PLAN_P1 &&
-                plan->kind != PLAN_A2) ||
-      !plan->timing)
+  if (!plan || plan->kind != PLAN_DECODER || !plan->timing)
     return RSX_ERR_INVALID_ARG;
   rsx_ctx* ctx = plan->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
@@ -1048,8 +1010,7 @@ extern "C" int rsx_plan_kernel_time(rsx_plan* plan, const char** kernel_name,
   rsx_ctx* ctx = plan->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (plan->kind == PLAN_LJPEG || plan->kind == PLAN_SV2 || plan->kind == PLAN_P1 ||
-      plan->kind == PLAN_A2) {
+  if (plan->kind == PLAN_DECODER) {
     // the dominant kernel = the one with the largest share of the timed runs
     if (int st = fold_kernel_timer(plan))
       return st;
@@ -1115,10 +1076,7 @@ extern "C" void rsx_plan_destroy(rsx_plan* plan) {
     if (plan->ktimer)
       for (int i = 0; i < plan->ktimer->created; ++i)
         (void)hipEventDestroy(plan->ktimer->ev[i]);
-    plan->ljpeg.reset();
-    samsung_v2_plan_destroy(plan->sv2);
-    phase_one_plan_destroy(plan->p1);
-    sony_arw2_plan_destroy(plan->a2);
+    plan->dec.reset();
   }
   delete plan;
 }
@@ -1601,69 +1559,99 @@ void dedupe_tables(LJpegJobIn& in, UniqueTables& store) {
   in.tables = store.t;
   in.n_tables = n;
 }
+
+// The frame of every decoder's plan_create: the arguments, the context's lock and device, and
+// the plan `make` builds for the jobs installed in a new rsx_plan.
+template <typename JobT, typename MakeFn>
+int decoder_plan_create(rsx_ctx* ctx, int n_jobs, const JobT* jobs, rsx_plan** out_plan,
+                        MakeFn make) {
+  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  auto plan = std::make_unique<rsx_plan>();
+  plan->ctx = ctx;
+  plan->kind = PLAN_DECODER;
+  plan->n_jobs = n_jobs;
+  if (int st = make(ctx, n_jobs, jobs, &plan->dec))
+    return st;
+  *out_plan = plan.release();
+  return RSX_OK;
+}
+
+// An LJPEG-family plan: `fill(job, in)` turns each job into its LJpegJobIn, status included.
+template <typename JobT, typename FillFn>
+int ljpeg_family_plan_create(rsx_ctx* ctx, int n_jobs, const JobT* jobs, rsx_plan** out_plan,
+                             FillFn fill) {
+  return decoder_plan_create(
+      ctx, n_jobs, jobs, out_plan,
+      [&](rsx_ctx* c, int n, const JobT* js, std::unique_ptr<DecoderPlan>* out) {
+        std::vector<LJpegJobIn> in(n);
+        std::vector<UniqueTables> unique(n);
+        for (int i = 0; i < n; ++i) {
+          fill(js[i], in[i]);
+          dedupe_tables(in[i], unique[i]); // (nothing to do for a job of one table)
+        }
+        return ljpeg_plan_create(c, in, out);
+      });
+}
+
+// the validation status of a raw decoder's job, with the odd pitch its 16-bit rows cannot have
+int raw_status(int st, const rsx_image& img) {
+  return st == RSX_OK && img.pitch_bytes % 2 != 0 ? RSX_ERR_INVALID_ARG : st;
+}
+
+// The stream of the raw decoders on the Nikon reconstruction kernels (Nikon, Pentax, SamsungV1,
+// Sony ARW1): a plain MSB bit stream (kind 2) of `rows` rows of `row_samples` samples, two
+// predictors alternating along a row
+template <typename JobT>
+void raw_pair_geom(const JobT& job, uint32_t rows, uint32_t row_samples, StreamGeom* g) {
+  std::memset(g, 0, sizeof *g);
+  g->kind = 2;
+  g->raw = 1;
+  g->in_offset = job.in_offset;
+  g->in_bytes = job.in_bytes;
+  g->img_offset = job.img_offset;
+  g->img_pitch_bytes = job.img.pitch_bytes;
+  g->n_comp = 2;
+  g->period = 2;
+  g->rows = rows;
+  g->row_samples = row_samples;
+  g->mcu_w = g->mcu_h = 1;
+  g->keep_samples = row_samples;
+}
+
 } // namespace
 
 extern "C" int rsx_ljpeg_plan_create(rsx_ctx* ctx, int n_jobs,
                                      const rsx_ljpeg_job* jobs,
                                      rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  std::vector<UniqueTables> unique(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    in[i].status = build_ljpeg_stream(jobs[i].desc, jobs[i].img, &in[i].geom);
-    in[i].geom.in_offset = jobs[i].in_offset;
-    in[i].geom.in_bytes = jobs[i].in_bytes;
-    in[i].geom.img_offset = jobs[i].img_offset;
-    in[i].tables = jobs[i].desc.tables;
-    in[i].n_tables = jobs[i].desc.n_tables;
-    in[i].rows_per_restart_interval = jobs[i].desc.rows_per_restart_interval;
-    in[i].frame_h = jobs[i].desc.frame_h;
-    dedupe_tables(in[i], unique[i]);
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_ljpeg_job& j, LJpegJobIn& J) {
+    J.status = build_ljpeg_stream(j.desc, j.img, &J.geom);
+    J.geom.in_offset = j.in_offset;
+    J.geom.in_bytes = j.in_bytes;
+    J.geom.img_offset = j.img_offset;
+    J.tables = j.desc.tables;
+    J.n_tables = j.desc.n_tables;
+    J.rows_per_restart_interval = j.desc.rows_per_restart_interval;
+    J.frame_h = j.desc.frame_h;
+  });
 }
 
 extern "C" int rsx_cr2_plan_create(rsx_ctx* ctx, int n_jobs,
                                    const rsx_cr2_job* jobs, rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  std::vector<UniqueTables> unique(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    in[i].status = build_cr2_stream(jobs[i].desc, jobs[i].img, &in[i].geom);
-    in[i].geom.in_offset = jobs[i].in_offset;
-    in[i].geom.in_bytes = jobs[i].in_bytes;
-    in[i].geom.img_offset = jobs[i].img_offset;
-    in[i].tables = jobs[i].desc.tables;
-    in[i].n_tables = jobs[i].desc.n_tables;
-    in[i].rows_per_restart_interval = 0; // CR2 rejects DRI (Cr2LJpegDecoder.cpp:59-60)
-    in[i].frame_h = 0;
-    dedupe_tables(in[i], unique[i]);
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_cr2_job& j, LJpegJobIn& J) {
+    J.status = build_cr2_stream(j.desc, j.img, &J.geom);
+    J.geom.in_offset = j.in_offset;
+    J.geom.in_bytes = j.in_bytes;
+    J.geom.img_offset = j.img_offset;
+    J.tables = j.desc.tables;
+    J.n_tables = j.desc.n_tables;
+    J.rows_per_restart_interval = 0; // CR2 rejects DRI (Cr2LJpegDecoder.cpp:59-60)
+    J.frame_h = 0;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1678,19 +1666,7 @@ extern "C" int rsx_samsung_v2_validate(const rsx_samsung_v2_desc* d, const rsx_i
 extern "C" int rsx_samsung_v2_plan_create(rsx_ctx* ctx, int n_jobs,
                                           const rsx_samsung_v2_job* jobs,
                                           rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_SV2;
-  plan->n_jobs = n_jobs;
-  plan->job_status.assign(n_jobs, RSX_OK);
-  if (int st = samsung_v2_plan_create(ctx, n_jobs, jobs, &plan->sv2))
-    return st;
-  *out_plan = plan.release();
-  return RSX_OK;
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, samsung_v2_plan_create);
 }
 
 // ---------------------------------------------------------------------------
@@ -1803,40 +1779,16 @@ extern "C" int rsx_nikon_validate(const rsx_nikon_desc* d, const rsx_image* img)
 
 extern "C" int rsx_nikon_plan_create(rsx_ctx* ctx, int n_jobs,
                                      const rsx_nikon_job* jobs, rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    const rsx_nikon_desc& d = jobs[i].desc;
-    const rsx_image& img = jobs[i].img;
-    LJpegJobIn& J = in[i];
-    J.status = validate_nikon(d, img);
-    if (J.status == RSX_OK && img.pitch_bytes % 2 != 0)
-      J.status = RSX_ERR_INVALID_ARG;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_nikon_job& j, LJpegJobIn& J) {
+    const rsx_nikon_desc& d = j.desc;
+    J.status = raw_status(validate_nikon(d, j.img), j.img);
     if (J.status != RSX_OK)
-      continue;
-    StreamGeom& g = J.geom;
-    std::memset(&g, 0, sizeof g);
-    g.kind = 2;
-    g.raw = 1;
-    g.in_offset = jobs[i].in_offset;
-    g.in_bytes = jobs[i].in_bytes;
-    g.img_offset = jobs[i].img_offset;
-    g.img_pitch_bytes = img.pitch_bytes;
+      return;
     // one table for the whole stream: the two columns alternate (:525-527) but
     // share it, so the "component" only matters to the reconstruction
-    g.n_comp = 2;
-    g.period = 2;
-    g.rows = uint32_t(d.split ? d.split : img.dim_y); // decompress(bits, 0, split) :555-556
-    g.row_samples = uint32_t(img.dim_x);
-    g.mcu_w = g.mcu_h = 1;
-    g.keep_samples = g.row_samples;
+    raw_pair_geom(j, uint32_t(d.split ? d.split : j.img.dim_y), // decompress(bits, 0, split) :555-556
+                  uint32_t(j.img.dim_x), &J.geom);
     J.tables = &d.tables[0];
     J.n_tables = 1;
     NikonIn& N = J.nikon;
@@ -1844,19 +1796,13 @@ extern "C" int rsx_nikon_plan_create(rsx_ctx* ctx, int n_jobs,
       N.p_up[k] = (&d.p_up[0][0])[k];
     N.uncorrected = d.uncorrected_raw_values != 0;
     N.split = d.split;
-    N.height = img.dim_y;
-    N.seed_offset = jobs[i].in_offset;
+    N.height = j.img.dim_y;
+    N.seed_offset = j.in_offset;
     if (d.split)
       N.table_after_split = d.tables[1];
     if (!N.uncorrected)
       build_dither_table(d.curve, d.curve_size, &N.dither);
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+  });
 }
 
 extern "C" int rsx_pentax_validate(const rsx_pentax_desc* d, const rsx_image* img) {
@@ -1867,50 +1813,20 @@ extern "C" int rsx_pentax_validate(const rsx_pentax_desc* d, const rsx_image* im
 
 extern "C" int rsx_pentax_plan_create(rsx_ctx* ctx, int n_jobs,
                                       const rsx_pentax_job* jobs, rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    const rsx_image& img = jobs[i].img;
-    LJpegJobIn& J = in[i];
-    J.status = validate_pentax(jobs[i].desc, img);
-    if (J.status == RSX_OK && img.pitch_bytes % 2 != 0)
-      J.status = RSX_ERR_INVALID_ARG;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_pentax_job& j, LJpegJobIn& J) {
+    J.status = raw_status(validate_pentax(j.desc, j.img), j.img);
     if (J.status != RSX_OK)
-      continue;
-    StreamGeom& g = J.geom;
-    std::memset(&g, 0, sizeof g);
-    g.kind = 2; // the Nikon reconstruction kernels, Pentax flavour
-    g.raw = 1;
-    g.in_offset = jobs[i].in_offset;
-    g.in_bytes = jobs[i].in_bytes;
-    g.img_offset = jobs[i].img_offset;
-    g.img_pitch_bytes = img.pitch_bytes;
-    g.n_comp = 2;
-    g.period = 2;
-    g.rows = uint32_t(img.dim_y);
-    g.row_samples = uint32_t(img.dim_x);
-    g.mcu_w = g.mcu_h = 1;
-    g.keep_samples = g.row_samples;
-    J.tables = &jobs[i].desc.table;
+      return;
+    // the Nikon reconstruction kernels, Pentax flavour
+    raw_pair_geom(j, uint32_t(j.img.dim_y), uint32_t(j.img.dim_x), &J.geom);
+    J.tables = &j.desc.table;
     J.n_tables = 1;
     J.nikon.uncorrected = true;
     J.nikon.pentax = true; // predictors start at 0, range check instead of clamp
-    J.nikon.height = img.dim_y;
-    J.nikon.seed_offset = jobs[i].in_offset;
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+    J.nikon.height = j.img.dim_y;
+    J.nikon.seed_offset = j.in_offset;
+  });
 }
 
 extern "C" int rsx_hasselblad_validate(const rsx_hasselblad_desc* d, const rsx_image* img) {
@@ -1922,38 +1838,27 @@ extern "C" int rsx_hasselblad_validate(const rsx_hasselblad_desc* d, const rsx_i
 extern "C" int rsx_hasselblad_plan_create(rsx_ctx* ctx, int n_jobs,
                                           const rsx_hasselblad_job* jobs,
                                           rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    const rsx_image& img = jobs[i].img;
-    LJpegJobIn& J = in[i];
-    J.status = validate_hasselblad(jobs[i].desc, img);
-    if (J.status == RSX_OK && img.pitch_bytes % 2 != 0)
-      J.status = RSX_ERR_INVALID_ARG;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_hasselblad_job& j, LJpegJobIn& J) {
+    const rsx_image& img = j.img;
+    J.status = raw_status(validate_hasselblad(j.desc, img), img);
     if (J.status != RSX_OK)
-      continue;
+      return;
     StreamGeom& g = J.geom;
     std::memset(&g, 0, sizeof g);
     g.kind = 0; // rows of W samples written in place, like an LJPEG tile that is the image
     g.raw = 1;  // BitStreamerMSB32: no stuffing, no markers, 8-byte over-read budget
     g.pair = 1;
     g.no_vertical = 1; // "int p1 = rec.initPred; int p2 = rec.initPred;" per row (:83-85)
-    g.in_offset = jobs[i].in_offset;
-    g.in_bytes = jobs[i].in_bytes;
-    g.img_offset = jobs[i].img_offset;
+    g.in_offset = j.in_offset;
+    g.in_bytes = j.in_bytes;
+    g.img_offset = j.img_offset;
     g.img_pitch_bytes = img.pitch_bytes;
     g.n_comp = 2; // p1 / p2 alternate along the row (:86-96)
     g.period = 2;
     g.pred_of_phase[0] = 0;
     g.pred_of_phase[1] = 1;
-    g.init_pred[0] = g.init_pred[1] = jobs[i].desc.init_pred;
+    g.init_pred[0] = g.init_pred[1] = j.desc.init_pred;
     g.seed_pos[0] = 0;
     g.seed_pos[1] = 1;
     g.rows = uint32_t(img.dim_y);
@@ -1961,15 +1866,9 @@ extern "C" int rsx_hasselblad_plan_create(rsx_ctx* ctx, int n_jobs,
     g.mcu_w = 2;
     g.mcu_h = 1;
     g.keep_samples = g.row_samples;
-    J.tables = &jobs[i].desc.table;
+    J.tables = &j.desc.table;
     J.n_tables = 1;
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+  });
 }
 
 extern "C" int rsx_samsung_v1_validate(const rsx_samsung_v1_desc* d, const rsx_image* img) {
@@ -1981,56 +1880,26 @@ extern "C" int rsx_samsung_v1_validate(const rsx_samsung_v1_desc* d, const rsx_i
 extern "C" int rsx_samsung_v1_plan_create(rsx_ctx* ctx, int n_jobs,
                                           const rsx_samsung_v1_job* jobs,
                                           rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    const rsx_image& img = jobs[i].img;
-    LJpegJobIn& J = in[i];
-    J.status = validate_samsung_v1(jobs[i].desc, img);
-    if (J.status == RSX_OK && img.pitch_bytes % 2 != 0)
-      J.status = RSX_ERR_INVALID_ARG;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_samsung_v1_job& j, LJpegJobIn& J) {
+    J.status = raw_status(validate_samsung_v1(j.desc, j.img), j.img);
     if (J.status != RSX_OK)
-      continue;
-    StreamGeom& g = J.geom;
-    std::memset(&g, 0, sizeof g);
-    g.kind = 2; // the Nikon / Pentax reconstruction kernels
-    g.raw = 1;
-    g.in_offset = jobs[i].in_offset;
-    g.in_bytes = jobs[i].in_bytes;
-    g.img_offset = jobs[i].img_offset;
-    g.img_pitch_bytes = img.pitch_bytes;
-    g.n_comp = 2;
-    g.period = 2;
-    g.rows = uint32_t(img.dim_y);
-    g.row_samples = uint32_t(img.dim_x);
-    g.mcu_w = g.mcu_h = 1;
-    g.keep_samples = g.row_samples;
+      return;
+    // the Nikon / Pentax reconstruction kernels
+    raw_pair_geom(j, uint32_t(j.img.dim_y), uint32_t(j.img.dim_x), &J.geom);
     // samsungDiff refills with fill(23), not fill(32) (.cpp:66): a symbol at bit c
     // needs 32 K - c >= 23, so symbols may start 9 bits later than with fill(32)
-    g.raw_limit = 32 * ((uint64_t(jobs[i].in_bytes) + 8) / 4) + 9 + 1;
+    J.geom.raw_limit = 32 * ((uint64_t(j.in_bytes) + 8) / 4) + 9 + 1;
     J.n_tables = 1;
-    J.explicit_enc_len = jobs[i].desc.enc_len;
-    J.explicit_diff_len = jobs[i].desc.diff_len;
-    J.explicit_n = jobs[i].desc.n_entries;
+    J.explicit_enc_len = j.desc.enc_len;
+    J.explicit_diff_len = j.desc.diff_len;
+    J.explicit_n = j.desc.n_entries;
     J.nikon.uncorrected = true;
     J.nikon.pentax = true;
-    J.nikon.range_bits = jobs[i].desc.bits;
-    J.nikon.height = img.dim_y;
-    J.nikon.seed_offset = jobs[i].in_offset;
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+    J.nikon.range_bits = j.desc.bits;
+    J.nikon.height = j.img.dim_y;
+    J.nikon.seed_offset = j.in_offset;
+  });
 }
 
 extern "C" int rsx_sony_arw1_validate(const rsx_image* img) {
@@ -2053,38 +1922,15 @@ constexpr uint8_t SONY_DIF[14] = {0xFF, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 0, 2, 1
 extern "C" int rsx_sony_arw1_plan_create(rsx_ctx* ctx, int n_jobs,
                                          const rsx_sony_arw1_job* jobs,
                                          rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_LJPEG;
-  plan->n_jobs = n_jobs;
-  std::vector<LJpegJobIn> in(n_jobs);
-  for (int i = 0; i < n_jobs; ++i) {
-    const rsx_image& img = jobs[i].img;
-    LJpegJobIn& J = in[i];
-    J.status = validate_sony_arw1(img);
-    if (J.status == RSX_OK && img.pitch_bytes % 2 != 0)
-      J.status = RSX_ERR_INVALID_ARG;
+  return ljpeg_family_plan_create(ctx, n_jobs, jobs, out_plan,
+                                  [](const rsx_sony_arw1_job& j, LJpegJobIn& J) {
+    J.status = raw_status(validate_sony_arw1(j.img), j.img);
     if (J.status != RSX_OK)
-      continue;
-    StreamGeom& g = J.geom;
-    std::memset(&g, 0, sizeof g);
-    g.kind = 2; // int32 sums + range check, like Pentax; sony_* reconstruction kernels
-    g.raw = 1;  // BitStreamerMSB, fill(32) per pixel (.cpp:70)
-    g.in_offset = jobs[i].in_offset;
-    g.in_bytes = jobs[i].in_bytes;
-    g.img_offset = jobs[i].img_offset;
-    g.img_pitch_bytes = img.pitch_bytes;
-    g.n_comp = 2;
-    g.period = 2;
-    // a stream row is an image column (.cpp:68-69): W rows of H samples
-    g.rows = uint32_t(img.dim_x);
-    g.row_samples = uint32_t(img.dim_y);
-    g.mcu_w = g.mcu_h = 1;
-    g.keep_samples = g.row_samples;
+      return;
+    // int32 sums + range check, like Pentax; sony_* reconstruction kernels; BitStreamerMSB,
+    // fill(32) per pixel (.cpp:70).  A stream row is an image column (.cpp:68-69): W rows of
+    // H samples
+    raw_pair_geom(j, uint32_t(j.img.dim_x), uint32_t(j.img.dim_y), &J.geom);
     J.n_tables = 1;
     J.explicit_enc_len = SONY_ENC;
     J.explicit_diff_len = SONY_DIF;
@@ -2094,15 +1940,9 @@ extern "C" int rsx_sony_arw1_plan_create(rsx_ctx* ctx, int n_jobs,
     J.nikon.pentax = true;
     J.nikon.range_bits = 12;
     J.nikon.sony = true;
-    J.nikon.height = img.dim_x;
-    J.nikon.seed_offset = jobs[i].in_offset;
-  }
-  LJpegPlan* lp = nullptr;
-  if (int st = ljpeg_plan_create(ctx, in, &lp))
-    return st;
-  plan->ljpeg.reset(lp);
-  *out_plan = plan.release();
-  return RSX_OK;
+    J.nikon.height = j.img.dim_x;
+    J.nikon.seed_offset = j.in_offset;
+  });
 }
 
 namespace {
@@ -2138,27 +1978,84 @@ HostRect out_rect(const rsx_hasselblad_job& j) {
   return {0, size_t(j.img.dim_y), 0, size_t(j.img.dim_x) * 2};
 }
 
-// What a job's plan is made FROM beyond the bytes of its struct: data behind host pointers.
-// The plan-cache key holds the contents, never the address (a freed and re-allocated
-// curve at the same address, or one mutated in place, must not find the old plan).
+// ---------------------------------------------------------------------------------------
+// The plan a host-pointer call runs is the lane's cached plan when the lane made it from the
+// same key (a burst, a benchmark loop, the tiles of one camera's files), else a new one.
+//   * A key is the plan's create function, then what the plan is made FROM: the jobs with the
+//     host pointers cleared, and the CONTENTS of data behind host pointers (the Nikon curve, the
+//     Phase One strip table), never an address -- a freed and re-allocated curve at the same
+//     address, or one mutated in place, must not find the old plan.  ARW2's table stays out of
+//     its key: it is call data and goes up on every call.
+//   * A call that fails on the device or for memory drops the lane's plan; Phase One and ARW2
+//     drop it on RSX_ERR_INVALID_ARG as well.
+//   * The uploads and the downloads of the calls of a context take turns (upload_mu,
+//     download_mu): calls side by side then share neither direction of the link.
+//   * A build with RSX_FORCE_UNSUPPORTED refuses every LJPEG-family call (ljpeg_family_host):
+//     the drop-in tests are checked against such a library.
+// ---------------------------------------------------------------------------------------
+template <typename JobT>
+using PlanCreateFn = int (*)(rsx_ctx*, int, const JobT*, rsx_plan**);
+
+// appends the bytes of v[0 .. n) to a key
+template <typename T>
+void key_append(std::vector<uint8_t>& key, const T* v, size_t n = 1) {
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(v);
+  key.insert(key.end(), p, p + n * sizeof(T));
+}
+
+template <typename JobT>
+void key_create(std::vector<uint8_t>& key, PlanCreateFn<JobT> create) {
+  const void* fn = reinterpret_cast<const void*>(create);
+  key_append(key, &fn);
+}
+
 template <typename JobT>
 void key_job(std::vector<uint8_t>& key, const JobT& job) {
   JobT j = job;
   j.img.data = nullptr;
-  const uint8_t* p = reinterpret_cast<const uint8_t*>(&j);
-  key.insert(key.end(), p, p + sizeof(JobT));
+  key_append(key, &j);
 }
 template <>
 void key_job<rsx_nikon_job>(std::vector<uint8_t>& key, const rsx_nikon_job& job) {
   rsx_nikon_job j = job;
   j.img.data = nullptr;
   j.desc.curve = nullptr;
-  const uint8_t* p = reinterpret_cast<const uint8_t*>(&j);
-  key.insert(key.end(), p, p + sizeof j);
-  if (job.desc.curve && job.desc.curve_size > 0 && job.desc.curve_size <= 65536) {
-    const uint8_t* c = reinterpret_cast<const uint8_t*>(job.desc.curve);
-    key.insert(key.end(), c, c + size_t(job.desc.curve_size) * sizeof(uint16_t));
+  key_append(key, &j);
+  if (job.desc.curve && job.desc.curve_size > 0 && job.desc.curve_size <= 65536)
+    key_append(key, job.desc.curve, size_t(job.desc.curve_size));
+}
+
+// The lane's plan for `key` (*reused: the one it held), else a new one from create(ctx, n,
+// jobs) in place of the one it held; when create fails, the lane holds none.
+template <typename JobT>
+int lane_plan(rsx_ctx* ctx, rsx_ctx::HostLane* L, std::vector<uint8_t>& key,
+              PlanCreateFn<JobT> create, int n, const JobT* jobs, rsx_plan** plan,
+              bool* reused = nullptr) {
+  const bool hit = L->holds_plan(key);
+  if (reused)
+    *reused = hit;
+  if (hit) {
+    *plan = L->cached_plan;
+    return RSX_OK;
   }
+  if (L->cached_plan)
+    rsx_plan_destroy(L->cached_plan);
+  L->cached_plan = nullptr;
+  if (int st = create(ctx, n, jobs, plan))
+    return st;
+  L->cached_plan = *plan;
+  L->cached_key = std::move(key);
+  return RSX_OK;
+}
+
+void evict_plan(rsx_ctx::HostLane* L) {
+  rsx_plan_destroy(L->cached_plan);
+  L->cached_plan = nullptr;
+}
+
+// the LJPEG-family plan behind a plan, or nullptr
+LJpegPlan* ljpeg_of(const rsx_plan* p) {
+  return p && p->dec ? p->dec->ljpeg() : nullptr;
 }
 
 // One large entropy-coded stream through a host-pointer call, in CHUNKS (round 6; the review's
@@ -2179,7 +2076,7 @@ int ljpeg_chunked_host(rsx_ctx* ctx, rsx_ctx::HostLane* L, rsx_plan* plan, size_
                        const HostRect& whole, size_t out_skip, int32_t* status,
                        uint32_t* consumed) {
   constexpr int NCH = 4;
-  LJpegPlan* lp = plan->ljpeg.get();
+  LJpegPlan* lp = ljpeg_of(plan);
   const uint32_t nblk = ljpeg_plan_blocks(lp);
   if (nblk < 4 * NCH || !L->ensure_overlap(NCH))
     return CHUNKED_NOT_TAKEN;
@@ -2310,10 +2207,10 @@ int ljpeg_chunked_host(rsx_ctx* ctx, rsx_ctx::HostLane* L, rsx_plan* plan, size_
   return rc;
 }
 
-template <typename JobT, typename CreateFn>
+template <typename JobT>
 int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
                       const uint8_t* const* ins, const rsx_image* img,
-                      CreateFn create, int32_t* statuses, uint32_t* consumed,
+                      PlanCreateFn<JobT> create, int32_t* statuses, uint32_t* consumed,
                       bool count_call = true) {
   if (count_call)
     ++ctx->host_calls;
@@ -2355,13 +2252,9 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
   // offsets, image geometry; not the host pointer of the image)
   std::vector<uint8_t> key;
   key.reserve(sizeof(void*) + size_t(n) * sizeof(JobT));
-  {
-    const void* fn = reinterpret_cast<const void*>(create);
-    const uint8_t* p = reinterpret_cast<const uint8_t*>(&fn);
-    key.insert(key.end(), p, p + sizeof fn);
-    for (int i = 0; i < n; ++i)
-      key_job(key, jobs[i]);
-  }
+  key_create(key, create);
+  for (int i = 0; i < n; ++i)
+    key_job(key, jobs[i]);
   LaneGuard lane(ctx, &key); // staging + stream of this call
   if (!lane.lane)
     return RSX_ERR_DEVICE;
@@ -2372,18 +2265,16 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
   hipStream_t s = lane.lane->stream;
   // ONE large stream of the single-pass kernel whose plan the lane holds (a frame decoded
   // again: a burst, a folder of one camera's files): in chunks -- see ljpeg_chunked_host.
-  if (n == 1 && ctx->host_overlap && jobs[0].in_bytes >= (size_t(8) << 20) &&
-      lane.lane->cached_plan && lane.lane->cached_key == key &&
-      lane.lane->cached_plan->kind == PLAN_LJPEG && !lane.lane->cached_plan->timing &&
-      ljpeg_plan_chunkable(lane.lane->cached_plan->ljpeg.get())) {
+  rsx_plan* const held = lane.lane->holds_plan(key) ? lane.lane->cached_plan : nullptr;
+  if (n == 1 && ctx->host_overlap && jobs[0].in_bytes >= (size_t(8) << 20) && held &&
+      !held->timing && ljpeg_of(held) && ljpeg_plan_chunkable(ljpeg_of(held))) {
     int32_t st1 = RSX_OK;
     uint32_t cons1 = 0;
-    const int rc = ljpeg_chunked_host(ctx, lane.lane, lane.lane->cached_plan, jobs[0].in_bytes, in_total,
+    const int rc = ljpeg_chunked_host(ctx, lane.lane, held, jobs[0].in_bytes, in_total,
                                       ins[0], img, out_rect(jobs[0]), out_skip, &st1, &cons1);
     if (rc != CHUNKED_NOT_TAKEN) {
       if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM) {
-        rsx_plan_destroy(lane.lane->cached_plan);
-        lane.lane->cached_plan = nullptr;
+        evict_plan(lane.lane);
         return rc;
       }
       if (statuses)
@@ -2406,17 +2297,8 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
                                         ins[i], jobs[i].in_bytes, hipMemcpyHostToDevice, s));
   }
   rsx_plan* plan = nullptr;
-  if (lane.lane->cached_plan && lane.lane->cached_key == key) {
-    plan = lane.lane->cached_plan;
-  } else {
-    if (lane.lane->cached_plan)
-      rsx_plan_destroy(lane.lane->cached_plan);
-    lane.lane->cached_plan = nullptr;
-    if (int st = create(ctx, n, jobs.data(), &plan))
-      return st;
-    lane.lane->cached_plan = plan;
-    lane.lane->cached_key = std::move(key);
-  }
+  if (int st = lane_plan(ctx, lane.lane, key, create, n, jobs.data(), &plan))
+    return st;
   std::vector<int32_t> st(n, RSX_OK);
   std::vector<uint32_t> cons(n, 0);
   uint8_t* const out_row0 = static_cast<uint8_t*>(lane.lane->d_out.ptr) - out_skip;
@@ -2424,71 +2306,9 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
   if (rc == RSX_OK)
     rc = rsx_plan_results(plan, st.data(), cons.data());
   if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM) {
-    rsx_plan_destroy(lane.lane->cached_plan);
-    lane.lane->cached_plan = nullptr;
+    evict_plan(lane.lane);
     return rc;
   }
-#ifdef RSX_DIAG_VERIFY
-  // (diagnostic build, round 6: an intermittent wrong tile with status OK under six host threads --
-  // was the INPUT on the device what the caller handed over, and does the same plan on the same
-  // device input give the same pixels a second time?)
-  {
-    static std::atomic<unsigned long long> calls{0}, bad_in{0}, bad_rerun{0};
-    ++calls;
-    std::vector<uint8_t> back(in_total + 64), out1(out_bytes), out2(out_bytes);
-    (void)hipMemcpyAsync(back.data(), lane.lane->d_in.ptr, in_total + 64, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(out1.data(), lane.lane->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    for (int i = 0; i < n; ++i) {
-      const uint8_t* h = static_cast<const uint8_t*>(ins[i]);
-      const uint8_t* d = back.data() + jobs[i].in_offset;
-      size_t nd = 0, first = 0, zeros = 0;
-      for (size_t k = 0; k < size_t(jobs[i].in_bytes); ++k)
-        if (h[k] != d[k]) {
-          if (!nd)
-            first = k;
-          ++nd;
-          zeros += d[k] == 0;
-        }
-      if (nd) {
-        ++bad_in;
-        fprintf(stderr, "RSX_DIAG_VERIFY: INPUT of job %d/%d on the device differs from the caller's in %zu of %zu "
-                        "bytes (first at %zu; %zu of them zero on the device), in_offset %zu\n",
-                i, n, nd, size_t(jobs[i].in_bytes), first, zeros, size_t(jobs[i].in_offset));
-      }
-    }
-    std::vector<int32_t> st2(n, RSX_OK);
-    std::vector<uint32_t> cons2(n, 0);
-    int rc2 = rsx_plan_run(plan, lane.lane->d_in.ptr, out_row0, s);
-    if (rc2 == RSX_OK)
-      rc2 = rsx_plan_results(plan, st2.data(), cons2.data());
-    (void)hipMemcpyAsync(out2.data(), lane.lane->d_out.ptr, out_bytes, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    size_t nd = 0, first = 0;
-    for (size_t k = 0; k < out_bytes; ++k)
-      if (out1[k] != out2[k]) {
-        if (!nd)
-          first = k;
-        ++nd;
-      }
-    if (nd || st2 != st || cons2 != cons || rc2 != rc) {
-      ++bad_rerun;
-      fprintf(stderr, "RSX_DIAG_VERIFY: a SECOND run of the plan on the same device input differs: %zu of %zu output "
-                      "bytes (first at %zu = row %zu byte %zu), rc %d -> %d;",
-              nd, out_bytes, first, first / size_t(img->pitch_bytes), first % size_t(img->pitch_bytes), rc, rc2);
-      for (int i = 0; i < n; ++i)
-        fprintf(stderr, " job %d: status %d -> %d consumed %u -> %u (in_bytes %zu);", i, st[i], st2[i], cons[i],
-                cons2[i], size_t(jobs[i].in_bytes));
-      fprintf(stderr, " (the second run's results are the ones delivered)\n");
-      st = st2;
-      cons = cons2;
-      rc = rc2;
-    }
-    if ((calls & 1023ull) == 0)
-      fprintf(stderr, "RSX_DIAG_VERIFY: %llu calls, %llu with a device input that differs, %llu with a second run that differs\n",
-              (unsigned long long)calls, (unsigned long long)bad_in, (unsigned long long)bad_rerun);
-  }
-#endif
   // only the rectangle a successful job decoded goes back to the host image:
   // pixels outside it (other tiles, padding) are never touched
   std::vector<HostRect> rects;
@@ -2537,169 +2357,82 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
                       img->pitch_bytes, r.bytes, r.rows});
     }
     std::lock_guard<std::mutex> down_lock(ctx->download_mu);
-#ifdef RSX_DIAG_DOWNLOAD
-    // (diagnostic build: the round-5 copies -- one 2-D copy a rectangle into the pageable image)
-    for (const DownRect& r : down)
-      RSX_HIP_CHECK(ctx, hipMemcpy2DAsync(r.host, r.host_pitch, r.dev, r.dev_pitch, r.bytes, r.rows,
-                                          hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-#else
     if (int e = download_rects(ctx, lane.lane, s, down.data(), down.size()))
       return e;
-#endif
   }
-#ifdef RSX_DIAG_DOWNLOAD
-  {
-    // Diagnostic build (scripts/r06a.sh): the same device rows once more, as ONE contiguous
-    // copy into memory of our own, and every rectangle of the host image compared with them.
-    // A difference = bytes the 2-D copy did not deliver although the device held them.
-    static std::atomic<uint64_t> calls{0}, bad_calls{0};
-    size_t r0 = ~size_t(0), r1 = 0;
-    for (const HostRect& r : rects) {
-      r0 = std::min(r0, r.row0);
-      r1 = std::max(r1, r.row0 + r.rows);
-    }
-    const size_t pitch = img->pitch_bytes;
-    if (!rects.empty()) {
-      std::vector<uint8_t> chk((r1 - r0) * pitch);
-      RSX_HIP_CHECK(ctx, hipMemcpy(chk.data(), out_row0 + r0 * pitch, chk.size(), hipMemcpyDeviceToHost));
-      ++calls;
-      bool bad = false;
-      for (size_t i = 0; i < rects.size(); ++i) {
-        const HostRect& r = rects[i];
-        for (size_t y = 0; y < r.rows; ++y) {
-          const uint8_t* h = static_cast<uint8_t*>(img->data) + (r.row0 + y) * pitch + r.byte0;
-          const uint8_t* d = chk.data() + (r.row0 + y - r0) * pitch + r.byte0;
-          if (std::memcmp(h, d, r.bytes) != 0) {
-            size_t a = 0, b = r.bytes;
-            while (a < r.bytes && h[a] == d[a]) ++a;
-            while (b > a && h[b - 1] == d[b - 1]) --b;
-            fprintf(stderr, "RSX_DIAG_DOWNLOAD: rect %zu/%zu (row0 %zu rows %zu byte0 %zu bytes %zu) row %zu: "
-                    "host != device in rect-bytes [%zu, %zu) (unit %zu + %zu); host %02x %02x .. device %02x %02x; "
-                    "host row addr %p, image %p pitch %zu\n", i, rects.size(), r.row0, r.rows, r.byte0, r.bytes,
-                    y, a, b, a / 16, a % 16, h[a], h[a + 1], d[a], d[a + 1], static_cast<const void*>(h),
-                    img->data, pitch);
-            bad = true;
-          }
-        }
-      }
-      if (bad) {
-        ++bad_calls;
-        auto still_bad = [&](std::vector<uintptr_t>* pages) {
-          size_t still = 0;
-          for (const HostRect& r : rects)
-            for (size_t y = 0; y < r.rows; ++y) {
-              const uint8_t* h = static_cast<uint8_t*>(img->data) + (r.row0 + y) * pitch + r.byte0;
-              const uint8_t* d = chk.data() + (r.row0 + y - r0) * pitch + r.byte0;
-              if (std::memcmp(h, d, r.bytes) != 0) {
-                ++still;
-                if (pages)
-                  for (size_t x = 0; x < r.bytes; ++x)
-                    if (h[x] != d[x]) {
-                      const uintptr_t pg = reinterpret_cast<uintptr_t>(h + x) & ~uintptr_t(4095);
-                      if (pages->empty() || pages->back() != pg)
-                        pages->push_back(pg);
-                    }
-              }
-            }
-          return still;
-        };
-        auto again2d = [&]() -> int {
-          for (const HostRect& r : rects) {
-            const size_t off = r.row0 * pitch + r.byte0;
-            RSX_HIP_CHECK(ctx, hipMemcpy2DAsync(static_cast<uint8_t*>(img->data) + off, pitch, out_row0 + off,
-                                                pitch, r.bytes, r.rows, hipMemcpyDeviceToHost, s));
-          }
-          RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-          return RSX_OK;
-        };
-        std::vector<uintptr_t> pages;
-        still_bad(&pages);
-        std::sort(pages.begin(), pages.end());
-        pages.erase(std::unique(pages.begin(), pages.end()), pages.end());
-        fprintf(stderr, "RSX_DIAG_DOWNLOAD: %zu host pages hold undelivered bytes:", pages.size());
-        for (size_t k = 0; k < pages.size() && k < 12; ++k)
-          fprintf(stderr, " %p", reinterpret_cast<void*>(pages[k]));
-        fprintf(stderr, "\n");
-        // /proc/self/pagemap of the first such page, its neighbours and the image's first page
-        // (bit 63 present, 62 swapped, 61 file/shared, 56 exclusively mapped, 55 soft-dirty)
-        if (FILE* pm = fopen("/proc/self/pagemap", "rb")) {
-          auto entry = [&](uintptr_t va) {
-            uint64_t e = 0;
-            if (fseek(pm, long(va / 4096 * 8), SEEK_SET) == 0 && fread(&e, 8, 1, pm) == 1)
-              return e;
-            return ~uint64_t(0);
-          };
-          const uintptr_t pg = pages.empty() ? 0 : pages[0];
-          fprintf(stderr, "RSX_DIAG_DOWNLOAD: pagemap bad %016llx prev %016llx next-good %016llx image[0] %016llx\n",
-                  (unsigned long long)entry(pg), (unsigned long long)entry(pg - 4096),
-                  (unsigned long long)entry(pages.empty() ? 0 : pages.back() + 4096),
-                  (unsigned long long)entry(reinterpret_cast<uintptr_t>(img->data)));
-          fclose(pm);
-        }
-        // A0: what does the DEVICE read from those host pages?  The rows up (the runtime pins the
-        // caller's pages for that as well), down again into memory of our own, compared with
-        // what the CPU reads there: bytes that come back as the decoded pixels although the CPU
-        // sees the fill = the device and the CPU look at different physical pages
-        {
-          void* d_tmp = nullptr;
-          if (hipMalloc(&d_tmp, chk.size()) == hipSuccess) {
-            std::vector<uint8_t> back(chk.size());
-            const uint8_t* rows0 = static_cast<uint8_t*>(img->data) + r0 * pitch;
-            RSX_HIP_CHECK(ctx, hipMemcpy(d_tmp, rows0, chk.size(), hipMemcpyHostToDevice));
-            RSX_HIP_CHECK(ctx, hipMemcpy(back.data(), d_tmp, chk.size(), hipMemcpyDeviceToHost));
-            size_t n_bad = 0, gpu_sees_pixels = 0, gpu_sees_fill = 0;
-            for (const HostRect& r : rects)
-              for (size_t y = 0; y < r.rows; ++y)
-                for (size_t x = 0; x < r.bytes; ++x) {
-                  const size_t o = (r.row0 + y - r0) * pitch + r.byte0 + x;
-                  if (rows0[o] != chk[o]) {
-                    ++n_bad;
-                    gpu_sees_pixels += back[o] == chk[o];
-                    gpu_sees_fill += back[o] == rows0[o];
-                  }
-                }
-            fprintf(stderr, "RSX_DIAG_DOWNLOAD: A0 of %zu undelivered bytes the device reads %zu as the decoded "
-                    "pixels and %zu as what the CPU sees\n", n_bad, gpu_sees_pixels, gpu_sees_fill);
-            (void)hipFree(d_tmp);
-          }
-        }
-        // A: the same 2-D copies once more
-        if (int e = again2d()) return e;
-        fprintf(stderr, "RSX_DIAG_DOWNLOAD: A after repeating the 2-D copies %zu rows still differ\n", still_bad(nullptr));
-        // B: the CPU writes one byte of every such page (the value it holds), then the copies again
-        for (uintptr_t pg : pages) {
-          volatile uint8_t* q = reinterpret_cast<volatile uint8_t*>(pg);
-          const uint8_t v = q[0];
-          q[0] = v;
-        }
-        if (int e = again2d()) return e;
-        fprintf(stderr, "RSX_DIAG_DOWNLOAD: B after a CPU write to each of the pages + the 2-D copies %zu rows still differ\n", still_bad(nullptr));
-        // C: page-lock the rows (hipHostRegister), the copies again
-        {
-          uint8_t* base = static_cast<uint8_t*>(img->data) + r0 * pitch;
-          const hipError_t er = hipHostRegister(base, (r1 - r0) * pitch, hipHostRegisterDefault);
-          if (er == hipSuccess) {
-            if (int e = again2d()) return e;
-            fprintf(stderr, "RSX_DIAG_DOWNLOAD: C with the rows registered (page-locked) %zu rows still differ\n", still_bad(nullptr));
-            (void)hipHostUnregister(base);
-          } else {
-            (void)hipGetLastError();
-            fprintf(stderr, "RSX_DIAG_DOWNLOAD: C hipHostRegister failed: %s\n", hipGetErrorString(er));
-          }
-        }
-        // D: ONE contiguous copy of the rows straight into the image (diagnostic only: it writes the padding too)
-        RSX_HIP_CHECK(ctx, hipMemcpy(static_cast<uint8_t*>(img->data) + r0 * pitch, out_row0 + r0 * pitch,
-                                     (r1 - r0) * pitch, hipMemcpyDeviceToHost));
-        fprintf(stderr, "RSX_DIAG_DOWNLOAD: D after one contiguous copy of the rows into the image %zu rows still differ\n", still_bad(nullptr));
-      }
-      if ((calls & 63) == 0 || bad)
-        fprintf(stderr, "RSX_DIAG_DOWNLOAD: %llu calls checked, %llu with undelivered bytes\n",
-                (unsigned long long)calls.load(), (unsigned long long)bad_calls.load());
-    }
-  }
-#endif
   return rc;
+}
+
+// The one-job host-pointer calls: the job is the call's descriptor (none for DescT void: Sony
+// ARW1) and input size.
+template <typename JobT, typename DescT>
+int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_bytes,
+                 const rsx_image* img, PlanCreateFn<JobT> create, uint32_t* consumed = nullptr) {
+  constexpr bool has_desc = !std::is_void<DescT>::value;
+  if (!ctx || (has_desc && !d) || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  std::vector<JobT> jobs(1);
+  if constexpr (has_desc)
+    jobs[0].desc = *d;
+  jobs[0].in_bytes = in_bytes;
+  int32_t st = RSX_OK;
+  uint32_t c = 0;
+  const int rc = ljpeg_family_host(ctx, 1, jobs, &in, img, create, &st, &c);
+  if (consumed)
+    *consumed = c;
+  return rc;
+}
+
+// One image through a host-pointer call of Phase One or ARW2: `span` bytes from `src` up as one
+// copy, the lane's plan for `key` run on them (on_reuse(plan, stream): this call's data onto a
+// plan the lane held), the row statuses out, and the image back as one rectangle through
+// download_rects -- only when every row decoded (the reference throws otherwise, and the
+// caller's image stays as it was).
+template <typename JobT, typename ReuseFn>
+int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
+                      const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
+                      int32_t* row_status, ReuseFn on_reuse) {
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  LaneGuard lane(ctx, &key);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t out_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y);
+  if (int e = lane.lane->d_in.ensure(span + 64))
+    return e;
+  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  if (span) {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, src, span, hipMemcpyHostToDevice, s));
+  }
+  rsx_plan* plan = nullptr;
+  bool reused = false;
+  if (int st = lane_plan(ctx, lane.lane, key, create, 1, &job, &plan, &reused))
+    return st;
+  if (reused)
+    if (int st = on_reuse(plan, s))
+      return st;
+  int32_t st = RSX_OK;
+  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
+  if (rc == RSX_OK)
+    rc = rsx_plan_results(plan, &st, nullptr);
+  if (rc == RSX_OK || rc == st) {
+    if (row_status)
+      if (int e = plan->dec->row_status(s, 0, row_status))
+        rc = e;
+  }
+  if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
+    evict_plan(lane.lane);
+    return rc;
+  }
+  if (rc != RSX_OK)
+    return rc; // (a failing row: nothing goes back into the caller's image)
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
+              size_t(img->dim_x) * 2, size_t(img->dim_y)};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  return download_rects(ctx, lane.lane, s, &dr, 1);
 }
 
 } // namespace
@@ -2707,110 +2440,50 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
 extern "C" int rsx_ljpeg_decode(rsx_ctx* ctx, const rsx_ljpeg_desc* d,
                                 const uint8_t* in, size_t in_bytes,
                                 const rsx_image* img, uint32_t* consumed) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_ljpeg_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  uint32_t c = 0;
-  const int rc = ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_ljpeg_plan_create,
-                                   &st, &c);
-  if (consumed)
-    *consumed = c;
-  return rc;
+  return one_job_host<rsx_ljpeg_job>(ctx, d, in, in_bytes, img, rsx_ljpeg_plan_create, consumed);
 }
 
 extern "C" int rsx_cr2_decode(rsx_ctx* ctx, const rsx_cr2_desc* d,
                               const uint8_t* in, size_t in_bytes,
                               const rsx_image* img, uint32_t* consumed) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_cr2_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  uint32_t c = 0;
-  const int rc = ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_cr2_plan_create,
-                                   &st, &c);
-  if (consumed)
-    *consumed = c;
-  return rc;
+  return one_job_host<rsx_cr2_job>(ctx, d, in, in_bytes, img, rsx_cr2_plan_create, consumed);
 }
 
 extern "C" int rsx_nikon_decompress(rsx_ctx* ctx, const rsx_nikon_desc* d,
                                     const uint8_t* in, size_t in_bytes,
                                     const rsx_image* img) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_nikon_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  return ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_nikon_plan_create, &st, nullptr);
+  return one_job_host<rsx_nikon_job>(ctx, d, in, in_bytes, img, rsx_nikon_plan_create);
 }
 
 extern "C" int rsx_pentax_decompress(rsx_ctx* ctx, const rsx_pentax_desc* d,
                                      const uint8_t* in, size_t in_bytes,
                                      const rsx_image* img) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_pentax_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  return ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_pentax_plan_create, &st, nullptr);
+  return one_job_host<rsx_pentax_job>(ctx, d, in, in_bytes, img, rsx_pentax_plan_create);
 }
 
 extern "C" int rsx_hasselblad_decompress(rsx_ctx* ctx, const rsx_hasselblad_desc* d,
                                          const uint8_t* in, size_t in_bytes,
                                          const rsx_image* img, uint32_t* consumed) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_hasselblad_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  uint32_t c = 0;
-  const int rc =
-      ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_hasselblad_plan_create, &st, &c);
-  if (consumed)
-    *consumed = c;
-  return rc;
+  return one_job_host<rsx_hasselblad_job>(ctx, d, in, in_bytes, img, rsx_hasselblad_plan_create,
+                                          consumed);
 }
 
 extern "C" int rsx_samsung_v1_decompress(rsx_ctx* ctx, const rsx_samsung_v1_desc* d,
                                          const uint8_t* in, size_t in_bytes,
                                          const rsx_image* img) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_samsung_v1_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  return ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_samsung_v1_plan_create, &st, nullptr);
+  return one_job_host<rsx_samsung_v1_job>(ctx, d, in, in_bytes, img, rsx_samsung_v1_plan_create);
 }
 
 extern "C" int rsx_samsung_v2_decompress(rsx_ctx* ctx, const rsx_samsung_v2_desc* d,
                                          const uint8_t* in, size_t in_bytes,
                                          const rsx_image* img) {
-  if (!ctx || !d || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_samsung_v2_job> jobs(1);
-  jobs[0].desc = *d;
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  return ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_samsung_v2_plan_create, &st, nullptr);
+  return one_job_host<rsx_samsung_v2_job>(ctx, d, in, in_bytes, img, rsx_samsung_v2_plan_create);
 }
 
 extern "C" int rsx_sony_arw1_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
                                         const rsx_image* img) {
-  if (!ctx || !in || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  std::vector<rsx_sony_arw1_job> jobs(1);
-  jobs[0].in_bytes = in_bytes;
-  int32_t st = RSX_OK;
-  return ljpeg_family_host(ctx, 1, jobs, &in, img, rsx_sony_arw1_plan_create, &st, nullptr);
+  return one_job_host<rsx_sony_arw1_job, void>(ctx, nullptr, in, in_bytes, img,
+                                               rsx_sony_arw1_plan_create);
 }
 
 extern "C" int rsx_dng_decompress_ljpeg(rsx_ctx* ctx, int n_tiles,
@@ -2936,24 +2609,11 @@ extern "C" int rsx_phase_one_validate(int n_strips, const rsx_phase_one_strip* s
 
 extern "C" int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs,
                                          rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_P1;
-  plan->n_jobs = n_jobs;
-  plan->job_status.assign(n_jobs, RSX_OK);
-  if (int st = phase_one_plan_create(ctx, n_jobs, jobs, &plan->p1))
-    return st;
-  *out_plan = plan.release();
-  return RSX_OK;
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, phase_one_plan_create);
 }
 
-// The host-pointer call: the bytes the strips cover go up as one copy, the image comes back
-// through download_rects -- only when every row decoded (the reference throws otherwise, and
-// the caller's image stays as it was).  The lane keeps the plan; its key holds the strip table.
+// The host-pointer call (single_image_host): the bytes the strips cover go up as one copy; the
+// plan's key holds the strip table.
 extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
                                         int n_strips, const rsx_phase_one_strip* strips,
                                         const rsx_image* img, int32_t* strip_status) {
@@ -2978,63 +2638,12 @@ extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t 
   job.img = *img;
   job.img.data = nullptr;
   std::vector<uint8_t> key;
-  {
-    const void* fn = reinterpret_cast<const void*>(rsx_phase_one_plan_create);
-    const uint8_t* p = reinterpret_cast<const uint8_t*>(&fn);
-    key.insert(key.end(), p, p + sizeof fn);
-    p = reinterpret_cast<const uint8_t*>(&job);
-    key.insert(key.end(), p, p + sizeof job);
-    p = reinterpret_cast<const uint8_t*>(local.data());
-    key.insert(key.end(), p, p + local.size() * sizeof(rsx_phase_one_strip));
-  }
+  key_create(key, rsx_phase_one_plan_create);
+  key_append(key, &job);
+  key_append(key, local.data(), local.size());
   job.strips = local.data();
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  LaneGuard lane(ctx, &key);
-  if (!lane.lane)
-    return RSX_ERR_DEVICE;
-  const size_t out_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y);
-  if (int e = lane.lane->d_in.ensure(span + 64))
-    return e;
-  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
-    return e;
-  hipStream_t s = lane.lane->stream;
-  if (span) {
-    std::lock_guard<std::mutex> up(ctx->upload_mu);
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, in + lo, span, hipMemcpyHostToDevice, s));
-  }
-  rsx_plan* plan = nullptr;
-  if (lane.lane->cached_plan && lane.lane->cached_key == key) {
-    plan = lane.lane->cached_plan;
-  } else {
-    if (lane.lane->cached_plan)
-      rsx_plan_destroy(lane.lane->cached_plan);
-    lane.lane->cached_plan = nullptr;
-    if (int st = rsx_phase_one_plan_create(ctx, 1, &job, &plan))
-      return st;
-    lane.lane->cached_plan = plan;
-    lane.lane->cached_key = std::move(key);
-  }
-  int32_t st = RSX_OK;
-  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
-  if (rc == RSX_OK)
-    rc = rsx_plan_results(plan, &st, nullptr);
-  if (rc == RSX_OK || rc == st) {
-    if (strip_status)
-      if (int e = phase_one_plan_row_status(plan->p1, s, 0, strip_status))
-        rc = e;
-  }
-  if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
-    rsx_plan_destroy(lane.lane->cached_plan);
-    lane.lane->cached_plan = nullptr;
-    return rc;
-  }
-  if (rc != RSX_OK)
-    return rc; // (a failing row: nothing goes back into the caller's image)
-  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
-              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
-              size_t(img->dim_x) * 2, size_t(img->dim_y)};
-  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
-  return download_rects(ctx, lane.lane, s, &dr, 1);
+  return single_image_host(ctx, key, rsx_phase_one_plan_create, job, in + lo, span, img,
+                           strip_status, [](rsx_plan*, hipStream_t) { return RSX_OK; });
 }
 
 // ---------------------------------------------------------------------------
@@ -3049,29 +2658,12 @@ extern "C" int rsx_sony_arw2_validate(const rsx_sony_arw2_desc* desc, const rsx_
 
 extern "C" int rsx_sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* jobs,
                                          rsx_plan** out_plan) {
-  if (!ctx || !jobs || n_jobs < 1 || !out_plan)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto plan = std::make_unique<rsx_plan>();
-  plan->ctx = ctx;
-  plan->kind = PLAN_A2;
-  plan->n_jobs = n_jobs;
-  plan->job_status.assign(n_jobs, RSX_OK);
-  plan->a2_consumed.assign(n_jobs, 0);
-  for (int i = 0; i < n_jobs; ++i)
-    if (sony_arw2_validate(&jobs[i].desc, jobs[i].img, size_t(jobs[i].in_bytes)) == RSX_OK)
-      plan->a2_consumed[i] = uint32_t(jobs[i].img.dim_x) * uint32_t(jobs[i].img.dim_y);
-  if (int st = sony_arw2_plan_create(ctx, n_jobs, jobs, &plan->a2))
-    return st;
-  *out_plan = plan.release();
-  return RSX_OK;
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, sony_arw2_plan_create);
 }
 
-// The host-pointer call: the w * h bytes go up as one copy, the image comes back as one
-// rectangle through download_rects -- only when every row decoded (the reference throws
-// otherwise, and the caller's image stays as it was).  The lane keeps the plan, keyed by the
-// geometry and the table mode; the table itself is call data and goes up on every call.
+// The host-pointer call (single_image_host): the w * h bytes go up as one copy.  The plan is
+// keyed by the geometry and the table mode; the table itself is call data and goes up on every
+// call.
 extern "C" int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* desc,
                                         const uint8_t* in, size_t in_bytes, const rsx_image* img,
                                         int32_t* row_status) {
@@ -3088,64 +2680,14 @@ extern "C" int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* 
   job.img = *img;
   job.img.data = nullptr;
   std::vector<uint8_t> key;
-  {
-    const void* fn = reinterpret_cast<const void*>(rsx_sony_arw2_plan_create);
-    const uint8_t* p = reinterpret_cast<const uint8_t*>(&fn);
-    key.insert(key.end(), p, p + sizeof fn);
-    p = reinterpret_cast<const uint8_t*>(&job); // (desc.table is NULL here: not in the key)
-    key.insert(key.end(), p, p + sizeof job);
-  }
+  key_create(key, rsx_sony_arw2_plan_create);
+  key_append(key, &job); // (desc.table is NULL here: not in the key)
   job.desc.table = desc->table;
-  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  LaneGuard lane(ctx, &key);
-  if (!lane.lane)
-    return RSX_ERR_DEVICE;
-  const size_t out_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y);
-  if (int e = lane.lane->d_in.ensure(span + 64))
-    return e;
-  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
-    return e;
-  hipStream_t s = lane.lane->stream;
-  {
-    std::lock_guard<std::mutex> up(ctx->upload_mu);
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, in, span, hipMemcpyHostToDevice, s));
-  }
-  rsx_plan* plan = nullptr;
-  if (lane.lane->cached_plan && lane.lane->cached_key == key) {
-    plan = lane.lane->cached_plan;
-    // this call's table, ordered before the run on the lane's stream
-    if (int st = sony_arw2_plan_set_table(plan->a2, 0, desc, s))
-      return st;
-  } else {
-    if (lane.lane->cached_plan)
-      rsx_plan_destroy(lane.lane->cached_plan);
-    lane.lane->cached_plan = nullptr;
-    if (int st = rsx_sony_arw2_plan_create(ctx, 1, &job, &plan))
-      return st;
-    lane.lane->cached_plan = plan;
-    lane.lane->cached_key = std::move(key);
-  }
-  int32_t st = RSX_OK;
-  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
-  if (rc == RSX_OK)
-    rc = rsx_plan_results(plan, &st, nullptr);
-  if (rc == RSX_OK || rc == st) {
-    if (row_status)
-      if (int e = sony_arw2_plan_row_status(plan->a2, s, 0, row_status))
-        rc = e;
-  }
-  if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
-    rsx_plan_destroy(lane.lane->cached_plan);
-    lane.lane->cached_plan = nullptr;
-    return rc;
-  }
-  if (rc != RSX_OK)
-    return rc; // (a failing row: nothing goes back into the caller's image)
-  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
-              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
-              size_t(img->dim_x) * 2, size_t(img->dim_y)};
-  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
-  return download_rects(ctx, lane.lane, s, &dr, 1);
+  // this call's table onto a plan the lane held, ordered before the run on the lane's stream
+  return single_image_host(ctx, key, rsx_sony_arw2_plan_create, job, in, span, img, row_status,
+                           [desc](rsx_plan* plan, hipStream_t s) {
+                             return sony_arw2_plan_set_table(plan->dec.get(), 0, desc, s);
+                           });
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

@@ -169,6 +169,25 @@ struct DeviceBuffer {
   void release();
 };
 
+// The device plan of a decoder (the LJPEG family, SamsungV2, Phase One, ARW2): what a
+// rsx_plan of such a decoder runs, whichever decoder made it.  The destructor releases the
+// plan's device memory.
+struct KernelTimer; // rsx_ljpeg_dev.h: an event after every launch of a timed run
+struct LJpegPlan;   // rsx_ljpeg.hip
+struct DecoderPlan {
+  virtual ~DecoderPlan() = default;
+  virtual int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) = 0;
+  // per-job status and input bytes consumed (either may be NULL) of the run on `s`, if
+  // there was one (`ran`); returns the last failing job's status, or RSX_OK
+  virtual int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) = 0;
+  // the status of every image row of job `job` of the last run, after results (Phase One, ARW2)
+  virtual int row_status(hipStream_t, int /*job*/, int32_t* /*row_status*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
+  // the plan as an LJPEG-family plan (the chunked host path), or nullptr
+  virtual LJpegPlan* ljpeg() { return nullptr; }
+};
+
 // ------------------------------------------------------------------------
 // Helper threads of a context's host-pointer calls (the uploader of a banded unpack call,
 // the bands of a split DNG call): a few PERSISTENT workers that sleep on a condition
@@ -289,6 +308,9 @@ struct rsx_ctx {
     // camera's files) skips the plan's construction -- tables, block lists, a dozen uploads
     struct rsx_plan* cached_plan = nullptr;
     std::vector<uint8_t> cached_key;
+    bool holds_plan(const std::vector<uint8_t>& key) const {
+      return cached_plan && cached_key == key;
+    }
     // page-locked staging of the lane's downloads (rsx_api.hip, download_rects): what does not
     // lie on the 16-byte grid in the caller's memory goes through here, in two halves that take
     // turns (the copy of one chunk under the host's scatter of the one before)

@@ -46,7 +46,8 @@ struct LJpegPlan;
 
 int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
                       LJpegPlan** out);
-struct KernelTimer; // rsx_ljpeg_dev.h: an event after every launch of the run
+int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
+                      std::unique_ptr<DecoderPlan>* out);
 int ljpeg_plan_run(LJpegPlan* plan, const void* in_dev, void* out_dev,
                    hipStream_t stream, KernelTimer* timer);
 // (continue_timer: a child plan's launches go on in the parent's kernel table)
@@ -54,7 +55,6 @@ int ljpeg_plan_run_(LJpegPlan* plan, const void* in_dev, void* out_dev, hipStrea
                     KernelTimer* timer, bool continue_timer);
 int ljpeg_plan_results(LJpegPlan* plan, hipStream_t stream, bool ran,
                        int32_t* job_status, uint32_t* job_consumed);
-void ljpeg_plan_destroy(LJpegPlan* plan);
 
 // A run in chunks of the plan's blocks (round 6; rsx_api.hip, ljpeg_family_host): one stream of the
 // single-pass kernel, each chunk's K0 + kernel queued behind the upload of its bytes, the pixels a
@@ -70,9 +70,5 @@ int ljpeg_plan_run_end(LJpegPlan* plan, hipStream_t stream);
 int ljpeg_plan_symbols_done(LJpegPlan* plan, hipStream_t stream, uint32_t blk_end, uint64_t* symbols);
 void ljpeg_plan_region(const LJpegPlan* plan, uint64_t sym_lo, uint64_t sym_hi, std::vector<LjRegion>* out);
 bool ljpeg_plan_single_pass_held(const LJpegPlan* plan);
-
-struct LJpegPlanDeleter {
-  void operator()(LJpegPlan* p) const { ljpeg_plan_destroy(p); }
-};
 
 } // namespace rsx

@@ -3596,7 +3596,15 @@ __global__ __launch_bounds__(1024) void lj_dri_layout_kernel(
 // Host side
 // ---------------------------------------------------------------------------
 constexpr int RSX_INTERNAL_RETRY = -1000; // a device-laid-out child plan: redo the old way
-struct LJpegPlan {
+struct LJpegPlan final : DecoderPlan {
+  ~LJpegPlan() override;
+  int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override {
+    return ljpeg_plan_run(this, in_dev, out_dev, s, timer);
+  }
+  int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override {
+    return ljpeg_plan_results(this, s, ran, job_status, job_consumed);
+  }
+  LJpegPlan* ljpeg() override { return this; }
   rsx_ctx* ctx = nullptr;
   int n_jobs = 0;
   std::vector<int32_t> job_status;      // validation results
@@ -4475,6 +4483,14 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
   return RSX_OK;
 }
 
+int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
+                      std::unique_ptr<DecoderPlan>* out) {
+  LJpegPlan* p = nullptr;
+  const int st = ljpeg_plan_create(ctx, jobs, &p);
+  out->reset(p);
+  return st;
+}
+
 
 namespace {
 
@@ -4656,7 +4672,7 @@ int run_dri_host(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t s)
   }
   if (!p->child || signature != p->dri_signature) {
     if (p->child) {
-      ljpeg_plan_destroy(p->child);
+      delete p->child;
       p->child = nullptr;
     }
     std::vector<LJpegJobIn> jobs;
@@ -4749,7 +4765,7 @@ int run_dri_device(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t 
     for (int st : c->job_status)
       ok = ok && st == RSX_OK;
     if (!ok) {
-      ljpeg_plan_destroy(c);
+      delete c;
       return RSX_INTERNAL_RETRY;
     }
     c->dev_layout = true;
@@ -4772,7 +4788,7 @@ int run_dri_device(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t 
       st = RSX_ERR_DEVICE;
     }
     if (st != RSX_OK) {
-      ljpeg_plan_destroy(c);
+      delete c;
       return st;
     }
     p->child_dev = c;
@@ -4855,7 +4871,7 @@ int run_nikon_split(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t
   }
   if (!p->nk_child || signature != p->nk_signature) {
     if (p->nk_child) {
-      ljpeg_plan_destroy(p->nk_child);
+      delete p->nk_child;
       p->nk_child = nullptr;
     }
     std::vector<LJpegJobIn> jobs;
@@ -5640,30 +5656,24 @@ int ljpeg_plan_results(LJpegPlan* p, hipStream_t s, bool ran, int32_t* job_statu
   return rc;
 }
 
-void ljpeg_plan_destroy(LJpegPlan* p) {
-  if (!p)
-    return;
-  if (p->child)
-    ljpeg_plan_destroy(p->child);
-  if (p->child_dev)
-    ljpeg_plan_destroy(p->child_dev);
-  if (p->nk_child)
-    ljpeg_plan_destroy(p->nk_child);
-  for (DeviceBuffer* b : {&p->d_nk, &p->d_nk_tables, &p->d_nk_rowpow, &p->d_nk_pup,
-                          &p->d_transfer, &p->d_fast_tabs, &p->d_lb, &p->d_tickets, &p->d_dbg, &p->d_fast_z, &p->d_fast_level,
-                          &p->d_k0w, &p->d_k0e, &p->d_k0p, &p->d_block_base0,
-                          &p->d_fast_order})
+LJpegPlan::~LJpegPlan() {
+  delete child;
+  delete child_dev;
+  delete nk_child;
+  for (DeviceBuffer* b : {&d_nk, &d_nk_tables, &d_nk_rowpow, &d_nk_pup,
+                          &d_transfer, &d_fast_tabs, &d_lb, &d_tickets, &d_dbg, &d_fast_z, &d_fast_level,
+                          &d_k0w, &d_k0e, &d_k0p, &d_block_base0,
+                          &d_fast_order})
     b->release();
-  p->d_marker_count.release();
-  p->d_marker_list.release();
+  d_marker_count.release();
+  d_marker_list.release();
   for (DeviceBuffer* b :
-       {&p->d_streams, &p->d_tables, &p->d_block_stream, &p->d_strips,
-        &p->d_block_flags, &p->d_block_tf, &p->d_sub_start, &p->d_sub_state, &p->d_sub_sums, &p->d_sub_first, &p->d_sub_psum, &p->d_block_start, &p->d_block_exit,
-        &p->d_block_sum, &p->d_block_base, &p->d_block_psum, &p->d_block_pbase,
-        &p->d_block_drops, &p->d_block_drop_base, &p->d_results, &p->d_diffs, &p->d_vseed,
-        &p->d_row_edge, &p->d_unstuffed})
+       {&d_streams, &d_tables, &d_block_stream, &d_strips,
+        &d_block_flags, &d_block_tf, &d_sub_start, &d_sub_state, &d_sub_sums, &d_sub_first, &d_sub_psum, &d_block_start, &d_block_exit,
+        &d_block_sum, &d_block_base, &d_block_psum, &d_block_pbase,
+        &d_block_drops, &d_block_drop_base, &d_results, &d_diffs, &d_vseed,
+        &d_row_edge, &d_unstuffed})
     b->release();
-  delete p;
 }
 
 } // namespace rsx

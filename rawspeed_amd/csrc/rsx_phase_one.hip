@@ -294,7 +294,8 @@ __global__ void __launch_bounds__(P1_THREADS) p1_row_kernel(P1Args A) {
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-struct P1Plan {
+namespace {
+struct P1Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<P1JobDev> jobs;
   std::vector<int32_t> host_status; // validation result per job
@@ -302,8 +303,13 @@ struct P1Plan {
   DeviceBuffer d_jobs, d_rows, d_row_status, d_status;
   std::vector<uint32_t> h_status, h_row_status;
   uint32_t total_rows = 0, max_words = 0;
-  bool ran = false;
+  bool launched = false;
+  ~P1Plan() override;
+  int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
+  int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
+  int row_status(hipStream_t s, int job, int32_t* statuses) override;
 };
+} // namespace
 
 int phase_one_validate(int n_strips, const rsx_phase_one_strip* strips, size_t in_bytes,
                        const rsx_image& img) {
@@ -331,7 +337,8 @@ int phase_one_validate(int n_strips, const rsx_phase_one_strip* strips, size_t i
   return RSX_OK;
 }
 
-int phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs, P1Plan** out) {
+int phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs,
+                          std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<P1Plan>();
   p->ctx = ctx;
   p->host_status.assign(n_jobs, RSX_OK);
@@ -378,54 +385,50 @@ int phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* job
     RSX_HIP_CHECK(ctx, hipMemcpy(p->d_rows.ptr, rows.data(), rows.size() * sizeof(P1RowDev),
                                  hipMemcpyHostToDevice));
   p->h_status.assign(n_jobs, P1_NONE);
-  *out = p.release();
+  *out = std::move(p);
   return RSX_OK;
 }
 
-void phase_one_plan_destroy(P1Plan* p) {
-  if (!p)
-    return;
-  for (DeviceBuffer* b : {&p->d_jobs, &p->d_rows, &p->d_row_status, &p->d_status})
+P1Plan::~P1Plan() {
+  for (DeviceBuffer* b : {&d_jobs, &d_rows, &d_row_status, &d_status})
     b->release();
-  delete p;
 }
 
-int phase_one_plan_run(P1Plan* p, const void* in_dev, void* out_dev, hipStream_t s,
-                       KernelTimer* timer) {
-  rsx_ctx* ctx = p->ctx;
-  if (p->total_rows == 0)
+int P1Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
+  if (total_rows == 0)
     return RSX_OK; // (every job was rejected by the host)
   if (timer)
     timer->begin(s);
   P1Args A{};
   A.in_base = static_cast<const uint8_t*>(in_dev);
   A.out_base = static_cast<uint8_t*>(out_dev);
-  A.rows = static_cast<const P1RowDev*>(p->d_rows.ptr);
-  A.jobs = static_cast<const P1JobDev*>(p->d_jobs.ptr);
-  A.row_status = static_cast<uint32_t*>(p->d_row_status.ptr);
-  A.job_status = static_cast<uint32_t*>(p->d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(p->d_status.ptr, 0xFF, p->jobs.size() * 4, s));
-  const size_t lds = (size_t(P1_LDS_HEAD) + p->max_words) * 4;
-  hipLaunchKernelGGL(p1_row_kernel, dim3(p->total_rows), dim3(P1_THREADS), lds, s, A);
+  A.rows = static_cast<const P1RowDev*>(d_rows.ptr);
+  A.jobs = static_cast<const P1JobDev*>(d_jobs.ptr);
+  A.row_status = static_cast<uint32_t*>(d_row_status.ptr);
+  A.job_status = static_cast<uint32_t*>(d_status.ptr);
+  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, jobs.size() * 4, s));
+  const size_t lds = (size_t(P1_LDS_HEAD) + max_words) * 4;
+  hipLaunchKernelGGL(p1_row_kernel, dim3(total_rows), dim3(P1_THREADS), lds, s, A);
   if (timer)
     timer->mark("p1_row_kernel");
   RSX_HIP_CHECK(ctx, hipGetLastError());
-  p->ran = true;
+  launched = true;
   return RSX_OK;
 }
 
-int phase_one_plan_results(P1Plan* p, hipStream_t s, bool ran, int32_t* job_status) {
-  rsx_ctx* ctx = p->ctx;
-  if (ran && p->total_rows != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(p->h_status.data(), p->d_status.ptr, p->h_status.size() * 4,
+int P1Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
+  if (job_consumed)
+    std::fill(job_consumed, job_consumed + jobs.size(), 0u);
+  if (ran && total_rows != 0) {
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
                                       hipMemcpyDeviceToHost, s));
     RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
   int rc = RSX_OK;
-  for (size_t i = 0; i < p->jobs.size(); ++i) {
-    int st = p->host_status[i];
-    if (st == RSX_OK && ran && p->h_status[i] != P1_NONE)
-      st = int(p->h_status[i] & 0xFFu);
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    int st = host_status[i];
+    if (st == RSX_OK && ran && h_status[i] != P1_NONE)
+      st = int(h_status[i] & 0xFFu);
     if (job_status)
       job_status[i] = st;
     if (st != RSX_OK)
@@ -434,18 +437,17 @@ int phase_one_plan_results(P1Plan* p, hipStream_t s, bool ran, int32_t* job_stat
   return rc;
 }
 
-int phase_one_plan_row_status(P1Plan* p, hipStream_t s, int job, int32_t* row_status) {
-  rsx_ctx* ctx = p->ctx;
-  if (job < 0 || size_t(job) >= p->jobs.size() || !p->ran || p->job_rows[job] == 0)
+int P1Plan::row_status(hipStream_t s, int job, int32_t* statuses) {
+  if (job < 0 || size_t(job) >= jobs.size() || !launched || job_rows[job] == 0)
     return RSX_ERR_INVALID_ARG;
-  const uint32_t n = p->job_rows[job];
-  p->h_row_status.resize(n);
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(p->h_row_status.data(),
-                                    static_cast<const uint32_t*>(p->d_row_status.ptr) + p->jobs[job].row_base,
+  const uint32_t n = job_rows[job];
+  h_row_status.resize(n);
+  RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_row_status.data(),
+                                    static_cast<const uint32_t*>(d_row_status.ptr) + jobs[job].row_base,
                                     size_t(n) * 4, hipMemcpyDeviceToHost, s));
   RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
   for (uint32_t r = 0; r < n; ++r)
-    row_status[r] = int32_t(p->h_row_status[r]);
+    statuses[r] = int32_t(h_row_status[r]);
   return RSX_OK;
 }
 

@@ -638,7 +638,8 @@ __global__ __launch_bounds__(SV2_RT) void sv2_recon_kernel(Sv2Args A) {
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-struct Sv2Plan {
+namespace {
+struct Sv2Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<Sv2JobDev> jobs;
   std::vector<int32_t> host_status; // validation result per job
@@ -646,7 +647,11 @@ struct Sv2Plan {
   std::vector<uint32_t> h_status;
   uint32_t max_bounds = 0, max_rows = 0, max_blocks = 0;
   bool aligned8 = true; // every job's image rows start at multiples of 8 bytes
+  ~Sv2Plan() override;
+  int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
+  int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
 };
+} // namespace
 
 int samsung_v2_validate(const rsx_samsung_v2_desc& d, const rsx_image& img) {
   // the constructor, SamsungV2Decompressor.cpp:87-141
@@ -666,7 +671,7 @@ int samsung_v2_validate(const rsx_samsung_v2_desc& d, const rsx_image& img) {
 }
 
 int samsung_v2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v2_job* jobs,
-                           Sv2Plan** out) {
+                           std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<Sv2Plan>();
   p->ctx = ctx;
   p->host_status.assign(n_jobs, RSX_OK);
@@ -724,24 +729,19 @@ int samsung_v2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v2_job* j
   RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(Sv2JobDev),
                                hipMemcpyHostToDevice));
   p->h_status.assign(n_jobs, SV2_NONE);
-  *out = p.release();
+  *out = std::move(p);
   return RSX_OK;
 }
 
-void samsung_v2_plan_destroy(Sv2Plan* p) {
-  if (!p)
-    return;
-  for (DeviceBuffer* b : {&p->d_jobs, &p->d_next, &p->d_ja, &p->d_jb, &p->d_row_start,
-                          &p->d_row_status, &p->d_hdr, &p->d_dq, &p->d_diffs, &p->d_status})
+Sv2Plan::~Sv2Plan() {
+  for (DeviceBuffer* b : {&d_jobs, &d_next, &d_ja, &d_jb, &d_row_start, &d_row_status, &d_hdr,
+                          &d_dq, &d_diffs, &d_status})
     b->release();
-  delete p;
 }
 
-int samsung_v2_plan_run(Sv2Plan* p, const void* in_dev, void* out_dev, hipStream_t s,
-                        KernelTimer* timer) {
-  rsx_ctx* ctx = p->ctx;
-  const uint32_t n = uint32_t(p->jobs.size());
-  if (p->max_rows == 0)
+int Sv2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
+  const uint32_t n = uint32_t(jobs.size());
+  if (max_rows == 0)
     return RSX_OK; // (every job was rejected by the host)
   // The reconstruction's LDS ring is 66 KB: more than a kernel gets without asking, and
   // the attribute is per DEVICE (a function-local static set it for whichever device was
@@ -758,23 +758,23 @@ int samsung_v2_plan_run(Sv2Plan* p, const void* in_dev, void* out_dev, hipStream
   Sv2Args A{};
   A.in_base = static_cast<const uint8_t*>(in_dev);
   A.out_base = static_cast<uint8_t*>(out_dev);
-  A.jobs = static_cast<const Sv2JobDev*>(p->d_jobs.ptr);
-  A.next = static_cast<uint32_t*>(p->d_next.ptr);
-  A.jump_a = static_cast<uint32_t*>(p->d_ja.ptr);
-  A.jump_b = static_cast<uint32_t*>(p->d_jb.ptr);
-  A.row_start = static_cast<uint32_t*>(p->d_row_start.ptr);
-  A.row_status = static_cast<uint32_t*>(p->d_row_status.ptr);
-  A.hdr = static_cast<uint32_t*>(p->d_hdr.ptr);
-  A.dq = static_cast<uint32_t*>(p->d_dq.ptr);
-  A.diffs = static_cast<int16_t*>(p->d_diffs.ptr);
-  A.job_status = static_cast<uint32_t*>(p->d_status.ptr);
+  A.jobs = static_cast<const Sv2JobDev*>(d_jobs.ptr);
+  A.next = static_cast<uint32_t*>(d_next.ptr);
+  A.jump_a = static_cast<uint32_t*>(d_ja.ptr);
+  A.jump_b = static_cast<uint32_t*>(d_jb.ptr);
+  A.row_start = static_cast<uint32_t*>(d_row_start.ptr);
+  A.row_status = static_cast<uint32_t*>(d_row_status.ptr);
+  A.hdr = static_cast<uint32_t*>(d_hdr.ptr);
+  A.dq = static_cast<uint32_t*>(d_dq.ptr);
+  A.diffs = static_cast<int16_t*>(d_diffs.ptr);
+  A.job_status = static_cast<uint32_t*>(d_status.ptr);
   A.n_jobs = n;
   auto mark = [&](const char* name) {
     if (timer)
       timer->mark(name);
   };
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(p->d_status.ptr, 0xFF, size_t(n) * 4, s));
-  const dim3 gb((p->max_bounds + 255) / 256, n);
+  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, size_t(n) * 4, s));
+  const dim3 gb((max_bounds + 255) / 256, n);
   hipLaunchKernelGGL(sv2_spec_kernel, gb, dim3(256), 0, s, A);
   mark("sv2_spec_kernel");
   // 2, 4, 8, 16, 32 rows per hop
@@ -788,14 +788,14 @@ int samsung_v2_plan_run(Sv2Plan* p, const void* in_dev, void* out_dev, hipStream
   mark("sv2_double_kernel");
   hipLaunchKernelGGL(sv2_chain_kernel, dim3((n + 63) / 64), dim3(64), 0, s, A, from);
   mark("sv2_chain_kernel");
-  const uint32_t segs = (p->max_rows + SV2_HOP - 1) / SV2_HOP;
+  const uint32_t segs = (max_rows + SV2_HOP - 1) / SV2_HOP;
   hipLaunchKernelGGL(sv2_fill_kernel, dim3((segs + 255) / 256, n), dim3(256), 0, s, A);
   mark("sv2_fill_kernel");
-  hipLaunchKernelGGL(sv2_parse_kernel, dim3((p->max_rows + 63) / 64, n), dim3(64), 0, s, A);
+  hipLaunchKernelGGL(sv2_parse_kernel, dim3((max_rows + 63) / 64, n), dim3(64), 0, s, A);
   mark("sv2_parse_kernel");
-  hipLaunchKernelGGL(sv2_diffs_kernel, dim3((p->max_blocks + 255) / 256, n), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(sv2_diffs_kernel, dim3((max_blocks + 255) / 256, n), dim3(256), 0, s, A);
   mark("sv2_diffs_kernel");
-  if (p->aligned8)
+  if (aligned8)
     hipLaunchKernelGGL(sv2_recon_kernel<true>, dim3(n), dim3(SV2_RT), SV2_RING_BYTES, s, A);
   else
     hipLaunchKernelGGL(sv2_recon_kernel<false>, dim3(n), dim3(SV2_RT), SV2_RING_BYTES, s, A);
@@ -804,18 +804,19 @@ int samsung_v2_plan_run(Sv2Plan* p, const void* in_dev, void* out_dev, hipStream
   return RSX_OK;
 }
 
-int samsung_v2_plan_results(Sv2Plan* p, hipStream_t s, bool ran, int32_t* job_status) {
-  rsx_ctx* ctx = p->ctx;
-  if (ran && p->max_rows != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(p->h_status.data(), p->d_status.ptr, p->h_status.size() * 4,
+int Sv2Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
+  if (job_consumed)
+    std::fill(job_consumed, job_consumed + jobs.size(), 0u);
+  if (ran && max_rows != 0) {
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
                                       hipMemcpyDeviceToHost, s));
     RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
   int rc = RSX_OK;
-  for (size_t i = 0; i < p->jobs.size(); ++i) {
-    int st = p->host_status[i];
-    if (st == RSX_OK && ran && p->h_status[i] != SV2_NONE)
-      st = int(int8_t(p->h_status[i] & 0xFFu));
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    int st = host_status[i];
+    if (st == RSX_OK && ran && h_status[i] != SV2_NONE)
+      st = int(int8_t(h_status[i] & 0xFFu));
     if (job_status)
       job_status[i] = st;
     if (st != RSX_OK)

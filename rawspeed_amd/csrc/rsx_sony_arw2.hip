@@ -289,18 +289,25 @@ void a2_lut(const rsx_sony_arw2_desc& d, uint32_t* out) {
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-struct Arw2Plan {
+namespace {
+struct Arw2Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<A2JobDev> jobs;
   std::vector<int32_t> host_status; // validation result per job
+  std::vector<uint32_t> consumed;   // input bytes a job reads (w * h when validated)
   std::vector<uint32_t> job_rows;   // rows of a job (0 when rejected)
   std::vector<int32_t> job_mode;    // table mode per job
   std::vector<uint32_t> h_tables;   // device form of every job's table
   DeviceBuffer d_jobs, d_items, d_tables, d_pow, d_row_status, d_status;
   std::vector<uint32_t> h_status, h_row_status;
   uint32_t n_items = 0, total_rows = 0;
-  bool ran = false;
+  bool launched = false;
+  ~Arw2Plan() override;
+  int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
+  int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
+  int row_status(hipStream_t s, int job, int32_t* statuses) override;
 };
+} // namespace
 
 int sony_arw2_validate(const rsx_sony_arw2_desc* desc, const rsx_image& img, size_t in_bytes) {
   // the table SonyArw2Decompressor finds in mRaw (none, plain or dithering)
@@ -325,10 +332,12 @@ int sony_arw2_validate(const rsx_sony_arw2_desc* desc, const rsx_image& img, siz
   return RSX_OK;
 }
 
-int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* jobs, Arw2Plan** out) {
+int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* jobs,
+                          std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<Arw2Plan>();
   p->ctx = ctx;
   p->host_status.assign(n_jobs, RSX_OK);
+  p->consumed.assign(n_jobs, 0);
   p->job_rows.assign(n_jobs, 0);
   p->job_mode.assign(n_jobs, RSX_ARW2_TABLE_NONE);
   p->jobs.resize(n_jobs);
@@ -339,6 +348,8 @@ int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* job
     std::memset(&J, 0, sizeof J);
     J.table = A2_NO_TABLE;
     int st = sony_arw2_validate(&j.desc, j.img, size_t(j.in_bytes));
+    if (st == RSX_OK) // (also for a job the alignment check below turns down)
+      p->consumed[i] = uint32_t(j.img.dim_x) * uint32_t(j.img.dim_y);
     if (st == RSX_OK && (j.img_offset % 2 != 0 || j.img.pitch_bytes % 2 != 0))
       st = RSX_ERR_INVALID_ARG;
     p->host_status[i] = st;
@@ -384,30 +395,27 @@ int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* job
                                  hipMemcpyHostToDevice));
   RSX_HIP_CHECK(ctx, hipMemcpy(p->d_pow.ptr, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
   p->h_status.assign(n_jobs, A2_NONE);
-  *out = p.release();
+  *out = std::move(p);
   return RSX_OK;
 }
 
-void sony_arw2_plan_destroy(Arw2Plan* p) {
-  if (!p)
-    return;
-  for (DeviceBuffer* b : {&p->d_jobs, &p->d_items, &p->d_tables, &p->d_pow, &p->d_row_status,
-                          &p->d_status})
+Arw2Plan::~Arw2Plan() {
+  for (DeviceBuffer* b : {&d_jobs, &d_items, &d_tables, &d_pow, &d_row_status, &d_status})
     b->release();
-  delete p;
 }
 
-int sony_arw2_plan_set_table(Arw2Plan* p, int job, const rsx_sony_arw2_desc* desc, hipStream_t s) {
-  rsx_ctx* ctx = p->ctx;
-  if (job < 0 || size_t(job) >= p->jobs.size() || !desc || p->host_status[job] != RSX_OK ||
+int sony_arw2_plan_set_table(DecoderPlan* plan, int job, const rsx_sony_arw2_desc* desc, hipStream_t s) {
+  Arw2Plan* p = dynamic_cast<Arw2Plan*>(plan);
+  if (!p || job < 0 || size_t(job) >= p->jobs.size() || !desc || p->host_status[job] != RSX_OK ||
       desc->table_mode != p->job_mode[job])
     return RSX_ERR_INVALID_ARG;
+  rsx_ctx* ctx = p->ctx;
   if (desc->table_mode == RSX_ARW2_TABLE_NONE)
     return RSX_OK;
   if (!desc->table)
     return RSX_ERR_INVALID_ARG;
   // (h_tables is not touched again before the stream has passed the copy: every run ends in
-  // sony_arw2_plan_results, which waits for the stream)
+  // the plan's results, which wait for the stream)
   uint32_t* t = p->h_tables.data() + p->jobs[job].table;
   a2_lut(*desc, t);
   RSX_HIP_CHECK(ctx, hipMemcpyAsync(static_cast<uint32_t*>(p->d_tables.ptr) + p->jobs[job].table, t,
@@ -415,43 +423,42 @@ int sony_arw2_plan_set_table(Arw2Plan* p, int job, const rsx_sony_arw2_desc* des
   return RSX_OK;
 }
 
-int sony_arw2_plan_run(Arw2Plan* p, const void* in_dev, void* out_dev, hipStream_t s,
-                       KernelTimer* timer) {
-  rsx_ctx* ctx = p->ctx;
-  if (p->n_items == 0)
+int Arw2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
+  if (n_items == 0)
     return RSX_OK; // (every job was rejected by the host)
   A2Args A{};
   A.in_base = static_cast<const uint8_t*>(in_dev);
   A.out_base = static_cast<uint8_t*>(out_dev);
-  A.items = static_cast<const A2Item*>(p->d_items.ptr);
-  A.jobs = static_cast<const A2JobDev*>(p->d_jobs.ptr);
-  A.tables = static_cast<const uint32_t*>(p->d_tables.ptr);
-  A.pow16 = static_cast<const uint32_t*>(p->d_pow.ptr);
-  A.row_status = static_cast<uint32_t*>(p->d_row_status.ptr);
-  A.job_status = static_cast<uint32_t*>(p->d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(p->d_status.ptr, 0xFF, p->jobs.size() * 4, s));
+  A.items = static_cast<const A2Item*>(d_items.ptr);
+  A.jobs = static_cast<const A2JobDev*>(d_jobs.ptr);
+  A.tables = static_cast<const uint32_t*>(d_tables.ptr);
+  A.pow16 = static_cast<const uint32_t*>(d_pow.ptr);
+  A.row_status = static_cast<uint32_t*>(d_row_status.ptr);
+  A.job_status = static_cast<uint32_t*>(d_status.ptr);
+  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, jobs.size() * 4, s));
   if (timer)
     timer->begin(s);
-  hipLaunchKernelGGL(arw2_kernel, dim3(p->n_items), dim3(A2_THREADS), 0, s, A);
+  hipLaunchKernelGGL(arw2_kernel, dim3(n_items), dim3(A2_THREADS), 0, s, A);
   if (timer)
     timer->mark("arw2_kernel");
   RSX_HIP_CHECK(ctx, hipGetLastError());
-  p->ran = true;
+  launched = true;
   return RSX_OK;
 }
 
-int sony_arw2_plan_results(Arw2Plan* p, hipStream_t s, bool ran, int32_t* job_status) {
-  rsx_ctx* ctx = p->ctx;
-  if (ran && p->n_items != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(p->h_status.data(), p->d_status.ptr, p->h_status.size() * 4,
+int Arw2Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
+  if (job_consumed)
+    std::copy(consumed.begin(), consumed.end(), job_consumed);
+  if (ran && n_items != 0) {
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
                                       hipMemcpyDeviceToHost, s));
     RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
   int rc = RSX_OK;
-  for (size_t i = 0; i < p->jobs.size(); ++i) {
-    int st = p->host_status[i];
-    if (st == RSX_OK && ran && p->h_status[i] != A2_NONE)
-      st = int(p->h_status[i] & 0xFFu);
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    int st = host_status[i];
+    if (st == RSX_OK && ran && h_status[i] != A2_NONE)
+      st = int(h_status[i] & 0xFFu);
     if (job_status)
       job_status[i] = st;
     if (st != RSX_OK)
@@ -460,18 +467,17 @@ int sony_arw2_plan_results(Arw2Plan* p, hipStream_t s, bool ran, int32_t* job_st
   return rc;
 }
 
-int sony_arw2_plan_row_status(Arw2Plan* p, hipStream_t s, int job, int32_t* row_status) {
-  rsx_ctx* ctx = p->ctx;
-  if (job < 0 || size_t(job) >= p->jobs.size() || !p->ran || p->job_rows[job] == 0)
+int Arw2Plan::row_status(hipStream_t s, int job, int32_t* statuses) {
+  if (job < 0 || size_t(job) >= jobs.size() || !launched || job_rows[job] == 0)
     return RSX_ERR_INVALID_ARG;
-  const uint32_t n = p->job_rows[job];
-  p->h_row_status.resize(n);
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(p->h_row_status.data(),
-                                    static_cast<const uint32_t*>(p->d_row_status.ptr) + p->jobs[job].row_base,
+  const uint32_t n = job_rows[job];
+  h_row_status.resize(n);
+  RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_row_status.data(),
+                                    static_cast<const uint32_t*>(d_row_status.ptr) + jobs[job].row_base,
                                     size_t(n) * 4, hipMemcpyDeviceToHost, s));
   RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
   for (uint32_t r = 0; r < n; ++r)
-    row_status[r] = int32_t(p->h_row_status[r]);
+    statuses[r] = int32_t(h_row_status[r]);
   return RSX_OK;
 }
 
