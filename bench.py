@@ -9,7 +9,11 @@ already resident in HBM: FRAMES frames of BASELINE configs[1]
 launch through the C-ABI (rawspeed_amd/librsx.so).  The batch is larger than
 the 256 MiB Infinity Cache on purpose, so the rate is an HBM rate.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, checks the path it times
+bit-exactly, warms up, times the K steps, dumps (--dump-outputs) and prints the line.
+Everything else the benchmark measures runs with --full only (below).
 
 --dump-outputs DIR: after the timed steps, what the last of them decoded -- a fixed, seeded
 sample of rows of the u16 output frames, as float32, and the per-frame statuses -- goes to
@@ -20,27 +24,28 @@ process is one rank; started bare, `--gpus N` re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N` on 127.0.0.1.  Every rank decodes
 its own shard of independent frames -- weak scaling for the headline leg, no data-path
 collective; RCCL carries the barrier / max-reduction of the timing and, for the
-batched-LJPEG leg (BASELINE configs[4]: 256 frames sharded with dist.shard_range over
-the ranks), optionally the distribution of the packed batch from rank 0
+batched-LJPEG leg (--full; BASELINE configs[4]: 256 frames sharded with dist.shard_range
+over the ranks), optionally the distribution of the packed batch from rank 0
 (with N > 1 all three ways in one run -- every rank's own shard, grouped send/recv of
 each rank's shard from rank 0, one RCCL broadcast of the whole batch -- each timed apart
 from the decode and reported as `input_distribution`; --scatter / --broadcast: that one only).
 
-Rank 0 prints ONE JSON line (kept under 6 KB: the driver holds a tail of stdout).  At
-every N it carries
+Rank 0 prints ONE JSON line (kept under 6 KB: a caller may keep only a tail of stdout).
+Every run's line carries
   roofline      -- dominant kernel: algorithmic bytes / hipEvent-measured launch time of
-                   rank 0's launches (per GPU), plus the measured copy ceiling of the device
-                   for the same bytes
+                   rank 0's timed launches (per GPU)
+and with --full, at every N, also
+  roofline.copy_ceiling -- the measured copy ceiling of the device for the same bytes
   cpu_baseline  -- the unmodified reference (oracle/_ref) timed on this host's cores (rank 0)
   ljpeg.cfg5_batch_8192x5464 -- BASELINE configs[4] with its own in-run `roofline`
-and at N=1 also
+and at N=1
   ljpeg         -- summary of the LJPEG configs (cfg 3 / cfg 4 / cfg 5, clipped highlights,
                    uniform-random data): ms, GPix/s, fraction of the HBM peak, per-kernel
                    ms, CPU baselines, and -- replayed from profiles/ and labelled so -- the
                    VALU issue fraction and the measured HBM traffic of the pipeline
-Everything else measured the same way (bench_ljpeg.py: configs[0], single-frame latency of
-configs[1], the fixed-layout unpack entry points, Canon sRaw + Cr2sRawInterpolator, Nikon,
-Hasselblad, Sony ARW1, the host-pointer path, the full LJPEG legs) goes to
+Everything else measured the same way with --full (bench_ljpeg.py: configs[0], single-frame
+latency of configs[1], the fixed-layout unpack entry points, Canon sRaw + Cr2sRawInterpolator,
+Nikon, Hasselblad, Sony ARW1, the host-pointer path, the full LJPEG legs) goes to
 bench_extra.json next to this file (and to stderr); the line names it in `extra_file`.
 """
 import argparse
@@ -77,6 +82,10 @@ def parse():
     ap.add_argument("--frames", type=int, default=8, help="frames per GPU per step")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step decoded to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the copy ceiling, the CPU baselines, "
+                         "the batched-LJPEG leg and every other leg (the options below "
+                         "narrow that down)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-cfg5", action="store_true",
@@ -92,6 +101,9 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if (args.broadcast or args.scatter) and not args.full:
+        ap.error("--broadcast / --scatter belong to the batched-LJPEG leg, which runs "
+                 "with --full only")
     return args
 
 
@@ -595,10 +607,10 @@ def main():
         dump_outputs(args.dump_outputs, out, CFG2, F, plan, max(1, DUMP_ROWS // n_gpus),
                      "_rank%d" % rank if grp.enabled else "")
     per_rank = grp.gather_objects(round(F * w * h * args.steps / my_elapsed / 1e6, 1), dst=0)
-    # copy ceiling for the same read:write mix (outside the timed region): a plain
+    # --full: copy ceiling for the same read:write mix (outside the timed region): a plain
     # streaming kernel over the very same buffers
     copy_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             copy_ms = ctx.probe_stream_copy(inp.data_ptr(), F * h * (w * bps // 8),
                                             out.data_ptr(), F * h * opitch, stream, reps=20)
@@ -635,9 +647,9 @@ def main():
         },
     }
 
-    # BASELINE configs[4]: batch of independent LJPEG frames sharded over the GPUs
+    # --full: BASELINE configs[4], a batch of independent LJPEG frames sharded over the GPUs
     cfg5 = None
-    if not args.no_cfg5:
+    if args.full and not args.no_cfg5:
         try:
             del out, inp
             torch.cuda.empty_cache()
@@ -646,7 +658,8 @@ def main():
             cfg5 = {"error": repr(e)}
 
     # rank 0 at every N: `roofline` from ITS in-run kernel time (per GPU: every rank runs the
-    # same launch over its own frames) and `cpu_baseline`; the secondary legs at N = 1 only
+    # same launch over its own frames); with --full also `cpu_baseline` at every N and the
+    # secondary legs at N = 1 only
     if rank == 0:
         alg_bytes = F * (h * (w * bps // 8) + h * w * 2)  # packed read once + u16 written once
         if ktime:
@@ -670,7 +683,7 @@ def main():
                     "what": "plain 16-byte load / non-temporal store kernel over the same "
                             "buffers (same bytes in, same bytes out)",
                 }
-        if not args.no_extra and n_gpus == 1:
+        if args.full and not args.no_extra and n_gpus == 1:
             extra = {}
             try:
                 extra["cfg1_12bit_lsb_4096x3072"] = small_unpack_leg(
@@ -689,7 +702,7 @@ def main():
             except Exception as e:  # the headline number must survive
                 extra["error"] = repr(e)
             result["extra"] = extra
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline_unpack(
                     CFG2, packed[:h * (w * bps // 8)], expect=pxs[0])

@@ -10,7 +10,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$ROUND
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py > $OUT/bench_full.json 2> $OUT/bench_full.log
+python $REPO/bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.log
 rm -rf /tmp/p_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- \
   python $REPO/bench.py --no-cpu-baseline --no-extra --no-cfg5 > $OUT/bench_under_rocprof.json 2> /dev/null

@@ -62,8 +62,8 @@ def test_bench_self_launches_its_ranks():
 def test_bench_cfg5_distribution_over_rccl(mode):
     """The cfg-5 distribution path on RCCL when the box has at least two GPUs: rank 0
     hands the packed batch out (grouped send/recv of the shards, or one broadcast of the
-    whole batch whose shards differ), every rank decodes its shard bit-exactly.  Without a
-    flag -- what the driver's scaling run is -- the ONE JSON line carries all three records
+    whole batch whose shards differ), every rank decodes its shard bit-exactly.  With --full
+    and no other flag the ONE JSON line carries all three records
     (own shard, scatter, broadcast: kernel-only and distribution-inclusive scaling apart)."""
     import torch
     n = min(torch.cuda.device_count(), 8)
@@ -72,8 +72,9 @@ def test_bench_cfg5_distribution_over_rccl(mode):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", str(n),
-           "--steps", "2", "--warmup", "1", "--frames", "1", "--no-extra", "--no-cpu-baseline",
-           "--cfg5-total-frames", str(2 * n), "--cfg5-distinct", "3"] + ([mode] if mode else [])
+           "--steps", "2", "--warmup", "1", "--frames", "1", "--full", "--no-extra",
+           "--no-cpu-baseline", "--cfg5-total-frames", str(2 * n),
+           "--cfg5-distinct", "3"] + ([mode] if mode else [])
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -9,6 +9,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -102,3 +104,19 @@ def test_bench_does_not_replay_a_fraction_above_one(tmp_path, monkeypatch):
     rep = bench.replayed_ljpeg_counters()
     assert "valu_issue_frac" not in rep
     assert "r99" in rep["valu_issue_frac_rejected"]
+
+
+def test_bench_plain_run_leaves_the_other_legs_to_full(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.steps, a.warmup) == (False, 5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--scatter"])
+    a = bench.parse()
+    assert a.full and a.scatter
+    # the distribution modes belong to the cfg-5 leg, which a plain run does not reach
+    for flag in ("--scatter", "--broadcast"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", flag])
+        with pytest.raises(SystemExit):
+            bench.parse()
