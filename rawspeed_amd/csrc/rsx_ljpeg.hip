@@ -4054,7 +4054,7 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
     const bool fast3 = !direct_n && g.kind == 0 && !g.raw && !g.las && !g.pair &&
                        !g.no_vertical && g.n_comp == 3 && g.period == 3 && g.mcu_h == 1 &&
                        g.mcu_w == 3 && (J.n_tables == 1 || per_phase) && J.explicit_n == 0 &&
-                       g.row_samples >= 3 && g.row_samples % 3 == 0;
+                       g.row_samples >= 3 && g.row_samples % 3 == 0 && tables.size() < 0xFFFFu;
     if (fast3)
       S.fast = J.n_tables == 1 ? 1 : 3;
     // Round 6: a stream whose RECONSTRUCTION the legacy kernels do -- a Nikon-type predictor with its

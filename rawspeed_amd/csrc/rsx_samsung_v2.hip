@@ -546,6 +546,9 @@ __global__ __launch_bounds__(SV2_RT) void sv2_recon_kernel(Sv2Args A) {
       const_cast<int16_t*>(diffs), 0, int(uint32_t(H) * uint32_t(W) * 2u), 0x00027000);
   const __amdgpu_buffer_rsrc_t rs_out =
       __builtin_amdgcn_make_buffer_rsrc(out, 0, int(uint32_t(H) * uint32_t(pitch)), 0x00027000);
+  // (an image that spans 2 GiB or more -- a padded pitch -- is out of reach of the resource's
+  // 32-bit offsets: its pixels go out through 64-bit addresses)
+  const bool wide = uint64_t(H) * pitch >= (uint64_t(1) << 31);
   auto fetch = [&](int t, Sv2Fetch& dst) {
     int r, c;
     const bool ok = sv2_diag_block(nb, H, t, slot, &r, &c) && t < T;
@@ -618,7 +621,15 @@ __global__ __launch_bounds__(SV2_RT) void sv2_recon_kernel(Sv2Args A) {
       const uint32_t wi = (sv2_ring_addr(r, col + px0) & okm) | (uint32_t(SV2_RING_PX) & ~okm);
       *reinterpret_cast<uint2*>(&ring[wi]) = pk;
       const uint32_t oo = (uint32_t(r) * uint32_t(pitch) + uint32_t(col + px0) * 2u) | ~okm;
-      if (ALIGNED8) {
+      if (wide) {
+        if (ok) {
+          uint16_t* o = reinterpret_cast<uint16_t*>(out + uint64_t(r) * pitch + uint64_t(col + px0) * 2u);
+          o[0] = uint16_t(v4[0]);
+          o[1] = uint16_t(v4[1]);
+          o[2] = uint16_t(v4[2]);
+          o[3] = uint16_t(v4[3]);
+        }
+      } else if (ALIGNED8) {
         const sv2_u32x2 pv = {pk.x, pk.y};
         __builtin_amdgcn_raw_buffer_store_b64(pv, rs_out, oo, 0, 0);
       } else {
