@@ -540,6 +540,64 @@ int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* desc, const
                              size_t in_bytes, const rsx_image* img, int32_t* row_status);
 
 /* ------------------------------------------------------------------------ */
+/* 3j. PanasonicV5Decompressor, PanasonicV6Decompressor,                     */
+/*     PanasonicV7Decompressor                                               */
+/*    replaces PanasonicV5Decompressor::decompress()                         */
+/*    (decompressors/PanasonicV5Decompressor.cpp:253-264 -> processBlock     */
+/*    :209-234), PanasonicV6Decompressor::decompress() (PanasonicV6-         */
+/*    Decompressor.cpp:250-261 -> decompressBlock :176-220) and              */
+/*    PanasonicV7Decompressor::decompress() (PanasonicV7Decompressor.cpp     */
+/*    :91-104 -> decompressBlock :67-74).  Rw2Decoder keeps its host work:   */
+/*    the container, the version switch (decoders/Rw2Decoder.cpp:138-175)    */
+/*    and the metadata.  PanasonicV4Decompressor is NOT covered (it appends  */
+/*    to mRaw->mBadPixelPositions, which has no shape here yet).             */
+/*    The image is a run of 16-byte packets, each read as one 128-bit        */
+/*    little-endian number (bit 0 = the LSB of byte 0).  Packet p holds the  */
+/*    pixels [p n, (p + 1) n) in row-major order:                            */
+/*      version 7, bps 14, n = 9   pixel i = bits [14 i, 14 i + 14); packet  */
+/*                                 p at byte 16 p                            */
+/*      version 5, bps 12, n = 10  pixel i = bits [bps i, bps i + bps).  The */
+/*      version 5, bps 14, n = 9   input is cut into blocks of 0x4000 bytes  */
+/*                                 = 1024 packets; a block's bytes [0x1FF8,  */
+/*                                 0x4000) are read first, then [0, 0x1FF8): */
+/*                                 packet q of a block starts at its byte    */
+/*                                 (16 q + 0x1FF8) mod 0x4000, and packet    */
+/*                                 512 wraps around the block's end          */
+/*      version 6, bps 14, n = 11  from bit 128 down: two pixels of bps      */
+/*      version 6, bps 12, n = 14  bits, then per three pixels a 2-bit scale */
+/*                                 b (3 means 4) and three fields of 10 (8)  */
+/*                                 bits; packet p at byte 16 p.  Per column  */
+/*                                 parity, e = the field while no non-zero   */
+/*                                 field was met (a zero field repeats the   */
+/*                                 parity's last e), afterwards e = (field   */
+/*                                 << b) + max(0, last e - (Z << b)) with    */
+/*                                 Z = 0x200 (0x80), the second term only    */
+/*                                 for b < 4.  Stored: e - 15, or 0 for      */
+/*                                 e < 15; NOT clamped to bps bits.          */
+/*    rsx_panasonic_validate: desc NULL or a version other than 5, 6, 7 ->   */
+/*    RSX_ERR_INVALID_ARG; Rw2Decoder's own rules (:155-157, :165-167):      */
+/*    version 6 takes bps 12 or 14, version 7 bps 14; then the constructors' */
+/*    checks in their order (V5 :74-108, V6 :141-169, V7 :44-60): cpp 1,     */
+/*    bps 12 or 14, dim > 0 and dim_x % n == 0 (and pitch_bytes >= 2 dim_x), */
+/*    then "Insufficient count of input blocks": in_bytes / 16 < packets     */
+/*    (V6, V7), in_bytes / 0x4000 < ceil(packets / 1024) (V5).  All of them  */
+/*    are ThrowRDE -> RSX_ERR_INVALID_ARG.  A job consumes what peekStream   */
+/*    takes, 16 packets resp. 0x4000 ceil(packets / 1024) bytes; a count     */
+/*    that does not fit 32 bits -> RSX_ERR_UNSUPPORTED.  Bytes behind the    */
+/*    consumed count are not read.  Nothing in the data can fail             */
+/*    (decompress() is noexcept), so there is no per-row status.             */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_panasonic_desc {
+  int32_t version; /* PANASONIC_RAWFORMAT: 5, 6 or 7 */
+  int32_t bps;     /* PANASONIC_BITSPERSAMPLE */
+} rsx_panasonic_desc;
+
+int rsx_panasonic_validate(const rsx_panasonic_desc* desc, const rsx_image* img,
+                           size_t in_bytes);
+int rsx_panasonic_decompress(rsx_ctx* ctx, const rsx_panasonic_desc* desc, const uint8_t* in,
+                             size_t in_bytes, const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -699,6 +757,16 @@ typedef struct rsx_sony_arw2_job {
   rsx_image img; /* .data ignored */
 } rsx_sony_arw2_job;
 
+/* jobs of different versions, depths and geometries may share a plan; any in_offset, any
+ * even pitch_bytes >= 2 dim_x and any even img_offset */
+typedef struct rsx_panasonic_job {
+  rsx_panasonic_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_panasonic_job;
+
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */
@@ -730,6 +798,8 @@ int rsx_sony_arw1_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw1_job*
 int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* jobs,
                               rsx_plan** out_plan);
 int rsx_sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* jobs,
+                              rsx_plan** out_plan);
+int rsx_panasonic_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_job* jobs,
                               rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,

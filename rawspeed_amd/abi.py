@@ -227,6 +227,26 @@ def sony_arw2_desc(mode, table=None):
     return d, arr
 
 
+class PanasonicDesc(C.Structure):
+    _fields_ = [("version", C.c_int32), ("bps", C.c_int32)]
+
+
+class PanasonicJob(C.Structure):
+    _fields_ = [("desc", PanasonicDesc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def panasonic_pixels_per_packet(version, bps):
+    """pixels a 16-byte packet holds (include/rsx.h section 3j)"""
+    return {(5, 12): 10, (5, 14): 9, (6, 12): 14, (6, 14): 11, (7, 14): 9}[(version, bps)]
+
+
+def panasonic_consumed(version, bps, dim_x, dim_y):
+    """input bytes the decompressor's peekStream takes"""
+    packets = dim_x * dim_y // panasonic_pixels_per_packet(version, bps)
+    return -(-packets // 1024) * 0x4000 if version == 5 else 16 * packets
+
+
 def phase_one_strips(table):
     """[(row, offset, bytes)] -> a ctypes array of rsx_phase_one_strip"""
     arr = (PhaseOneStrip * max(1, len(table)))()

@@ -32,6 +32,7 @@ EXPORTS = [
     "rsx_sony_arw1_validate", "rsx_sony_arw1_decompress", "rsx_sony_arw1_plan_create",
     "rsx_phase_one_validate", "rsx_phase_one_decompress", "rsx_phase_one_plan_create",
     "rsx_sony_arw2_validate", "rsx_sony_arw2_decompress", "rsx_sony_arw2_plan_create",
+    "rsx_panasonic_validate", "rsx_panasonic_decompress", "rsx_panasonic_plan_create",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
@@ -99,6 +100,9 @@ def lib():
         L.rsx_sony_arw2_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsx_sony_arw2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_void_p]
+        L.rsx_panasonic_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_panasonic_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -119,7 +123,7 @@ def lib():
                      "rsx_samsung_v2_plan_create",
                      "rsx_sraw_plan_create", "rsx_hasselblad_plan_create",
                      "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
-                     "rsx_sony_arw2_plan_create"):
+                     "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -154,6 +158,14 @@ def sony_arw2_validate(mode, table, img_view, in_bytes):
         return lib().rsx_sony_arw2_validate(None, C.byref(img_view), in_bytes)
     d, keep = abi.sony_arw2_desc(mode, table)
     return lib().rsx_sony_arw2_validate(C.byref(d), C.byref(img_view), in_bytes)
+
+
+def panasonic_validate(version, bps, img_view, in_bytes):
+    """rsx_panasonic_validate; version None passes a NULL desc"""
+    if version is None:
+        return lib().rsx_panasonic_validate(None, C.byref(img_view), in_bytes)
+    d = abi.PanasonicDesc(version, bps)
+    return lib().rsx_panasonic_validate(C.byref(d), C.byref(img_view), in_bytes)
 
 
 def _u8(a):
@@ -315,6 +327,12 @@ class Context:
                                             C.byref(img_view), rs)
         return st, (list(rs)[:img_view.dim_y] if rows else None)
 
+    def panasonic_decompress(self, version, bps, data, img_view):
+        a = _u8(data)
+        d = abi.PanasonicDesc(version, bps)
+        return lib().rsx_panasonic_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
+                                              C.byref(img_view))
+
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
@@ -377,6 +395,10 @@ class Context:
     def sony_arw2_plan(self, jobs):
         """jobs: abi.SonyArw2Job (their tables are copied at plan creation)"""
         return Plan(self, "rsx_sony_arw2_plan_create", abi.SonyArw2Job, jobs)
+
+    def panasonic_plan(self, jobs):
+        """jobs: abi.PanasonicJob (versions, depths and geometries may mix)"""
+        return Plan(self, "rsx_panasonic_plan_create", abi.PanasonicJob, jobs)
 
     def pentax_plan(self, jobs):
         return Plan(self, "rsx_pentax_plan_create", abi.PentaxJob, jobs)

@@ -7,6 +7,7 @@
 #include "rsx_internal.h"
 #include "rsx_ljpeg.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_panasonic.h"
 #include "rsx_phase_one.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
@@ -2383,7 +2384,7 @@ int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_byte
   return rc;
 }
 
-// One image through a host-pointer call of Phase One or ARW2: `span` bytes from `src` up as one
+// One image through a host-pointer call of Phase One, ARW2 or Panasonic: `span` bytes from `src` up as one
 // copy, the lane's plan for `key` run on them (on_reuse(plan, stream): this call's data onto a
 // plan the lane held), the row statuses out, and the image back as one rectangle through
 // download_rects -- only when every row decoded (the reference throws otherwise, and the
@@ -2688,6 +2689,44 @@ extern "C" int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* 
                            [desc](rsx_plan* plan, hipStream_t s) {
                              return sony_arw2_plan_set_table(plan->dec.get(), 0, desc, s);
                            });
+}
+
+// ---------------------------------------------------------------------------
+// PanasonicV5Decompressor, PanasonicV6Decompressor, PanasonicV7Decompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_panasonic_validate(const rsx_panasonic_desc* desc, const rsx_image* img,
+                                      size_t in_bytes) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return panasonic_validate(desc, *img, in_bytes);
+}
+
+extern "C" int rsx_panasonic_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_job* jobs,
+                                         rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, panasonic_plan_create);
+}
+
+// The host-pointer call (single_image_host): the bytes the constructor's peekStream takes go up
+// as one copy.  The plan is keyed by version, bps and geometry; nothing is per-call data.
+extern "C" int rsx_panasonic_decompress(rsx_ctx* ctx, const rsx_panasonic_desc* desc,
+                                        const uint8_t* in, size_t in_bytes, const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  uint64_t span = 0;
+  if (int st = panasonic_validate(desc, *img, in_bytes, &span))
+    return st;
+  rsx_panasonic_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *desc;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  key_create(key, rsx_panasonic_plan_create);
+  key_append(key, &job);
+  return single_image_host(ctx, key, rsx_panasonic_plan_create, job, in, size_t(span), img, nullptr,
+                           [](rsx_plan*, hipStream_t) { return RSX_OK; });
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

@@ -23,6 +23,8 @@
 #include "common/RawImage.h"
 #include "common/TableLookUp.h"
 #include "decoders/RawDecoderException.h"
+#include "io/Buffer.h"
+#include "io/ByteStream.h"
 #include "io/IOException.h"
 
 #include <atomic>
@@ -73,6 +75,18 @@ inline rsx_sony_arw2_desc arw2_desc(const TableLookUp* t) {
                     : (t->dither ? RSX_ARW2_TABLE_DITHER : RSX_ARW2_TABLE_PLAIN);
   d.table = t ? t->tables.data() : nullptr; // (table 0; the call reads its first 4096 / 8192)
   return d;
+}
+
+// PanasonicV5Decompressor / V6 / V7::decompress(): the descriptor and the call;
+// `input` is the stream the constructor kept (exactly the bytes peekStream took)
+inline int panasonic(int version, uint32_t bps, const ByteStream& input, const RawImage& img) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  const rsx_panasonic_desc d{version, implicit_cast<int32_t>(bps)};
+  const rsx_image v = view(img);
+  const Buffer in = input.peekRemainingBuffer();
+  return rsx_panasonic_decompress(rsx, &d, in.begin(), in.getSize(), &v);
 }
 
 // status -> the exception the reference would have thrown
