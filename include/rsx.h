@@ -598,6 +598,59 @@ int rsx_panasonic_decompress(rsx_ctx* ctx, const rsx_panasonic_desc* desc, const
                              size_t in_bytes, const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 3k. SamsungV0Decompressor                                                 */
+/*    replaces SamsungV0Decompressor::decompress()                           */
+/*    (decompressors/SamsungV0Decompressor.cpp:92-102 -> decompressStrip     */
+/*    :110-204 for every row, then the swap).  SrwDecoder keeps its host     */
+/*    work (decoders/SrwDecoder.cpp:85-106): tag 40976 holds the file offset */
+/*    of dim_y little-endian u32 row offsets (`bso`), `in` is the strip      */
+/*    (`bsr`).  Row y is the bytes [off[y], off[y + 1]) of `in`, off[dim_y]  */
+/*    = in_bytes; each is a BitStreamerMSB32 over exactly its own bytes      */
+/*    (bytes behind the row read as zero, not as the next row).  len[0..3]   */
+/*    start at 7 for rows 0 and 1, at 4 otherwise.  Per block of 16 columns: */
+/*    1 bit dir, four 2-bit ops, then for i = 0..3: op 3 len[i] = 4 bits,    */
+/*    op 2 len[i]--, op 1 len[i]++, op 0 keep; the 8 even pixels (len[c>>3]) */
+/*    and the 8 odd ones (len[2 | c >> 3]) follow, each signExtend(bits(n),  */
+/*    n), 0 for n = 0.  dir 0: pixel = adj + the block's left neighbour of   */
+/*    the same parity, out(row, col - 2) resp. out(row, col - 1), 128 at     */
+/*    col 0 -- one predictor for all eight; pixels at col + c >= dim_x are   */
+/*    read, not written.  dir 1: even pixel = adj + out(row - 1, col + c),   */
+/*    odd pixel = adj + out(row - 2, col + c).  All mod 2^16.  At the end    */
+/*    out(row, col + 1) <-> out(row + 1, col) for even row < dim_y - 1 and   */
+/*    even col < dim_x - 1.                                                  */
+/*    rsx_samsung_v0_validate = the constructor's checks, then               */
+/*    computeStripes' (:44-90), in their order: cpp 1, 16 <= dim_x <= 5546,  */
+/*    1 <= dim_y <= 3714 (and pitch_bytes >= 2 dim_x) -> RSX_ERR_INVALID_ARG;*/
+/*    in_bytes >= 4 GiB -> RSX_ERR_UNSUPPORTED (the offsets are 32-bit);     */
+/*    n_offsets < dim_y (peekStream) -> RSX_ERR_IO; off[0] > in_bytes        */
+/*    (skipBytes) -> RSX_ERR_IO; then pair by pair: off[y] >= off[y + 1]     */
+/*    ("Line offsets are out of sequence or slice is empty") ->              */
+/*    RSX_ERR_INVALID_ARG, off[y + 1] > in_bytes (getStream) -> RSX_ERR_IO.  */
+/*    Offsets behind the first dim_y are not read.                           */
+/*    Per-row statuses, the first exception of the row in stream order:      */
+/*      RSX_ERR_IO              row shorter than 4 bytes ("Bit stream size   */
+/*                              is smaller than MaxProcessBytes")            */
+/*      RSX_ERR_INPUT_OVERFLOW  a refill more than 8 bytes past the row      */
+/*                              (BitStreamer.h:100-132): a request of n bits */
+/*                              after c consumed ones -- 32 at a block's     */
+/*                              start, 4 per op 3, len per pixel with        */
+/*                              len > 0 -- with 4 (ceil((c + n) / 32) - 1)   */
+/*                              > size + 8                                   */
+/*      RSX_ERR_VALUE_RANGE     a length below 0 or above 16 (:147-150)      */
+/*      RSX_ERR_INVALID_ARG     dir 1 in rows 0, 1 or in the last block of a */
+/*                              row (:156-160)                               */
+/*    The reference throws at the first failing row; the call returns the    */
+/*    status of the lowest-numbered failing row, and through host pointers   */
+/*    leaves the caller's image untouched then.                              */
+/*    `row_status` (may be NULL) gets one status per image row.              */
+/* ------------------------------------------------------------------------ */
+int rsx_samsung_v0_validate(const uint32_t* row_offsets, int n_offsets, size_t in_bytes,
+                            const rsx_image* img);
+int rsx_samsung_v0_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                              const uint32_t* row_offsets, int n_offsets,
+                              const rsx_image* img, int32_t* row_status);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -767,6 +820,19 @@ typedef struct rsx_panasonic_job {
   rsx_image img; /* .data ignored */
 } rsx_panasonic_job;
 
+/* row offsets are relative to in_offset; jobs of different geometry may share a plan; any
+ * in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset.  The plan owns a scratch
+ * plane of dim_y x roundUp(dim_x, 16) 16-bit values per job. */
+typedef struct rsx_samsung_v0_job {
+  const uint32_t* row_offsets; /* host pointer, copied at plan creation */
+  int32_t n_offsets;
+  int32_t reserved;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_samsung_v0_job;
+
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */
@@ -801,6 +867,8 @@ int rsx_sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job*
                               rsx_plan** out_plan);
 int rsx_panasonic_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_job* jobs,
                               rsx_plan** out_plan);
+int rsx_samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_job* jobs,
+                               rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
                  void* stream);

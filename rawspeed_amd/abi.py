@@ -247,6 +247,20 @@ def panasonic_consumed(version, bps, dim_x, dim_y):
     return -(-packets // 1024) * 0x4000 if version == 5 else 16 * packets
 
 
+class SamsungV0Job(C.Structure):
+    _fields_ = [("row_offsets", C.POINTER(C.c_uint32)), ("n_offsets", C.c_int32),
+                ("reserved", C.c_int32), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def samsung_v0_offsets(offsets):
+    """row offsets -> a ctypes array of uint32 (include/rsx.h section 3k)"""
+    arr = (C.c_uint32 * max(1, len(offsets)))()
+    for i, o in enumerate(offsets):
+        arr[i] = o
+    return arr
+
+
 def phase_one_strips(table):
     """[(row, offset, bytes)] -> a ctypes array of rsx_phase_one_strip"""
     arr = (PhaseOneStrip * max(1, len(table)))()

@@ -33,6 +33,7 @@ EXPORTS = [
     "rsx_phase_one_validate", "rsx_phase_one_decompress", "rsx_phase_one_plan_create",
     "rsx_sony_arw2_validate", "rsx_sony_arw2_decompress", "rsx_sony_arw2_plan_create",
     "rsx_panasonic_validate", "rsx_panasonic_decompress", "rsx_panasonic_plan_create",
+    "rsx_samsung_v0_validate", "rsx_samsung_v0_decompress", "rsx_samsung_v0_plan_create",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
@@ -103,6 +104,9 @@ def lib():
         L.rsx_panasonic_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsx_panasonic_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.c_void_p]
+        L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+        L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -123,7 +127,8 @@ def lib():
                      "rsx_samsung_v2_plan_create",
                      "rsx_sraw_plan_create", "rsx_hasselblad_plan_create",
                      "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
-                     "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create"):
+                     "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
+                     "rsx_samsung_v0_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -166,6 +171,15 @@ def panasonic_validate(version, bps, img_view, in_bytes):
         return lib().rsx_panasonic_validate(None, C.byref(img_view), in_bytes)
     d = abi.PanasonicDesc(version, bps)
     return lib().rsx_panasonic_validate(C.byref(d), C.byref(img_view), in_bytes)
+
+
+def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
+    """rsx_samsung_v0_validate; offsets None passes a NULL table"""
+    if offsets is None:
+        return lib().rsx_samsung_v0_validate(None, n_offsets or 0, in_bytes, C.byref(img_view))
+    arr = abi.samsung_v0_offsets(offsets)
+    n = len(offsets) if n_offsets is None else n_offsets
+    return lib().rsx_samsung_v0_validate(arr, n, in_bytes, C.byref(img_view))
 
 
 def _u8(a):
@@ -333,6 +347,15 @@ class Context:
         return lib().rsx_panasonic_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
                                               C.byref(img_view))
 
+    def samsung_v0_decompress(self, data, offsets, img_view, rows=True):
+        """data: the strip; offsets: one per image row.  Returns (status, per-row statuses)."""
+        a = _u8(data)
+        arr = abi.samsung_v0_offsets(offsets)
+        rs = (C.c_int32 * max(1, img_view.dim_y))() if rows else None
+        st = lib().rsx_samsung_v0_decompress(self._h, a.ctypes.data, a.size, arr, len(offsets),
+                                             C.byref(img_view), rs)
+        return st, (list(rs)[:img_view.dim_y] if rows else None)
+
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
@@ -399,6 +422,10 @@ class Context:
     def panasonic_plan(self, jobs):
         """jobs: abi.PanasonicJob (versions, depths and geometries may mix)"""
         return Plan(self, "rsx_panasonic_plan_create", abi.PanasonicJob, jobs)
+
+    def samsung_v0_plan(self, jobs):
+        """jobs: abi.SamsungV0Job (their offset arrays are copied at plan creation)"""
+        return Plan(self, "rsx_samsung_v0_plan_create", abi.SamsungV0Job, jobs)
 
     def pentax_plan(self, jobs):
         return Plan(self, "rsx_pentax_plan_create", abi.PentaxJob, jobs)

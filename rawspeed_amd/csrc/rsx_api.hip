@@ -9,6 +9,7 @@
 #include "rsx_ljpeg_dev.h"
 #include "rsx_panasonic.h"
 #include "rsx_phase_one.h"
+#include "rsx_samsung_v0.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 
@@ -2384,7 +2385,7 @@ int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_byte
   return rc;
 }
 
-// One image through a host-pointer call of Phase One, ARW2 or Panasonic: `span` bytes from `src` up as one
+// One image through a host-pointer call of Phase One, ARW2, Panasonic or SamsungV0: `span` bytes from `src` up as one
 // copy, the lane's plan for `key` run on them (on_reuse(plan, stream): this call's data onto a
 // plan the lane held), the row statuses out, and the image back as one rectangle through
 // download_rects -- only when every row decoded (the reference throws otherwise, and the
@@ -2727,6 +2728,51 @@ extern "C" int rsx_panasonic_decompress(rsx_ctx* ctx, const rsx_panasonic_desc* 
   key_append(key, &job);
   return single_image_host(ctx, key, rsx_panasonic_plan_create, job, in, size_t(span), img, nullptr,
                            [](rsx_plan*, hipStream_t) { return RSX_OK; });
+}
+
+// ---------------------------------------------------------------------------
+// SamsungV0Decompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_samsung_v0_validate(const uint32_t* row_offsets, int n_offsets, size_t in_bytes,
+                                       const rsx_image* img) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return samsung_v0_validate(row_offsets, n_offsets, in_bytes, *img);
+}
+
+extern "C" int rsx_samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_job* jobs,
+                                          rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, samsung_v0_plan_create);
+}
+
+// The host-pointer call (single_image_host): the bytes from the first row's offset up go up as
+// one copy; the plan's key holds the row offsets.
+extern "C" int rsx_samsung_v0_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                         const uint32_t* row_offsets, int n_offsets,
+                                         const rsx_image* img, int32_t* row_status) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = samsung_v0_validate(row_offsets, n_offsets, in_bytes, *img))
+    return st;
+  const uint32_t lo = row_offsets[0];
+  std::vector<uint32_t> local(row_offsets, row_offsets + img->dim_y);
+  for (uint32_t& o : local)
+    o -= lo;
+  const size_t span = in_bytes - lo;
+  rsx_samsung_v0_job job;
+  std::memset(&job, 0, sizeof job);
+  job.n_offsets = img->dim_y;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  key_create(key, rsx_samsung_v0_plan_create);
+  key_append(key, &job);
+  key_append(key, local.data(), local.size());
+  job.row_offsets = local.data();
+  return single_image_host(ctx, key, rsx_samsung_v0_plan_create, job, in + lo, span, img,
+                           row_status, [](rsx_plan*, hipStream_t) { return RSX_OK; });
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

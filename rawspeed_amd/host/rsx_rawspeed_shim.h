@@ -89,6 +89,25 @@ inline int panasonic(int version, uint32_t bps, const ByteStream& input, const R
   return rsx_panasonic_decompress(rsx, &d, in.begin(), in.getSize(), &v);
 }
 
+// SamsungV0Decompressor::decompress(): `stripes` are the rows computeStripes cut
+// out of the strip, one behind the other; the call takes the strip from the first row up and the
+// rows' offsets in it
+inline int samsung_v0(const std::vector<ByteStream>& stripes, const RawImage& img) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  if (stripes.empty())
+    return RSX_ERR_INVALID_ARG;
+  const uint8_t* lo = stripes.front().peekRemainingBuffer().begin();
+  const uint8_t* hi = stripes.back().peekRemainingBuffer().end();
+  std::vector<uint32_t> offsets(stripes.size());
+  for (size_t i = 0; i < stripes.size(); ++i)
+    offsets[i] = implicit_cast<uint32_t>(stripes[i].peekRemainingBuffer().begin() - lo);
+  const rsx_image v = view(img);
+  return rsx_samsung_v0_decompress(rsx, lo, static_cast<size_t>(hi - lo), offsets.data(),
+                                   implicit_cast<int>(offsets.size()), &v, nullptr);
+}
+
 // status -> the exception the reference would have thrown
 [[noreturn]] inline void raise(int st) {
   switch (st) {
