@@ -651,6 +651,58 @@ int rsx_samsung_v0_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
                               const rsx_image* img, int32_t* row_status);
 
 /* ------------------------------------------------------------------------ */
+/* 3l. PanasonicV4Decompressor                                               */
+/*    replaces PanasonicV4Decompressor::decompress()                         */
+/*    (decompressors/PanasonicV4Decompressor.cpp:268-275 -> processBlock     */
+/*    :220-241 -> processPixelPacket :173-218).  Rw2Decoder keeps its host   */
+/*    work; it builds the decompressor for PANASONIC_RAWFORMAT 4 with        */
+/*    section_split_offset 0x1FF8 (decoders/Rw2Decoder.cpp:140-146) and for  */
+/*    old-style files without PANASONIC_STRIPOFFSET with 0 (:79-120).        */
+/*    The input is cut into blocks of 0x4000 bytes = 1024 packets of 16      */
+/*    bytes (split 0: the last block may be partial); a block's bytes        */
+/*    [split, 0x4000) are read first, then [0, split): packet q of a block   */
+/*    starts at its byte (16 q + split) mod 0x4000, and with 0x1FF8 packet   */
+/*    512 wraps around the block's end.  A packet is one 128-bit little-     */
+/*    endian number read from bit 128 down and holds 14 pixels of one row    */
+/*    (dim_x % 14 == 0).  Per pixel p, column parity c = p & 1: in front of  */
+/*    the pixels 2, 5, 8, 11 a 2-bit scale b, sh = 4 >> (3 - b); then 8 bits */
+/*    f.  While the parity has met no non-zero f: nonz = f, and for f != 0   */
+/*    or p > 11 four more bits g follow, pred = f << 4 | g.  Afterwards, for */
+/*    f != 0: pred -= 0x80 << sh; if pred < 0 or sh == 4, pred &= (1 << sh)  */
+/*    - 1; pred += f << sh.  The pixel is uint16(pred).  Every parity reads  */
+/*    exactly one g, so a packet always takes its 128 bits, and pred stays   */
+/*    in 0 .. 16287.  Nothing in the data can fail (decompress() is          */
+/*    noexcept), so there is no per-row status.                              */
+/*    rsx_panasonic_v4_validate = the constructor's checks (:49-86) in their */
+/*    order: desc NULL, cpp != 1, dim <= 0 or dim_x % 14 != 0 (or            */
+/*    pitch_bytes < 2 dim_x), section_split_offset > 0x4000, bufSize >       */
+/*    UINT32_MAX -> RSX_ERR_INVALID_ARG, where bufSize = 16 dim_x dim_y / 14 */
+/*    for split 0 and that rounded up to whole blocks otherwise; in_bytes <  */
+/*    bufSize (peekStream) -> RSX_ERR_IO; then a split other than 0 and      */
+/*    0x1FF8 -> RSX_ERR_UNSUPPORTED (no caller passes one).  A job consumes  */
+/*    bufSize; bytes behind it are not read.                                 */
+/*    The bad-pixel list: with zero_is_bad the reference appends row << 16 | */
+/*    col of every pixel with pred == 0 -- exactly the zero pixels of the    */
+/*    image -- to mRaw->mBadPixelPositions, per thread in completion order.  */
+/*    Here the entries come back in ascending order (the reference's order   */
+/*    on one thread).  *n_bad (may be NULL) is always the exact count; 0     */
+/*    with zero_is_bad == 0, when nothing is collected.  When n_bad exceeds  */
+/*    the capacity the image is still complete and correct, the call (the    */
+/*    job) reports RSX_ERR_UNSUPPORTED and the list's contents are           */
+/*    unspecified.  `bad` NULL with bad_cap 0 is allowed.                    */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_panasonic_v4_desc {
+  uint32_t section_split_offset; /* 0 (old-style files) or 0x1FF8 (PANASONIC_RAWFORMAT 4) */
+  int32_t zero_is_bad;           /* !hints.contains("zero_is_not_bad") */
+} rsx_panasonic_v4_desc;
+
+int rsx_panasonic_v4_validate(const rsx_panasonic_v4_desc* desc, const rsx_image* img,
+                              size_t in_bytes);
+int rsx_panasonic_v4_decompress(rsx_ctx* ctx, const rsx_panasonic_v4_desc* desc, const uint8_t* in,
+                                size_t in_bytes, const rsx_image* img, uint32_t* bad,
+                                uint32_t bad_cap, uint64_t* n_bad);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -833,6 +885,19 @@ typedef struct rsx_samsung_v0_job {
   rsx_image img; /* .data ignored */
 } rsx_samsung_v0_job;
 
+/* jobs of both splits, both flags and different geometries may share a plan; any in_offset, any
+ * even pitch_bytes >= 2 dim_x and any even img_offset.  The plan owns a list of min(bad_cap,
+ * dim_x dim_y) entries per job with zero_is_bad. */
+typedef struct rsx_panasonic_v4_job {
+  rsx_panasonic_v4_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+  uint32_t bad_cap;
+  uint32_t reserved;
+} rsx_panasonic_v4_job;
+
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */
@@ -869,6 +934,8 @@ int rsx_panasonic_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_job*
                               rsx_plan** out_plan);
 int rsx_samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_job* jobs,
                                rsx_plan** out_plan);
+int rsx_panasonic_v4_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_v4_job* jobs,
+                                 rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
                  void* stream);
@@ -876,6 +943,12 @@ int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
  * `job_consumed` may be NULL.  Returns RSX_OK iff every job is RSX_OK. */
 int rsx_plan_results(rsx_plan* plan, int32_t* job_status,
                      uint32_t* job_consumed);
+/* Panasonic V4 plans, after rsx_plan_results: the zero pixels of job `job` of the last run,
+ * ascending, into `out` (`cap` entries; NULL with cap 0 is allowed), *n_bad (may be NULL) = the
+ * exact count.  RSX_ERR_UNSUPPORTED when the count exceeds `cap` or the job's bad_cap (`out` is
+ * not written), RSX_ERR_INVALID_ARG for another plan, a refused job or before results. */
+int rsx_panasonic_v4_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
+                                     uint64_t* n_bad);
 /* Name of the dominant kernel of this plan and the average duration (ms) of
  * its launches since the previous call, measured with hipEvents recorded on
  * the stream the kernel is launched on.  Timing is off by default; enable

@@ -247,6 +247,22 @@ def panasonic_consumed(version, bps, dim_x, dim_y):
     return -(-packets // 1024) * 0x4000 if version == 5 else 16 * packets
 
 
+class PanasonicV4Desc(C.Structure):
+    _fields_ = [("section_split_offset", C.c_uint32), ("zero_is_bad", C.c_int32)]
+
+
+class PanasonicV4Job(C.Structure):
+    _fields_ = [("desc", PanasonicV4Desc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image), ("bad_cap", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+def panasonic_v4_consumed(split, dim_x, dim_y):
+    """input bytes PanasonicV4Decompressor's peekStream takes (include/rsx.h section 3l)"""
+    total = dim_x * dim_y // 14 * 16
+    return total if split == 0 else -(-total // 0x4000) * 0x4000
+
+
 class SamsungV0Job(C.Structure):
     _fields_ = [("row_offsets", C.POINTER(C.c_uint32)), ("n_offsets", C.c_int32),
                 ("reserved", C.c_int32), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),

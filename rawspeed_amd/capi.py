@@ -34,6 +34,8 @@ EXPORTS = [
     "rsx_sony_arw2_validate", "rsx_sony_arw2_decompress", "rsx_sony_arw2_plan_create",
     "rsx_panasonic_validate", "rsx_panasonic_decompress", "rsx_panasonic_plan_create",
     "rsx_samsung_v0_validate", "rsx_samsung_v0_decompress", "rsx_samsung_v0_plan_create",
+    "rsx_panasonic_v4_validate", "rsx_panasonic_v4_decompress", "rsx_panasonic_v4_plan_create",
+    "rsx_panasonic_v4_plan_bad_pixels",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
@@ -104,6 +106,11 @@ def lib():
         L.rsx_panasonic_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsx_panasonic_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.c_void_p]
+        L.rsx_panasonic_v4_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_panasonic_v4_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rsx_panasonic_v4_plan_bad_pixels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
+                                                       C.c_void_p]
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p]
@@ -128,7 +135,7 @@ def lib():
                      "rsx_sraw_plan_create", "rsx_hasselblad_plan_create",
                      "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
                      "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
-                     "rsx_samsung_v0_plan_create"):
+                     "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -171,6 +178,13 @@ def panasonic_validate(version, bps, img_view, in_bytes):
         return lib().rsx_panasonic_validate(None, C.byref(img_view), in_bytes)
     d = abi.PanasonicDesc(version, bps)
     return lib().rsx_panasonic_validate(C.byref(d), C.byref(img_view), in_bytes)
+
+
+def panasonic_v4_validate(split, zero_is_bad, img_view, in_bytes):
+    """rsx_panasonic_v4_validate; split None passes a NULL desc, img_view None a NULL image"""
+    d = None if split is None else C.byref(abi.PanasonicV4Desc(split, int(zero_is_bad)))
+    v = None if img_view is None else C.byref(img_view)
+    return lib().rsx_panasonic_v4_validate(d, v, in_bytes)
 
 
 def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
@@ -347,6 +361,18 @@ class Context:
         return lib().rsx_panasonic_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
                                               C.byref(img_view))
 
+    def panasonic_v4_decompress(self, split, zero_is_bad, data, img_view, bad_cap=0):
+        """Returns (status, the exact count of zero pixels, the sorted list -- None unless the
+        status is RSX_OK)."""
+        a = _u8(data)
+        d = abi.PanasonicV4Desc(split, int(zero_is_bad))
+        bad = np.zeros(max(1, bad_cap), np.uint32)
+        n = C.c_uint64(0)
+        st = lib().rsx_panasonic_v4_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
+                                               C.byref(img_view), bad.ctypes.data if bad_cap else None,
+                                               bad_cap, C.byref(n))
+        return st, n.value, (bad[:n.value].copy() if st == abi.RSX_OK else None)
+
     def samsung_v0_decompress(self, data, offsets, img_view, rows=True):
         """data: the strip; offsets: one per image row.  Returns (status, per-row statuses)."""
         a = _u8(data)
@@ -423,6 +449,10 @@ class Context:
         """jobs: abi.PanasonicJob (versions, depths and geometries may mix)"""
         return Plan(self, "rsx_panasonic_plan_create", abi.PanasonicJob, jobs)
 
+    def panasonic_v4_plan(self, jobs):
+        """jobs: abi.PanasonicV4Job (splits, flags and geometries may mix)"""
+        return PanasonicV4Plan(self, "rsx_panasonic_v4_plan_create", abi.PanasonicV4Job, jobs)
+
     def samsung_v0_plan(self, jobs):
         """jobs: abi.SamsungV0Job (their offset arrays are copied at plan creation)"""
         return Plan(self, "rsx_samsung_v0_plan_create", abi.SamsungV0Job, jobs)
@@ -494,3 +524,13 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class PanasonicV4Plan(Plan):
+    def bad_pixels(self, job, cap):
+        """after results(): (status, the exact count, the job's sorted list -- None unless RSX_OK)"""
+        bad = np.zeros(max(1, cap), np.uint32)
+        n = C.c_uint64(0)
+        st = lib().rsx_panasonic_v4_plan_bad_pixels(self._h, job, bad.ctypes.data if cap else None,
+                                                    cap, C.byref(n))
+        return st, n.value, (bad[:n.value].copy() if st == abi.RSX_OK else None)

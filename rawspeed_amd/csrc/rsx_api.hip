@@ -8,6 +8,7 @@
 #include "rsx_ljpeg.h"
 #include "rsx_ljpeg_dev.h"
 #include "rsx_panasonic.h"
+#include "rsx_panasonic_v4.h"
 #include "rsx_phase_one.h"
 #include "rsx_samsung_v0.h"
 #include "rsx_samsung_v2.h"
@@ -2385,15 +2386,18 @@ int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_byte
   return rc;
 }
 
-// One image through a host-pointer call of Phase One, ARW2, Panasonic or SamsungV0: `span` bytes from `src` up as one
+// One image through a host-pointer call of Phase One, ARW2, Panasonic, Panasonic V4 or SamsungV0: `span` bytes from `src` up as one
 // copy, the lane's plan for `key` run on them (on_reuse(plan, stream): this call's data onto a
 // plan the lane held), the row statuses out, and the image back as one rectangle through
 // download_rects -- only when every row decoded (the reference throws otherwise, and the
 // caller's image stays as it was).
-template <typename JobT, typename ReuseFn>
+// on_done(plan, rc): what the call takes from the plan besides the image, behind the results; the
+// status it returns decides about the download (Panasonic V4: the list, and an image that is
+// complete although the list did not fit).
+template <typename JobT, typename ReuseFn, typename DoneFn>
 int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
                       const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
-                      int32_t* row_status, ReuseFn on_reuse) {
+                      int32_t* row_status, ReuseFn on_reuse, DoneFn on_done) {
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   LaneGuard lane(ctx, &key);
   if (!lane.lane)
@@ -2424,6 +2428,7 @@ int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT
       if (int e = plan->dec->row_status(s, 0, row_status))
         rc = e;
   }
+  rc = on_done(plan, rc);
   if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
     evict_plan(lane.lane);
     return rc;
@@ -2435,6 +2440,14 @@ int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT
               size_t(img->dim_x) * 2, size_t(img->dim_y)};
   std::lock_guard<std::mutex> down_lock(ctx->download_mu);
   return download_rects(ctx, lane.lane, s, &dr, 1);
+}
+
+template <typename JobT, typename ReuseFn>
+int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
+                      const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
+                      int32_t* row_status, ReuseFn on_reuse) {
+  return single_image_host(ctx, key, create, job, src, span, img, row_status, on_reuse,
+                           [](rsx_plan*, int rc) { return rc; });
 }
 
 } // namespace
@@ -2728,6 +2741,70 @@ extern "C" int rsx_panasonic_decompress(rsx_ctx* ctx, const rsx_panasonic_desc* 
   key_append(key, &job);
   return single_image_host(ctx, key, rsx_panasonic_plan_create, job, in, size_t(span), img, nullptr,
                            [](rsx_plan*, hipStream_t) { return RSX_OK; });
+}
+
+// ---------------------------------------------------------------------------
+// PanasonicV4Decompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_panasonic_v4_validate(const rsx_panasonic_v4_desc* desc, const rsx_image* img,
+                                         size_t in_bytes) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return panasonic_v4_validate(desc, *img, in_bytes);
+}
+
+extern "C" int rsx_panasonic_v4_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_v4_job* jobs,
+                                            rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, panasonic_v4_plan_create);
+}
+
+extern "C" int rsx_panasonic_v4_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
+                                                uint64_t* n_bad) {
+  if (n_bad)
+    *n_bad = 0;
+  if (!plan || plan->kind != PLAN_DECODER)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
+  return plan->dec->bad_pixels(job, out, cap, n_bad);
+}
+
+// The host-pointer call (single_image_host): the bytes the constructor's peekStream takes go up
+// as one copy.  The plan is keyed by the split, the flag, the capacity and the geometry.  Behind
+// the results the list and its count go to the caller; an image whose list did not fit is
+// complete, and comes down like any other before the call reports RSX_ERR_UNSUPPORTED.
+extern "C" int rsx_panasonic_v4_decompress(rsx_ctx* ctx, const rsx_panasonic_v4_desc* desc,
+                                           const uint8_t* in, size_t in_bytes, const rsx_image* img,
+                                           uint32_t* bad, uint32_t bad_cap, uint64_t* n_bad) {
+  if (n_bad)
+    *n_bad = 0;
+  if (!ctx || !in || !img || !img->data || (!bad && bad_cap != 0))
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  uint64_t span = 0;
+  if (int st = panasonic_v4_validate(desc, *img, in_bytes, &span))
+    return st;
+  rsx_panasonic_v4_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc.section_split_offset = desc->section_split_offset;
+  job.desc.zero_is_bad = desc->zero_is_bad != 0;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  job.bad_cap = uint32_t(std::min<uint64_t>(bad_cap, uint64_t(img->dim_x) * uint64_t(img->dim_y)));
+  std::vector<uint8_t> key;
+  key_create(key, rsx_panasonic_v4_plan_create);
+  key_append(key, &job);
+  int list_rc = RSX_OK;
+  const int rc = single_image_host(
+      ctx, key, rsx_panasonic_v4_plan_create, job, in, size_t(span), img, nullptr,
+      [](rsx_plan*, hipStream_t) { return RSX_OK; },
+      [&](rsx_plan* plan, int st) {
+        if (st != RSX_OK && st != RSX_ERR_UNSUPPORTED)
+          return st;
+        list_rc = plan->dec->bad_pixels(0, bad, job.bad_cap, n_bad);
+        return list_rc == RSX_OK || list_rc == RSX_ERR_UNSUPPORTED ? int(RSX_OK) : list_rc;
+      });
+  return rc != RSX_OK ? rc : list_rc;
 }
 
 // ---------------------------------------------------------------------------

@@ -184,6 +184,10 @@ struct DecoderPlan {
   virtual int row_status(hipStream_t, int /*job*/, int32_t* /*row_status*/) {
     return RSX_ERR_INVALID_ARG;
   }
+  // the zero pixels of job `job` of the last run, ascending, after results (Panasonic V4)
+  virtual int bad_pixels(int /*job*/, uint32_t* /*out*/, uint32_t /*cap*/, uint64_t* /*n_bad*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };

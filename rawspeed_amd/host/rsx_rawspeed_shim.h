@@ -18,6 +18,7 @@
 #include "rsx_pin.h"
 
 #include "adt/Array1DRef.h"
+#include "adt/Mutex.h"
 #include "adt/Point.h"
 #include "codes/PrefixCodeDecoder.h"
 #include "common/RawImage.h"
@@ -28,6 +29,7 @@
 #include "io/IOException.h"
 
 #include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -87,6 +89,33 @@ inline int panasonic(int version, uint32_t bps, const ByteStream& input, const R
   const rsx_image v = view(img);
   const Buffer in = input.peekRemainingBuffer();
   return rsx_panasonic_decompress(rsx, &d, in.begin(), in.getSize(), &v);
+}
+
+// PanasonicV4Decompressor::decompress(): `input` is the stream the constructor
+// kept (exactly the bytes peekStream took).  The zero pixels come back in ascending order and are
+// appended to mRaw->mBadPixelPositions under its mutex, as decompressThread does; a list longer
+// than the room made for it (RSX_ERR_UNSUPPORTED) leaves the frame to the original code, like any
+// status but RSX_OK.
+inline int panasonic_v4(const ByteStream& input, const RawImage& img, bool zero_is_bad,
+                        uint32_t section_split_offset) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  constexpr uint32_t MaxBadPixels = 1U << 16; // (real files hold a handful)
+  const rsx_panasonic_v4_desc d{section_split_offset, zero_is_bad ? 1 : 0};
+  const rsx_image v = view(img);
+  const Buffer in = input.peekRemainingBuffer();
+  std::vector<uint32_t> bad(zero_is_bad ? MaxBadPixels : 0);
+  uint64_t n = 0;
+  const int st = rsx_panasonic_v4_decompress(rsx, &d, in.begin(), in.getSize(), &v,
+                                             bad.empty() ? nullptr : bad.data(),
+                                             implicit_cast<uint32_t>(bad.size()), &n);
+  if (st == RSX_OK && n != 0) {
+    MutexLocker guard(&img->mBadPixelMutex);
+    img->mBadPixelPositions.insert(img->mBadPixelPositions.end(), bad.begin(),
+                                   bad.begin() + implicit_cast<std::ptrdiff_t>(n));
+  }
+  return st;
 }
 
 // SamsungV0Decompressor::decompress(): `stripes` are the rows computeStripes cut
