@@ -950,8 +950,11 @@ int rsx_plan_results(rsx_plan* plan, int32_t* job_status,
 int rsx_panasonic_v4_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
                                      uint64_t* n_bad);
 /* Name of the dominant kernel of this plan and the average duration (ms) of
- * its launches since the previous call, measured with hipEvents recorded on
- * the stream the kernel is launched on.  Timing is off by default; enable
+ * its launches since the previous call.  Unpack and sRaw plans: the kernel
+ * stamps the device's wall clock on entry and exit (first entry to last exit of
+ * a launch; up to 64 launches between two calls, further ones go untimed) and a
+ * timed launch queues nothing besides the kernel.  The other plans: hipEvents
+ * recorded on the launch stream.  Timing is off by default; enable
  * with rsx_plan_set_timing(plan, 1).  Returns RSX_OK, or RSX_ERR_INVALID_ARG
  * if timing is disabled / no launches happened. */
 int rsx_plan_set_timing(rsx_plan* plan, int enable);

@@ -22,7 +22,7 @@ CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_dir
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
                 "rsx_panasonic_v4.hip", "rsx_host.cpp"]
-CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
+CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
                 "rsx_panasonic_dev.h", "rsx_panasonic_v4.h"]

@@ -40,9 +40,8 @@ struct UnpackLaunch {
   uintptr_t last_out_base = ~uintptr_t(0);
 };
 
-struct EventPair {
-  hipEvent_t start = nullptr, stop = nullptr;
-};
+// in-run kernel time: launches a plan can time between two read-outs (rsx_stamp.h)
+constexpr size_t TIMED_LAUNCHES = 64;
 
 } // namespace
 
@@ -60,10 +59,14 @@ struct rsx_plan {
   bool sraw_versions[3] = {false, false, false};
   hipStream_t last_stream = nullptr;
   bool ran = false;
-  // dominant-kernel timing
+  // dominant-kernel timing: TIMED_LAUNCHES x STAMP_WORDS clock words the kernels fold their
+  // entry and exit times into; `stamps_dirty` launches' worth has been handed out since the
+  // buffer was last seeded, on `timed_streams`
   bool timing = false;
-  std::vector<EventPair> events;
-  size_t events_used = 0;
+  DeviceBuffer d_stamps;
+  size_t stamps_used = 0, stamps_dirty = 0;
+  std::vector<hipStream_t> timed_streams;
+  int wall_clock_khz = 0;
   // decoder plans: an event after every kernel of a timed run; the totals per kernel
   // name are folded in before the events are reused
   std::unique_ptr<KernelTimer> ktimer;
@@ -82,12 +85,36 @@ int upload(rsx_ctx* ctx, DeviceBuffer& buf, const void* src, size_t bytes) {
   return RSX_OK;
 }
 
-// The pool is created by rsx_plan_set_timing(); once it is exhausted further
-// launches simply go untimed (event creation is far too slow for a hot path).
-EventPair* next_events(rsx_plan* p) {
-  if (p->events_used == p->events.size())
+// The buffer is made by rsx_plan_set_timing(); once its TIMED_LAUNCHES sets of slots are
+// handed out, further launches simply go untimed.
+unsigned long long* next_stamps(rsx_plan* p, hipStream_t s) {
+  if (!p->d_stamps.ptr || p->stamps_used == TIMED_LAUNCHES)
     return nullptr;
-  return &p->events[p->events_used++];
+  if (std::find(p->timed_streams.begin(), p->timed_streams.end(), s) == p->timed_streams.end())
+    p->timed_streams.push_back(s);
+  unsigned long long* w =
+      static_cast<unsigned long long*>(p->d_stamps.ptr) + p->stamps_used++ * STAMP_WORDS;
+  p->stamps_dirty = std::max(p->stamps_dirty, p->stamps_used);
+  return w;
+}
+
+// (first entry, last exit) = (~0, 0) in every slot handed out since the last seeding.  Waits
+// for the timed launches first: never called between the steps of a timed loop.
+int seed_stamps(rsx_plan* p, size_t launches) {
+  rsx_ctx* ctx = p->ctx;
+  for (hipStream_t s : p->timed_streams)
+    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  p->timed_streams.clear();
+  if (launches) {
+    std::vector<unsigned long long> seed(launches * STAMP_WORDS, 0ull);
+    for (size_t i = 0; i < seed.size(); i += 2)
+      seed[i] = ~0ull;
+    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_stamps.ptr, seed.data(),
+                                 seed.size() * sizeof(unsigned long long),
+                                 hipMemcpyHostToDevice));
+  }
+  p->stamps_dirty = 0;
+  return RSX_OK;
 }
 
 // add the durations of the last timed LJPEG run to the per-kernel totals
@@ -869,15 +896,13 @@ int run_unpack(rsx_plan* p, const void* in_dev, void* out_dev, hipStream_t s) {
                                           hipMemcpyHostToDevice, s));
       L.last_out_base = base;
     }
-    EventPair* ev = p->timing ? next_events(p) : nullptr;
-    if (ev)
-      RSX_HIP_CHECK(ctx, hipEventRecord(ev->start, s));
+    // timed: the kernel stamps its own begin and end (rsx_stamp.h); the launch is the same
+    // single packet either way
+    unsigned long long* stamps = p->timing && L.total_blocks ? next_stamps(p, s) : nullptr;
     RSX_HIP_CHECK(ctx, launch_unpack_mode(L.mode, L.order,
                                           static_cast<const UnpackJobDev*>(L.d_jobs.ptr),
                                           static_cast<const uint32_t*>(L.d_block_start.ptr),
-                                          L.n_jobs, L.total_blocks, in_dev, out_dev, s));
-    if (ev)
-      RSX_HIP_CHECK(ctx, hipEventRecord(ev->stop, s));
+                                          L.n_jobs, L.total_blocks, in_dev, out_dev, s, stamps));
   }
   return RSX_OK;
 }
@@ -906,19 +931,15 @@ extern "C" int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
   plan->ran = true;
   if (plan->kind == PLAN_UNPACK)
     return run_unpack(plan, in_dev, out_dev, s);
-  EventPair* ev = plan->timing ? next_events(plan) : nullptr;
   if (plan->kind == PLAN_SRAW) {
-    if (ev)
-      RSX_HIP_CHECK(ctx, hipEventRecord(ev->start, s));
+    unsigned long long* stamps =
+        plan->timing && plan->sraw_blocks ? next_stamps(plan, s) : nullptr;
     RSX_HIP_CHECK(ctx, launch_sraw(static_cast<const SrawJobDev*>(plan->d_sraw_jobs.ptr),
                                    static_cast<const uint32_t*>(plan->d_sraw_starts.ptr),
                                    plan->n_sraw, plan->sraw_blocks, plan->sraw_versions,
-                                   in_dev, out_dev, s));
-    if (ev)
-      RSX_HIP_CHECK(ctx, hipEventRecord(ev->stop, s));
+                                   in_dev, out_dev, s, stamps));
     return RSX_OK;
   }
-  (void)ev;
   if (!plan->timing)
     return plan->dec->run(in_dev, out_dev, s, nullptr);
   if (int st = fold_kernel_timer(plan)) // (waits for the previous timed run)
@@ -957,25 +978,27 @@ extern "C" int rsx_plan_set_timing(rsx_plan* plan, int enable) {
   if (!plan)
     return RSX_ERR_INVALID_ARG;
   plan->timing = enable != 0;
-  plan->events_used = 0;
+  plan->stamps_used = 0;
   plan->ktotals.clear();
   plan->kruns = 0;
   plan->ktimer_pending = false;
   if (plan->kind == PLAN_DECODER)
     return RSX_OK; // its events are created on the first timed run
-  if (plan->timing && plan->events.size() < 64) {
-    // event creation is slow on ROCm: pre-create the pool outside timed regions
-    std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
-    (void)hipSetDevice(plan->ctx->device);
-    while (plan->events.size() < 64) {
-      EventPair e;
-      if (hipEventCreate(&e.start) != hipSuccess ||
-          hipEventCreate(&e.stop) != hipSuccess)
-        return RSX_ERR_DEVICE;
-      plan->events.push_back(e);
-    }
+  rsx_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (plan->timing && !plan->d_stamps.ptr) {
+    // the slots are made and seeded here, outside timed regions
+    if (int st = plan->d_stamps.ensure(TIMED_LAUNCHES * STAMP_WORDS * sizeof(unsigned long long)))
+      return st;
+    RSX_HIP_CHECK(ctx, hipDeviceGetAttribute(&plan->wall_clock_khz,
+                                             hipDeviceAttributeWallClockRate, ctx->device));
+    if (plan->wall_clock_khz <= 0)
+      return RSX_ERR_DEVICE;
+    return seed_stamps(plan, TIMED_LAUNCHES);
   }
-  return RSX_OK;
+  // what was timed and not read out is dropped
+  return plan->stamps_dirty ? seed_stamps(plan, plan->stamps_dirty) : RSX_OK;
 }
 
 extern "C" int rsx_plan_kernel_table(rsx_plan* plan, int cap, const char** names,
@@ -1033,15 +1056,24 @@ extern "C" int rsx_plan_kernel_time(rsx_plan* plan, const char** kernel_name,
     plan->kruns = 0;
     return RSX_OK;
   }
-  if (plan->events_used == 0)
+  if (plan->stamps_used == 0)
     return RSX_ERR_INVALID_ARG;
+  // per launch: last exit - first entry over its slots, in ticks of the device's wall clock
+  const size_t n = plan->stamps_used;
+  for (hipStream_t s : plan->timed_streams)
+    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  std::vector<unsigned long long> w(n * STAMP_WORDS);
+  RSX_HIP_CHECK(ctx, hipMemcpy(w.data(), plan->d_stamps.ptr,
+                               w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   double total = 0;
-  for (size_t i = 0; i < plan->events_used; ++i) {
-    RSX_HIP_CHECK(ctx, hipEventSynchronize(plan->events[i].stop));
-    float ms = 0;
-    RSX_HIP_CHECK(ctx, hipEventElapsedTime(&ms, plan->events[i].start,
-                                           plan->events[i].stop));
-    total += ms;
+  for (size_t i = 0; i < n; ++i) {
+    unsigned long long begin = ~0ull, end = 0;
+    for (size_t k = 0; k < STAMP_WORDS; k += 2) {
+      begin = std::min(begin, w[i * STAMP_WORDS + k]);
+      end = std::max(end, w[i * STAMP_WORDS + k + 1]);
+    }
+    if (end > begin)
+      total += double(end - begin) / double(plan->wall_clock_khz);
   }
   if (kernel_name)
     *kernel_name = plan->kind == PLAN_SRAW ? "sraw_kernel"
@@ -1050,11 +1082,11 @@ extern "C" int rsx_plan_kernel_time(rsx_plan* plan, const char** kernel_name,
                        ? "unpack_control_kernel"
                        : unpack_kernel_name();
   if (avg_ms)
-    *avg_ms = total / double(plan->events_used);
+    *avg_ms = total / double(n);
   if (n_launches)
-    *n_launches = int(plan->events_used);
-  plan->events_used = 0;
-  return RSX_OK;
+    *n_launches = int(n);
+  plan->stamps_used = 0;
+  return seed_stamps(plan, plan->stamps_dirty);
 }
 
 extern "C" void rsx_plan_destroy(rsx_plan* plan) {
@@ -1072,10 +1104,9 @@ extern "C" void rsx_plan_destroy(rsx_plan* plan) {
     }
     plan->d_sraw_jobs.release();
     plan->d_sraw_starts.release();
-    for (auto& e : plan->events) {
-      (void)hipEventDestroy(e.start);
-      (void)hipEventDestroy(e.stop);
-    }
+    for (hipStream_t s : plan->timed_streams)
+      (void)hipStreamSynchronize(s);
+    plan->d_stamps.release();
     if (plan->ktimer)
       for (int i = 0; i < plan->ktimer->created; ++i)
         (void)hipEventDestroy(plan->ktimer->ev[i]);

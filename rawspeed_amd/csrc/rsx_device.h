@@ -41,6 +41,11 @@ enum UnpackMode {
   UNPACK_MODE_LUT8 = 4 // decode8BitRaw<false>: 8-bit walk + 256-entry table
 };
 
+// In-run kernel time (rsx_stamp.h): a timed launch owns STAMP_SLOTS pairs of
+// (first entry, last exit) wall-clock words, seeded (~0, 0); `stamps` = null: untimed.
+constexpr int STAMP_SLOTS = 1024;
+constexpr size_t STAMP_WORDS = 2 * size_t(STAMP_SLOTS);
+
 size_t unpack_lds_bytes();
 // fill groups_per_row / segs_per_row / seg_groups from n_rows and cols;
 // return the number of workgroups of the job
@@ -51,11 +56,13 @@ uint32_t unpack_fp_blocks_for(UnpackJobDev* u);
 hipError_t launch_unpack_mode(int mode, int order, const UnpackJobDev* d_jobs,
                               const uint32_t* d_block_start, int n_jobs,
                               uint32_t total_blocks, const void* in_base,
-                              void* out_base, hipStream_t stream);
+                              void* out_base, hipStream_t stream,
+                              unsigned long long* stamps = nullptr);
 hipError_t launch_unpack(int order, const UnpackJobDev* d_jobs,
                          const uint32_t* d_block_start, int n_jobs,
                          uint32_t total_blocks, const void* in_base,
-                         void* out_base, hipStream_t stream);
+                         void* out_base, hipStream_t stream,
+                         unsigned long long* stamps = nullptr);
 
 // One Cr2sRawInterpolator job, flattened for the kernel (rsx_sraw.hip).
 struct SrawJobDev {
@@ -78,6 +85,7 @@ hipError_t launch_stream_probe(const void* in, uint64_t in_bytes, void* out,
 uint32_t sraw_blocks_for(SrawJobDev* j);
 hipError_t launch_sraw(const SrawJobDev* d_jobs, const uint32_t* d_block_start, int n_jobs,
                        uint32_t total_blocks, const bool versions[3], const void* in_base,
-                       void* out_base, hipStream_t stream);
+                       void* out_base, hipStream_t stream,
+                       unsigned long long* stamps = nullptr);
 
 } // namespace rsx

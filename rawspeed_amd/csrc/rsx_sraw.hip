@@ -11,6 +11,7 @@
 // (+ one neighbour dword), 48 output bytes per output row as 16-byte stores; pure
 // streaming.
 #include "rsx_device.h"
+#include "rsx_stamp.h"
 
 namespace rsx {
 
@@ -130,7 +131,9 @@ __device__ __forceinline__ void pack2(uint32_t* o, Rgb p, Rgb q) {
 template <int VERSION>
 __global__ __launch_bounds__(SRAW_THREADS) void sraw_kernel(
     const SrawJobDev* __restrict__ jobs, const uint32_t* __restrict__ job_block_start,
-    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base) {
+    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base,
+    unsigned long long* stamps) {
+  const BlockStamp stamp(stamps);
   // block -> job
   int lo = 0, hi = n_jobs - 1;
   while (lo < hi) {
@@ -200,21 +203,24 @@ uint32_t sraw_blocks_for(SrawJobDev* j) {
 
 hipError_t launch_sraw(const SrawJobDev* d_jobs, const uint32_t* d_block_start, int n_jobs,
                        uint32_t total_blocks, const bool versions[3], const void* in_base,
-                       void* out_base, hipStream_t stream) {
+                       void* out_base, hipStream_t stream,
+                       unsigned long long* stamps) {
   if (total_blocks == 0)
     return hipSuccess;
   const dim3 grid(total_blocks), block(SRAW_THREADS);
   const uint8_t* in = static_cast<const uint8_t*>(in_base);
   uint8_t* out = static_cast<uint8_t*>(out_base);
+  // (timed: the kernels of a launch share its slots -- first entry of the first, last exit
+  // of the last)
   if (versions[0])
     hipLaunchKernelGGL(sraw_kernel<0>, grid, block, 0, stream, d_jobs, d_block_start, n_jobs,
-                       in, out);
+                       in, out, stamps);
   if (versions[1])
     hipLaunchKernelGGL(sraw_kernel<1>, grid, block, 0, stream, d_jobs, d_block_start, n_jobs,
-                       in, out);
+                       in, out, stamps);
   if (versions[2])
     hipLaunchKernelGGL(sraw_kernel<2>, grid, block, 0, stream, d_jobs, d_block_start, n_jobs,
-                       in, out);
+                       in, out, stamps);
   return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 // groups from LDS, extracts 8 samples with 64-bit shifts and emits one
 // 16-byte coalesced store per group.  No MFMA: there is no contraction here.
 #include "rsx_device.h"
+#include "rsx_stamp.h"
 
 namespace rsx {
 
@@ -165,7 +166,9 @@ __device__ __forceinline__ void store8(uint16_t* __restrict__ dst, const uint32_
 template <int ORDER, int POST = 0>
 __global__ __launch_bounds__(UNPACK_THREADS) void unpack_kernel(
     const UnpackJobDev* __restrict__ jobs, const uint32_t* __restrict__ job_block_start,
-    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base) {
+    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base,
+    unsigned long long* stamps) {
+  const BlockStamp stamp(stamps);
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint32_t* lds = reinterpret_cast<uint32_t*>(smem);
 
@@ -313,7 +316,9 @@ constexpr int CTRL_LDS_DWORDS = UNPACK_THREADS * 5;
 template <bool BIG>
 __global__ __launch_bounds__(UNPACK_THREADS) void unpack_control_kernel(
     const UnpackJobDev* __restrict__ jobs, const uint32_t* __restrict__ job_block_start,
-    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base) {
+    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base,
+    unsigned long long* stamps) {
+  const BlockStamp stamp(stamps);
   __shared__ __attribute__((aligned(16))) uint32_t lds[CTRL_LDS_DWORDS];
   const int job = find_job(job_block_start, n_jobs);
   const UnpackJobDev J = jobs[job];
@@ -430,7 +435,9 @@ __device__ __forceinline__ uint32_t widen_fp(uint32_t narrow) {
 template <int BPS, bool MSB>
 __global__ __launch_bounds__(UNPACK_THREADS) void unpack_fp_kernel(
     const UnpackJobDev* __restrict__ jobs, const uint32_t* __restrict__ job_block_start,
-    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base) {
+    int n_jobs, const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base,
+    unsigned long long* stamps) {
+  const BlockStamp stamp(stamps);
   const int job = find_job(job_block_start, n_jobs);
   const UnpackJobDev J = jobs[job];
   const uint32_t local_block = blockIdx.x - job_block_start[job];
@@ -540,10 +547,11 @@ const char* unpack_kernel_name() { return "unpack_kernel"; }
 hipError_t launch_unpack_mode(int mode, int order, const UnpackJobDev* d_jobs,
                               const uint32_t* d_block_start, int n_jobs,
                               uint32_t total_blocks, const void* in_base,
-                              void* out_base, hipStream_t stream) {
+                              void* out_base, hipStream_t stream,
+                              unsigned long long* stamps) {
   if (mode == UNPACK_MODE_PACKED)
     return launch_unpack(order, d_jobs, d_block_start, n_jobs, total_blocks, in_base,
-                         out_base, stream);
+                         out_base, stream, stamps);
   if (total_blocks == 0)
     return hipSuccess;
   const dim3 grid(total_blocks), block(UNPACK_THREADS);
@@ -555,41 +563,41 @@ hipError_t launch_unpack_mode(int mode, int order, const UnpackJobDev* d_jobs,
     const bool msb = (order & 0xFF) == RSX_ORDER_MSB;
     if (bps == 32)
       hipLaunchKernelGGL((unpack_fp_kernel<32, false>), grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     else if (bps == 16 && msb)
       hipLaunchKernelGGL((unpack_fp_kernel<16, true>), grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     else if (bps == 16)
       hipLaunchKernelGGL((unpack_fp_kernel<16, false>), grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     else if (msb)
       hipLaunchKernelGGL((unpack_fp_kernel<24, true>), grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     else
       hipLaunchKernelGGL((unpack_fp_kernel<24, false>), grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     return hipGetLastError();
   }
   if (mode == UNPACK_MODE_LUT8) {
     hipLaunchKernelGGL((unpack_kernel<0, 2>), grid, block, unpack_lds_bytes(), stream,
-                       d_jobs, d_block_start, n_jobs, in, out);
+                       d_jobs, d_block_start, n_jobs, in, out, stamps);
     return hipGetLastError();
   }
   if (mode == UNPACK_MODE_SHIFT) {
     const size_t lds = unpack_lds_bytes();
     if (order == RSX_ORDER_LSB)
       hipLaunchKernelGGL((unpack_kernel<0, 1>), grid, block, lds, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     else
       hipLaunchKernelGGL((unpack_kernel<1, 1>), grid, block, lds, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
   } else {
     if (order == RSX_ORDER_LSB)
       hipLaunchKernelGGL(unpack_control_kernel<false>, grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
     else
       hipLaunchKernelGGL(unpack_control_kernel<true>, grid, block, 0, stream, d_jobs,
-                         d_block_start, n_jobs, in, out);
+                         d_block_start, n_jobs, in, out, stamps);
   }
   return hipGetLastError();
 }
@@ -597,7 +605,8 @@ hipError_t launch_unpack_mode(int mode, int order, const UnpackJobDev* d_jobs,
 hipError_t launch_unpack(int order, const UnpackJobDev* d_jobs,
                          const uint32_t* d_block_start, int n_jobs,
                          uint32_t total_blocks, const void* in_base,
-                         void* out_base, hipStream_t stream) {
+                         void* out_base, hipStream_t stream,
+                         unsigned long long* stamps) {
   if (total_blocks == 0)
     return hipSuccess;
   const dim3 grid(total_blocks), block(UNPACK_THREADS);
@@ -607,19 +616,19 @@ hipError_t launch_unpack(int order, const UnpackJobDev* d_jobs,
   switch (order) {
   case RSX_ORDER_LSB:
     hipLaunchKernelGGL(unpack_kernel<0>, grid, block, lds, stream, d_jobs,
-                       d_block_start, n_jobs, in, out);
+                       d_block_start, n_jobs, in, out, stamps);
     break;
   case RSX_ORDER_MSB:
     hipLaunchKernelGGL(unpack_kernel<1>, grid, block, lds, stream, d_jobs,
-                       d_block_start, n_jobs, in, out);
+                       d_block_start, n_jobs, in, out, stamps);
     break;
   case RSX_ORDER_MSB16:
     hipLaunchKernelGGL(unpack_kernel<2>, grid, block, lds, stream, d_jobs,
-                       d_block_start, n_jobs, in, out);
+                       d_block_start, n_jobs, in, out, stamps);
     break;
   default:
     hipLaunchKernelGGL(unpack_kernel<3>, grid, block, lds, stream, d_jobs,
-                       d_block_start, n_jobs, in, out);
+                       d_block_start, n_jobs, in, out, stamps);
     break;
   }
   return hipGetLastError();
