@@ -738,6 +738,69 @@ int rsx_dng_decompress_uncompressed(rsx_ctx* ctx, int n_tiles,
                                     int32_t* tile_status);
 
 /* ------------------------------------------------------------------------ */
+/* 4b. AbstractDngDecompressor, compression 8: deflate + floating-point      */
+/*    predictor (decompressThread<8>, AbstractDngDecompressor.cpp:134-155 -> */
+/*    DeflateDecompressor, decompressors/DeflateDecompressor.cpp:49-176).    */
+/*    All sizes are in SAMPLES: tile_w x tile_h = maxDim (cpp * tileW,       */
+/*    tileH), width x height = dim (cpp * e.width, e.height), off_x, off_y = */
+/*    off (cpp * e.offX, e.offY); cpp is the image's.  The image holds       */
+/*    4-byte samples (RawImageType::F32).                                    */
+/*    Per tile: predFactor = 1 / 2 / 4 for predictor 3 / 34894 / 34895,      */
+/*    times cpp; bytesps = bps / 8; dstLen = bytesps * tile_w * tile_h.      */
+/*    zlib's uncompress(buf, &dstLen, in, in_bytes): the zlib wrapper (CMF,  */
+/*    FLG), the deflate blocks, the Adler-32; bytes behind the stream are    */
+/*    ignored.  Then for every row below `height`, over rows of bytesps *    */
+/*    tile_w bytes: b[col] += b[col - predFactor] mod 256 from predFactor to */
+/*    the end of the row (across the byte planes); sample col = the bytes    */
+/*    b[col + c * tile_w], c = 0 .. bytesps - 1, most significant first;     */
+/*    binary16 and binary24 (1 + 7 + 16) widened as                          */
+/*    extendBinaryFloatingPoint does, binary32 as it is; the first `width`   */
+/*    samples go to out(off_y + row, off_x + col).  Nothing else of the      */
+/*    image is written, its pitch padding included.                          */
+/*    rsx_dng_deflate_validate, in this order: bps not 16 / 24 / 32;         */
+/*    predictor not 3 / 34894 / 34895; an image that cannot hold 4-byte      */
+/*    samples (cpp outside 1..4, no pixels, pitch_bytes no multiple of 4);   */
+/*    an empty tile or window, width > tile_w, height > tile_h; the window   */
+/*    outside the image; pitch_bytes < 4 cpp dim_x -> RSX_ERR_INVALID_ARG;   */
+/*    in_bytes or dstLen >= 4 GiB -> RSX_ERR_UNSUPPORTED.                    */
+/*    Per-tile status:                                                       */
+/*      RSX_OK               libz answers Z_OK and gave exactly dstLen bytes */
+/*                           (empty blocks behind a full output included)    */
+/*      RSX_ERR_UNSUPPORTED  Z_OK with fewer bytes: the reference then reads */
+/*                           indeterminate bytes of a reused buffer -- the   */
+/*                           CPU gets the tile                               */
+/*      RSX_ERR_IO           everything libz rejects ("failed to uncompress  */
+/*                           tile"): a byte too many, a wrong Adler-32,      */
+/*                           FDICT, CM != 8, a window above 15, a bad        */
+/*                           FCHECK, BTYPE 3, LEN != ~NLEN, code length sets */
+/*                           inflate_table rejects, a missing end-of-block   */
+/*                           code, HLIT > 286, HDIST > 30, a bad repeat,     */
+/*                           codes 286 / 287 / distance 30 / 31, a distance  */
+/*                           before the output's start, truncation anywhere  */
+/*    A tile that is not RSX_OK writes NOTHING into the image; the others    */
+/*    are written.  The call returns RSX_ERR_TILE_ERRORS if any tile failed. */
+/*    One upload of the packed tile bytes, one launch sequence, one download;*/
+/*    one host call in rsx_ctx_host_calls.                                   */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_dng_deflate_desc {
+  int32_t bps;       /* 16, 24 or 32 */
+  int32_t predictor; /* 3, 34894 or 34895 */
+} rsx_dng_deflate_desc;
+
+typedef struct rsx_dng_deflate_tile {
+  const uint8_t* in; /* the tile's zlib stream */
+  size_t in_bytes;
+  uint32_t tile_w, tile_h;               /* maxDim, samples */
+  uint32_t off_x, off_y, width, height;  /* off, dim, samples */
+} rsx_dng_deflate_tile;
+
+int rsx_dng_deflate_validate(const rsx_dng_deflate_desc* desc, const rsx_dng_deflate_tile* tile,
+                             const rsx_image* img);
+int rsx_dng_decompress_deflate(rsx_ctx* ctx, const rsx_dng_deflate_desc* desc, int n_tiles,
+                               const rsx_dng_deflate_tile* tiles, const rsx_image* img,
+                               int32_t* tile_status);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */
@@ -898,6 +961,20 @@ typedef struct rsx_panasonic_v4_job {
   uint32_t reserved;
 } rsx_panasonic_v4_job;
 
+/* one tile of a deflate DNG (section 4b): geometry in samples, as in rsx_dng_deflate_tile; any
+ * in_offset, img_offset and pitch_bytes multiples of 4.  The plan owns the inflated bytes of all
+ * its jobs (dstLen each, rounded up to 16); more than 1 GiB of them: RSX_ERR_UNSUPPORTED at
+ * creation.  job_consumed = the stream's length up to and including the Adler-32. */
+typedef struct rsx_dng_deflate_job {
+  rsx_dng_deflate_desc desc;
+  uint32_t tile_w, tile_h;
+  uint32_t off_x, off_y, width, height;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_dng_deflate_job;
+
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */
@@ -936,6 +1013,8 @@ int rsx_samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_jo
                                rsx_plan** out_plan);
 int rsx_panasonic_v4_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_v4_job* jobs,
                                  rsx_plan** out_plan);
+int rsx_dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job* jobs,
+                                rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
                  void* stream);

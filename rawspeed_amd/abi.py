@@ -277,6 +277,26 @@ def samsung_v0_offsets(offsets):
     return arr
 
 
+class DngDeflateDesc(C.Structure):
+    _fields_ = [("bps", C.c_int32), ("predictor", C.c_int32)]
+
+
+class DngDeflateTile(C.Structure):
+    """geometry in samples (include/rsx.h section 4b)"""
+    _fields_ = [("in_", C.c_void_p), ("in_bytes", C.c_size_t),
+                ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("off_x", C.c_uint32), ("off_y", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class DngDeflateJob(C.Structure):
+    _fields_ = [("desc", DngDeflateDesc), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("off_x", C.c_uint32), ("off_y", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32),
+                ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
 def phase_one_strips(table):
     """[(row, offset, bytes)] -> a ctypes array of rsx_phase_one_strip"""
     arr = (PhaseOneStrip * max(1, len(table)))()

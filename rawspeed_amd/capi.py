@@ -37,6 +37,7 @@ EXPORTS = [
     "rsx_panasonic_v4_validate", "rsx_panasonic_v4_decompress", "rsx_panasonic_v4_plan_create",
     "rsx_panasonic_v4_plan_bad_pixels",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
+    "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -114,6 +115,9 @@ def lib():
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p]
+        L.rsx_dng_deflate_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_dng_decompress_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -135,7 +139,8 @@ def lib():
                      "rsx_sraw_plan_create", "rsx_hasselblad_plan_create",
                      "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
                      "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
-                     "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create"):
+                     "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
+                     "rsx_dng_deflate_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -194,6 +199,20 @@ def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
     arr = abi.samsung_v0_offsets(offsets)
     n = len(offsets) if n_offsets is None else n_offsets
     return lib().rsx_samsung_v0_validate(arr, n, in_bytes, C.byref(img_view))
+
+
+def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
+    """geom: (tile_w, tile_h, off_x, off_y, width, height), samples"""
+    t = abi.DngDeflateTile()
+    t.in_, t.in_bytes = in_ptr, in_bytes
+    t.tile_w, t.tile_h, t.off_x, t.off_y, t.width, t.height = geom
+    return t
+
+
+def dng_deflate_validate(bps, predictor, geom, in_bytes, img_view):
+    d = abi.DngDeflateDesc(bps, predictor)
+    t = dng_deflate_tile(geom, in_bytes)
+    return lib().rsx_dng_deflate_validate(C.byref(d), C.byref(t), C.byref(img_view))
 
 
 def _u8(a):
@@ -382,6 +401,21 @@ class Context:
                                              C.byref(img_view), rs)
         return st, (list(rs)[:img_view.dim_y] if rows else None)
 
+    def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
+        """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
+        tiles' zlib streams.  Returns (status, per-tile statuses)."""
+        n = len(geoms)
+        arrs = [_u8(np.frombuffer(d, np.uint8) if isinstance(d, (bytes, bytearray)) else d)
+                for d in datas]
+        keep = [a if a.size else np.zeros(1, np.uint8) for a in arrs]  # (a pointer for no bytes)
+        tiles = (abi.DngDeflateTile * n)()
+        for i in range(n):
+            tiles[i] = dng_deflate_tile(geoms[i], arrs[i].size, keep[i].ctypes.data)
+        d = abi.DngDeflateDesc(bps, predictor)
+        st = (C.c_int32 * n)()
+        rc = lib().rsx_dng_decompress_deflate(self._h, C.byref(d), n, tiles, C.byref(img_view), st)
+        return rc, list(st)
+
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
@@ -456,6 +490,10 @@ class Context:
     def samsung_v0_plan(self, jobs):
         """jobs: abi.SamsungV0Job (their offset arrays are copied at plan creation)"""
         return Plan(self, "rsx_samsung_v0_plan_create", abi.SamsungV0Job, jobs)
+
+    def dng_deflate_plan(self, jobs):
+        """jobs: abi.DngDeflateJob, one per tile (depths, predictors and images may mix)"""
+        return Plan(self, "rsx_dng_deflate_plan_create", abi.DngDeflateJob, jobs)
 
     def pentax_plan(self, jobs):
         return Plan(self, "rsx_pentax_plan_create", abi.PentaxJob, jobs)

@@ -6,6 +6,7 @@
 #include "rsx_device.h"
 #include "rsx_internal.h"
 #include "rsx_ljpeg.h"
+#include "rsx_dng_deflate.h"
 #include "rsx_ljpeg_dev.h"
 #include "rsx_panasonic.h"
 #include "rsx_panasonic_v4.h"
@@ -2008,6 +2009,9 @@ HostRect out_rect(const rsx_samsung_v2_job& j) {
 HostRect out_rect(const rsx_sony_arw1_job& j) {
   return {0, size_t(j.img.dim_y), 0, size_t(j.img.dim_x) * 2};
 }
+HostRect out_rect(const rsx_dng_deflate_job& j) {
+  return {size_t(j.off_y), size_t(j.height), size_t(j.off_x) * 4, size_t(j.width) * 4};
+}
 HostRect out_rect(const rsx_hasselblad_job& j) {
   return {0, size_t(j.img.dim_y), 0, size_t(j.img.dim_x) * 2};
 }
@@ -2635,6 +2639,63 @@ extern "C" int rsx_dng_decompress_ljpeg(rsx_ctx* ctx, int n_tiles,
     std::copy(st.begin(), st.end(), tile_status);
   if (tile_consumed)
     std::copy(cons.begin(), cons.end(), tile_consumed);
+  if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM)
+    return rc;
+  for (int i = 0; i < n_tiles; ++i)
+    if (st[i] != RSX_OK)
+      return RSX_ERR_TILE_ERRORS; // AbstractDngDecompressor.cpp:247-251
+  return RSX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// AbstractDngDecompressor, compression 8 (deflate + floating-point predictor)
+// ---------------------------------------------------------------------------
+extern "C" int rsx_dng_deflate_validate(const rsx_dng_deflate_desc* desc,
+                                        const rsx_dng_deflate_tile* tile, const rsx_image* img) {
+  if (!desc || !tile || !img)
+    return RSX_ERR_INVALID_ARG;
+  return dng_deflate_validate(*desc, tile->tile_w, tile->tile_h, tile->off_x, tile->off_y,
+                              tile->width, tile->height, tile->in_bytes, *img);
+}
+
+extern "C" int rsx_dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job* jobs,
+                                           rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, dng_deflate_plan_create);
+}
+
+// The host-pointer call, as rsx_dng_decompress_ljpeg's: the tiles' bytes packed into one upload,
+// one plan run, the windows of the tiles that decoded back through download_rects.
+extern "C" int rsx_dng_decompress_deflate(rsx_ctx* ctx, const rsx_dng_deflate_desc* desc, int n_tiles,
+                                          const rsx_dng_deflate_tile* tiles, const rsx_image* img,
+                                          int32_t* tile_status) {
+  if (!ctx || !desc || !tiles || n_tiles < 1 || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  std::vector<rsx_dng_deflate_job> jobs(n_tiles);
+  std::vector<const uint8_t*> ins(n_tiles);
+  for (int i = 0; i < n_tiles; ++i) {
+    const rsx_dng_deflate_tile& t = tiles[i];
+    std::memset(&jobs[i], 0, sizeof jobs[i]);
+    jobs[i].desc = *desc;
+    jobs[i].tile_w = t.tile_w;
+    jobs[i].tile_h = t.tile_h;
+    jobs[i].off_x = t.off_x;
+    jobs[i].off_y = t.off_y;
+    jobs[i].width = t.width;
+    jobs[i].height = t.height;
+    jobs[i].in_bytes = t.in_bytes;
+    ins[i] = t.in;
+    if (t.in_bytes && !t.in)
+      return RSX_ERR_INVALID_ARG;
+  }
+  constexpr int32_t ST_UNSET = INT32_MIN; // "ljpeg_family_host never got to this tile"
+  std::vector<int32_t> st(n_tiles, ST_UNSET);
+  const int rc = ljpeg_family_host(ctx, n_tiles, jobs, ins.data(), img, rsx_dng_deflate_plan_create,
+                                   st.data(), nullptr);
+  for (int32_t& v : st)
+    if (v == ST_UNSET)
+      v = rc != RSX_OK ? rc : RSX_ERR_DEVICE;
+  if (tile_status)
+    std::copy(st.begin(), st.end(), tile_status);
   if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM)
     return rc;
   for (int i = 0; i < n_tiles; ++i)

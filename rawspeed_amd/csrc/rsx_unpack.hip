@@ -19,6 +19,7 @@
 // groups from LDS, extracts 8 samples with 64-bit shifts and emits one
 // 16-byte coalesced store per group.  No MFMA: there is no contraction here.
 #include "rsx_device.h"
+#include "rsx_fp_widen.h"
 #include "rsx_stamp.h"
 
 namespace rsx {
@@ -405,32 +406,8 @@ __global__ __launch_bounds__(UNPACK_THREADS) void unpack_control_kernel(
 // 24 or 32 bits on byte boundaries.  One lane owns 4 samples: 8 / 12 / 16 input
 // bytes (unaligned loads, contiguous across the wave), one 16-byte store.
 // extendBinaryFloatingPoint<Narrow, Binary32> (common/FloatingPoint.h:109-145)
-// in integer arithmetic: exact, subnormals renormalised, NaN payload kept.
+// in integer arithmetic: widen_fp (rsx_fp_widen.h).
 // ---------------------------------------------------------------------------
-template <int FRAC, int EXPW>
-__device__ __forceinline__ uint32_t widen_fp(uint32_t narrow) {
-  constexpr int BIAS = (1 << (EXPW - 1)) - 1;
-  const uint32_t sign = (narrow >> (FRAC + EXPW)) & 1u;
-  const uint32_t ne = (narrow >> FRAC) & ((1u << EXPW) - 1u);
-  const uint32_t nf = narrow & ((1u << FRAC) - 1u);
-  uint32_t we = ne - BIAS + 127;
-  uint32_t wf = nf << (23 - FRAC);
-  if (ne == (1u << EXPW) - 1u) {
-    we = 255; // infinity / NaN, fraction widened
-  } else if (ne == 0) {
-    if (nf == 0) {
-      we = 0;
-      wf = 0;
-    } else {
-      // subnormal: normalise (shift until the hidden bit appears)
-      const uint32_t sh = uint32_t(__builtin_clz(wf)) - 8u; // wf < 2^23
-      we = 1 - BIAS + 127 - sh;
-      wf = (wf << sh) & 0x7FFFFFu;
-    }
-  }
-  return (sign << 31) | (we << 23) | wf;
-}
-
 // BPS in {16, 24, 32}; MSB: the bytes of a sample arrive most significant first
 template <int BPS, bool MSB>
 __global__ __launch_bounds__(UNPACK_THREADS) void unpack_fp_kernel(
