@@ -120,6 +120,18 @@ __device__ __forceinline__ uint32_t sv2_peek(const uint8_t* base, uint32_t size,
   return uint32_t((((uint64_t(w0) << 32) | w1) << (q & 31u)) >> 32);
 }
 
+// The bit offset no getBits of a row may pass: the reference's pump loads whole 32-bit words,
+// up to 8 bytes past the end of what is left of the strip.  `size` is everything behind the
+// row's start -- up to 2^32 - 64 bytes where a frame is followed by other data -- and
+// 32 * (size / 4) leaves 32 bits from size = 2^29 on (it wrapped to 96 there, and the first
+// row longer than 96 bits failed with RSX_ERR_INPUT_OVERFLOW): saturated at 2^24 bytes, far
+// past any row (406 blocks of at most 283 bits: offsets stay under 2^20).
+// (tests/test_gpu_samsung_v2.py, test_half_a_gigabyte_behind_the_frame)
+__device__ __forceinline__ uint32_t sv2_bit_limit(uint32_t size) {
+  const uint32_t s = size < (1u << 24) ? size : (1u << 24);
+  return 32u * ((s + 8u) / 4u + 1u);
+}
+
 // How many bytes a row takes, by position: everything in front of a block's differences
 // fits one 32-bit peek (2 + 12 scale, 1 + 3 motion, 1 coded, 8 flags = 27 bits), the up to
 // four explicit lengths a second one, the differences themselves are skipped.  Less than
@@ -128,7 +140,7 @@ __device__ __forceinline__ uint32_t sv2_row_bytes(const Sv2JobDev& J, const uint
                                                   uint32_t size, int first_mode, uint32_t* used) {
   if (size < 4u)
     return 1u;
-  const uint32_t limit = 32u * ((size + 8u) / 4u + 1u);
+  const uint32_t limit = sv2_bit_limit(size);
   const uint32_t optflags = J.optflags, nb = J.nb, max_len = J.bits + 1u;
   const bool qp = (optflags & 4u) != 0, mv = (optflags & 2u) != 0, skip = (optflags & 1u) != 0;
   uint32_t m00 = uint32_t(first_mode), m01 = m00, m10 = m00, m11 = m00;
@@ -207,7 +219,7 @@ __device__ __forceinline__ uint32_t sv2_row_parse(const Sv2JobDev& J, const uint
                                                   uint32_t* hdr, uint32_t* dq, uint32_t* used) {
   if (size < 4u)
     return uint32_t(RSX_ERR_IO); // (BitStreamer.h:56-60)
-  const uint32_t limit = 32u * ((size + 8u) / 4u + 1u);
+  const uint32_t limit = sv2_bit_limit(size);
   const uint32_t optflags = J.optflags, nb = J.nb, max_len = J.bits + 1u;
   const bool qp = (optflags & 4u) != 0, mv = (optflags & 2u) != 0, skip = (optflags & 1u) != 0;
   const int width = int(J.width);

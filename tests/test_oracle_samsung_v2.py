@@ -1,7 +1,8 @@
 """SamsungV2Decompressor: the oracle's restatement (oracle/rsx_oracle.c) against the
 reference build, on streams of the writer in samsung_v2_cases.py (every block mode, scale
-changes, all three optimisation flags) and on damaged ones.  The codec is not served by
-the GPU library yet; this is the checker a later kernel will be held to."""
+changes, all three optimisation flags) and on damaged ones.  This is the checker the device
+decoder (rawspeed_amd/csrc/rsx_samsung_v2.hip) is held to in tests/test_gpu_samsung_v2.py;
+tests/test_samsung_v2_model.py pins it on the value classes and directed streams as well."""
 import numpy as np
 import pytest
 
