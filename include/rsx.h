@@ -703,6 +703,62 @@ int rsx_panasonic_v4_decompress(rsx_ctx* ctx, const rsx_panasonic_v4_desc* desc,
                                 uint32_t bad_cap, uint64_t* n_bad);
 
 /* ------------------------------------------------------------------------ */
+/* 3m. NefDecoder::DecodeNikonSNef                                           */
+/*    replaces the pixel loop of NefDecoder::DecodeNikonSNef                 */
+/*    (decoders/NefDecoder.cpp:707-792), Nikon's "RAW S" files: 12-bit       */
+/*    Y/Y/Cb/Cr packets.  NefDecoder keeps its host work: the container and  */
+/*    DecodeSNefUncompressed (:383-400), the white balance and its check     */
+/*    (:671-687), inv_wb = int(1024.0F / wb) (:693-694), gammaCurve (:696-   */
+/*    703) and the curve guard (:705), which always installs the DITHERING   */
+/*    TableLookUp (its third argument is the literal false).                 */
+/*    W = dim_x pixels; row y is exactly the bytes [3 W y, 3 W (y + 1)), and */
+/*    holds 3 W 16-bit samples in the image (cpp 3).  Group g = 0 .. W/2 - 1 */
+/*    is the bytes b0..b5 at 6 g, four 12-bit fields, LSB first:             */
+/*      y1 = b0 | (b1 & 15) << 8, y2 = b1 >> 4 | b2 << 4,                    */
+/*      cb = b3 | (b4 & 15) << 8, cr = b4 >> 4 | b5 << 4.                    */
+/*    Pixel 1 of the group uses (y1, cb, cr), pixel 2 (y2, cb2, cr2) with    */
+/*    cb2 = (float(cb of g + 1) + float(cb)) * 0.5F, cr2 likewise (exact in  */
+/*    binary32), in the last group of a row cb2 = cb, cr2 = cr.  2048 comes  */
+/*    off all four chroma values.  Per pixel, in binary64, every product and */
+/*    every sum rounded on its own (no fused multiply-add), left to right:   */
+/*      e0 = y + 1.370705 cr, e1 = (y - 0.337633 cb) - 0.698001 cr,          */
+/*      e2 = y + 1.732446 cb; v_k = clampBits(int(e_k), 12) (truncation).    */
+/*    Each v goes through setWithLookUp (RawImage.h:335-353): t = base +     */
+/*    ((delta (r & 2047) + 1024) >> 12) mod 2^16 with base = table[2 v],     */
+/*    delta = table[2 v + 1] (8192 entries read), then r = 15700 (r & 65535) */
+/*    + (r >> 16) -- in the order of the six samples, so the step number of  */
+/*    a sample is its index 6 g + k in the output row; r at the start of a   */
+/*    row is b0 + (b1 << 8) + (b2 << 16) of the row's first three bytes (a   */
+/*    seed of 0 stays 0).  Samples 1 and 4 (green) store t; samples 0 and 3  */
+/*    clampBits((inv_wb_r t + 512) >> 10, 15), samples 2 and 5 the same with */
+/*    inv_wb_b.  Nothing in the data can fail: there is no per-row status.   */
+/*    The table is copied during the call (or at plan creation).             */
+/*    rsx_nikon_snef_validate, in this order: desc NULL or table NULL ->     */
+/*    RSX_ERR_INVALID_ARG; DecodeSNefUncompressed's checks (:389-394): cpp   */
+/*    != 3, dim_x or dim_y <= 0, dim_x odd, dim_x > 3680, dim_y > 2456 (and  */
+/*    pitch_bytes < 6 dim_x) -> RSX_ERR_INVALID_ARG; dim_x < 6 (:666-667,    */
+/*    ThrowIOE) -> RSX_ERR_IO; an inv_wb outside 102 .. 32768 ->             */
+/*    RSX_ERR_INVALID_ARG: the reference's check (:682-687) lets through     */
+/*    float(13421568.0 / 429496627.0) = 0.03124953 <= wb <= 10.0F, and       */
+/*    int(1024.0F / wb) is 102 = int(102.4F) at one end and 32768 =          */
+/*    int(32768.492F) at the other; 32768 * 65535 + 512 = 2147451904 keeps   */
+/*    inv_wb t + 512 inside int; in_bytes < 3 dim_x dim_y (input.peekData)   */
+/*    -> RSX_ERR_IO.  Bytes behind 3 dim_x dim_y are not read; a job         */
+/*    consumes exactly that many.  Pitch padding and everything outside the  */
+/*    image are never written.                                               */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_nikon_snef_desc {
+  int32_t inv_wb_r, inv_wb_b; /* int(1024.0F / wb), NefDecoder.cpp:693-694 */
+  const uint16_t* table;      /* TableLookUp::tables, dither form: [2 v] base, [2 v + 1] delta;
+                                 8192 entries read */
+} rsx_nikon_snef_desc;
+
+int rsx_nikon_snef_validate(const rsx_nikon_snef_desc* desc, const rsx_image* img,
+                            size_t in_bytes);
+int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc, const uint8_t* in,
+                              size_t in_bytes, const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -961,6 +1017,17 @@ typedef struct rsx_panasonic_v4_job {
   uint32_t reserved;
 } rsx_panasonic_v4_job;
 
+/* row y of a job starts at in_offset + 3 y dim_x; its table is copied at plan creation.  Jobs of
+ * different geometry, white balance and table may share a plan; any in_offset, any even
+ * pitch_bytes >= 6 dim_x and any even img_offset */
+typedef struct rsx_nikon_snef_job {
+  rsx_nikon_snef_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_nikon_snef_job;
+
 /* one tile of a deflate DNG (section 4b): geometry in samples, as in rsx_dng_deflate_tile; any
  * in_offset, img_offset and pitch_bytes multiples of 4.  The plan owns the inflated bytes of all
  * its jobs (dstLen each, rounded up to 16); more than 1 GiB of them: RSX_ERR_UNSUPPORTED at
@@ -1013,6 +1080,8 @@ int rsx_samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_jo
                                rsx_plan** out_plan);
 int rsx_panasonic_v4_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_v4_job* jobs,
                                  rsx_plan** out_plan);
+int rsx_nikon_snef_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_nikon_snef_job* jobs,
+                               rsx_plan** out_plan);
 int rsx_dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job* jobs,
                                 rsx_plan** out_plan);
 /* Enqueue one pass of the plan on `stream`. */

@@ -227,6 +227,28 @@ def sony_arw2_desc(mode, table=None):
     return d, arr
 
 
+class NikonSnefDesc(C.Structure):
+    _fields_ = [("inv_wb_r", C.c_int32), ("inv_wb_b", C.c_int32),
+                ("table", C.POINTER(C.c_uint16))]
+
+
+class NikonSnefJob(C.Structure):
+    _fields_ = [("desc", NikonSnefDesc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def nikon_snef_desc(inv_wb_r, inv_wb_b, table=None):
+    """(desc, keep-alive array): `table` as the dithering TableLookUp holds it (uint16, 8192
+    entries read; None leaves the pointer NULL)"""
+    d = NikonSnefDesc()
+    d.inv_wb_r, d.inv_wb_b = inv_wb_r, inv_wb_b
+    arr = None
+    if table is not None:
+        arr = np.ascontiguousarray(table, dtype=np.uint16)
+        d.table = arr.ctypes.data_as(C.POINTER(C.c_uint16))
+    return d, arr
+
+
 class PanasonicDesc(C.Structure):
     _fields_ = [("version", C.c_int32), ("bps", C.c_int32)]
 

@@ -25,12 +25,12 @@ BIN_INFLATE_CHECK = os.path.join(PKG, "rsx_inflate_host_check")
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
-                "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_host.cpp"]
+                "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
                 "rsx_panasonic_dev.h", "rsx_panasonic_v4.h", "rsx_dng_deflate.h",
-                "rsx_inflate_core.h", "rsx_fp_widen.h"]
+                "rsx_inflate_core.h", "rsx_fp_widen.h", "rsx_dither_dev.h", "rsx_nikon_snef.h"]
 
 
 def _hipcc():

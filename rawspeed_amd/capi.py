@@ -36,6 +36,7 @@ EXPORTS = [
     "rsx_samsung_v0_validate", "rsx_samsung_v0_decompress", "rsx_samsung_v0_plan_create",
     "rsx_panasonic_v4_validate", "rsx_panasonic_v4_decompress", "rsx_panasonic_v4_plan_create",
     "rsx_panasonic_v4_plan_bad_pixels",
+    "rsx_nikon_snef_validate", "rsx_nikon_snef_decompress", "rsx_nikon_snef_plan_create",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
@@ -112,6 +113,9 @@ def lib():
                                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rsx_panasonic_v4_plan_bad_pixels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
                                                        C.c_void_p]
+        L.rsx_nikon_snef_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_nikon_snef_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p]
@@ -140,7 +144,7 @@ def lib():
                      "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
                      "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
                      "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
-                     "rsx_dng_deflate_plan_create"):
+                     "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -190,6 +194,14 @@ def panasonic_v4_validate(split, zero_is_bad, img_view, in_bytes):
     d = None if split is None else C.byref(abi.PanasonicV4Desc(split, int(zero_is_bad)))
     v = None if img_view is None else C.byref(img_view)
     return lib().rsx_panasonic_v4_validate(d, v, in_bytes)
+
+
+def nikon_snef_validate(inv_wb, table, img_view, in_bytes):
+    """rsx_nikon_snef_validate; inv_wb = (r, b), None passes a NULL desc; table None a NULL table"""
+    if inv_wb is None:
+        return lib().rsx_nikon_snef_validate(None, C.byref(img_view), in_bytes)
+    d, keep = abi.nikon_snef_desc(inv_wb[0], inv_wb[1], table)
+    return lib().rsx_nikon_snef_validate(C.byref(d), C.byref(img_view), in_bytes)
 
 
 def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
@@ -392,6 +404,13 @@ class Context:
                                                bad_cap, C.byref(n))
         return st, n.value, (bad[:n.value].copy() if st == abi.RSX_OK else None)
 
+    def nikon_snef_decompress(self, inv_wb, table, data, img_view):
+        """inv_wb = (r, b); table: the dithering TableLookUp's 8192 entries"""
+        a = _u8(data)
+        d, keep = abi.nikon_snef_desc(inv_wb[0], inv_wb[1], table)
+        return lib().rsx_nikon_snef_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
+                                               C.byref(img_view))
+
     def samsung_v0_decompress(self, data, offsets, img_view, rows=True):
         """data: the strip; offsets: one per image row.  Returns (status, per-row statuses)."""
         a = _u8(data)
@@ -486,6 +505,10 @@ class Context:
     def panasonic_v4_plan(self, jobs):
         """jobs: abi.PanasonicV4Job (splits, flags and geometries may mix)"""
         return PanasonicV4Plan(self, "rsx_panasonic_v4_plan_create", abi.PanasonicV4Job, jobs)
+
+    def nikon_snef_plan(self, jobs):
+        """jobs: abi.NikonSnefJob (their tables are copied at plan creation)"""
+        return Plan(self, "rsx_nikon_snef_plan_create", abi.NikonSnefJob, jobs)
 
     def samsung_v0_plan(self, jobs):
         """jobs: abi.SamsungV0Job (their offset arrays are copied at plan creation)"""

@@ -14,6 +14,7 @@
 #include "rsx_samsung_v0.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
+#include "rsx_nikon_snef.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2421,7 +2422,7 @@ int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_byte
   return rc;
 }
 
-// One image through a host-pointer call of Phase One, ARW2, Panasonic, Panasonic V4 or SamsungV0: `span` bytes from `src` up as one
+// One image through a host-pointer call of Phase One, ARW2, Panasonic, Panasonic V4, SamsungV0 or sNEF: `span` bytes from `src` up as one
 // copy, the lane's plan for `key` run on them (on_reuse(plan, stream): this call's data onto a
 // plan the lane held), the row statuses out, and the image back as one rectangle through
 // download_rects -- only when every row decoded (the reference throws otherwise, and the
@@ -2472,7 +2473,7 @@ int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT
     return rc; // (a failing row: nothing goes back into the caller's image)
   DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
               static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
-              size_t(img->dim_x) * 2, size_t(img->dim_y)};
+              size_t(img->dim_x) * size_t(img->cpp) * 2, size_t(img->dim_y)};
   std::lock_guard<std::mutex> down_lock(ctx->download_mu);
   return download_rects(ctx, lane.lane, s, &dr, 1);
 }
@@ -2794,6 +2795,50 @@ extern "C" int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* 
   return single_image_host(ctx, key, rsx_sony_arw2_plan_create, job, in, span, img, row_status,
                            [desc](rsx_plan* plan, hipStream_t s) {
                              return sony_arw2_plan_set_table(plan->dec.get(), 0, desc, s);
+                           });
+}
+
+// ---------------------------------------------------------------------------
+// NefDecoder::DecodeNikonSNef
+// ---------------------------------------------------------------------------
+extern "C" int rsx_nikon_snef_validate(const rsx_nikon_snef_desc* desc, const rsx_image* img,
+                                       size_t in_bytes) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return nikon_snef_validate(desc, *img, in_bytes);
+}
+
+extern "C" int rsx_nikon_snef_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_nikon_snef_job* jobs,
+                                          rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, nikon_snef_plan_create);
+}
+
+// The host-pointer call (single_image_host): the 3 w h bytes go up as one copy.  The plan is
+// keyed by the geometry and the white balance; the table itself is call data and goes up on
+// every call.
+extern "C" int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc,
+                                         const uint8_t* in, size_t in_bytes, const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = nikon_snef_validate(desc, *img, in_bytes))
+    return st;
+  const size_t span = size_t(img->dim_x) * size_t(img->dim_y) * 3u;
+  rsx_nikon_snef_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc.inv_wb_r = desc->inv_wb_r;
+  job.desc.inv_wb_b = desc->inv_wb_b;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  key_create(key, rsx_nikon_snef_plan_create);
+  key_append(key, &job); // (desc.table is NULL here: not in the key)
+  job.desc.table = desc->table;
+  // this call's table onto a plan the lane held, ordered before the run on the lane's stream
+  return single_image_host(ctx, key, rsx_nikon_snef_plan_create, job, in, span, img, nullptr,
+                           [desc](rsx_plan* plan, hipStream_t s) {
+                             return nikon_snef_plan_set_table(plan->dec.get(), 0, desc, s);
                            });
 }
 

@@ -12,9 +12,9 @@
 //   table, which steps the generator r' = 15700 (r & 65535) + (r >> 16) once per pixel in
 //   decode order.
 // Nothing in a block depends on another block, save the generator -- and that is a lag-1
-// multiply-with-carry, r_n = r_0 15700^n mod m, m = 15700 * 2^16 - 1 (rsx_ljpeg_recon.hip has
-// the argument; tests/test_dither_jump_model.py checks it): the state in front of block b is
-// one multiplication mod m away from the seed.
+// multiply-with-carry, r_n = r_0 15700^n mod m, m = 15700 * 2^16 - 1 (rsx_dither_dev.h, shared
+// with rsx_nikon_snef.hip; tests/test_dither_jump_model.py checks it): the state in front of
+// block b is one multiplication mod m away from the seed.
 //
 //   arw2_kernel   one workgroup of 256 lanes per item (whole rows of one job, at most 1024
 //                 blocks); one lane per 16-byte block, up to 4 blocks a lane:
@@ -40,6 +40,7 @@
 #include <memory>
 #include <vector>
 
+#include "rsx_dither_dev.h"
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
 #include "rsx_sony_arw2.h"
@@ -56,7 +57,6 @@ constexpr uint32_t A2_MAX_BLOCKS = A2_MAX_W / 16;        // blocks a row (at mos
 constexpr uint32_t A2_LUT = 2048;                        // table entries: p = 0 .. 0x7ff
 constexpr uint32_t A2_NO_TABLE = 0xFFFFFFFFu;
 constexpr uint32_t A2_NONE = 0xFFFFFFFFu;
-constexpr uint64_t A2_MOD = 15700ull * 65536ull - 1ull; // the generator's modulus
 
 struct A2JobDev {
   uint64_t in_off;     // first byte of row 0 in the plan's input
@@ -139,9 +139,7 @@ __device__ __forceinline__ bool a2_block(const uint32_t (&w)[4], uint32_t r, con
     p = uint32_t(i) == imax ? mx : p;
     uint32_t v;
     if constexpr (LUT) {
-      const uint32_t e = lut[p];
-      v = ((e & 0xFFFFu) + (((e >> 16) * (r & 2047u) + 1024u) >> 12)) & 0xFFFFu;
-      r = 15700u * (r & 65535u) + (r >> 16);
+      v = dither_lookup(lut[p], r);
     } else {
       v = p << 1;
     }
@@ -197,7 +195,7 @@ template <bool LUT> __device__ __forceinline__ void a2_item(const A2Args& A, con
       continue;
     uint32_t r = 0;
     if constexpr (LUT)
-      r = uint32_t((uint64_t(seed[k]) * pw[k]) % A2_MOD);
+      r = dither_jump(seed[k], pw[k]);
     uint32_t pk[8];
     if (a2_block<LUT>(w[k], r, lut, pk))
       atomicOr(&bad[(row[k] - I.row0) >> 5], 1u << ((row[k] - I.row0) & 31u));
@@ -260,20 +258,6 @@ __global__ void __launch_bounds__(A2_THREADS) arw2_kernel(A2Args A) {
     if (b)
       atomicMin(&A.job_status[I.job], ((I.row0 + r) << 8) | uint32_t(RSX_ERR_TILE_ERRORS));
   }
-}
-
-// 15700^(16 b) mod m for every block index a row can have
-std::vector<uint32_t> a2_pow16() {
-  std::vector<uint32_t> p(A2_MAX_BLOCKS);
-  uint64_t step = 1;
-  for (int i = 0; i < 16; ++i)
-    step = step * 15700u % A2_MOD;
-  uint64_t x = 1;
-  for (uint32_t b = 0; b < A2_MAX_BLOCKS; ++b) {
-    p[b] = uint32_t(x);
-    x = x * step % A2_MOD;
-  }
-  return p;
 }
 
 // the device form of a table: [p] = base | delta << 16 (a plain table: delta 0)
@@ -376,7 +360,7 @@ int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* job
   }
   p->n_items = uint32_t(items.size());
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const std::vector<uint32_t> pw = a2_pow16();
+  const std::vector<uint32_t> pw = dither_powers(16, A2_MAX_BLOCKS); // 15700^(16 b) mod m
   int st;
   if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(A2JobDev) + 16)) ||
       (st = p->d_items.ensure(items.size() * sizeof(A2Item) + 16)) ||

@@ -79,6 +79,23 @@ inline rsx_sony_arw2_desc arw2_desc(const TableLookUp* t) {
   return d;
 }
 
+// NefDecoder::DecodeNikonSNef: the descriptor and the call.  `t` is the table
+// the curve guard installed (mRaw->table through the accessor of 3i; always the dithering one
+// here), inv_wb_r / inv_wb_b what :693-694 computed, `input` the stream the loop would peek.
+inline int nikon_snef(const ByteStream& input, const RawImage& img, const TableLookUp* t,
+                      int inv_wb_r, int inv_wb_b) {
+  rsx_ctx* rsx = context();
+  if (!rsx || !t || !t->dither)
+    return RSX_ERR_DEVICE;
+  rsx_nikon_snef_desc d{};
+  d.inv_wb_r = inv_wb_r;
+  d.inv_wb_b = inv_wb_b;
+  d.table = t->tables.data(); // (table 0; the call reads its first 8192 entries)
+  const rsx_image v = view(img);
+  const Buffer in = input.peekRemainingBuffer();
+  return rsx_nikon_snef_decompress(rsx, &d, in.begin(), in.getSize(), &v);
+}
+
 // PanasonicV5Decompressor / V6 / V7::decompress(): the descriptor and the call;
 // `input` is the stream the constructor kept (exactly the bytes peekStream took)
 inline int panasonic(int version, uint32_t bps, const ByteStream& input, const RawImage& img) {
