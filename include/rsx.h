@@ -857,6 +857,98 @@ int rsx_dng_decompress_deflate(rsx_ctx* ctx, const rsx_dng_deflate_desc* desc, i
                                int32_t* tile_status);
 
 /* ------------------------------------------------------------------------ */
+/* 4c. AbstractDngDecompressor, compression 9: GoPro VC-5                    */
+/*    replaces VC5Decompressor::decode (decompressThread<9>,                 */
+/*    AbstractDngDecompressor.cpp:161-179 -> decompressors/VC5Decompressor   */
+/*    .cpp).  The constructor keeps its host work: the checks of :384-424    */
+/*    and the tag parse (parseVC5, parseLargeCodeblock); the caller hands    */
+/*    over what the parse found, the code book and the log curve.            */
+/*    The image is W x H 16-bit samples, cpp 1; four channels of ceil(W/2) x */
+/*    ceil(H/2), each three wavelet levels deep: level k = 1..3 has bands of */
+/*    w_k x h_k coefficients, w_k = ceil(w_(k-1) / 2), w_0 = ceil(W / 2).    */
+/*    bands[c][s] is subband s of channel c inside the tile's bytes: s = 0   */
+/*    the low-pass band of level 3 (w_3 h_3 fields of `precision` bits, MSB  */
+/*    first, row-major, each stored as int16_t: values above 32767 wrap;     */
+/*    `bytes` = 8 ceil(w_3 h_3 precision / 64), :657-666), s = 1-3 / 4-6 /   */
+/*    7-9 the high-pass bands 1..3 of level 3 / 2 / 1 (`bytes` = the whole   */
+/*    chunk, :798-799; `quant` the band's Quantization).                     */
+/*    A high-pass band is a sequence of symbols: a word of the code book,    */
+/*    then one sign bit when the word's value is not 0 (1 = negative); it    */
+/*    stands for `count` coefficients value * quant, row-major.  The band    */
+/*    must give exactly w_k h_k coefficients, followed by the end marker     */
+/*    (value +1, count 0).  A band's status, the first that applies in       */
+/*    stream order (the bit reader refills four bytes at a time, bytes       */
+/*    behind the chunk read as zeros; BitStreamer.h:100-132):                */
+/*      RSX_ERR_INPUT_OVERFLOW   a symbol that starts more than              */
+/*                               32 floor((bytes + 8) / 4) bits into the     */
+/*                               chunk ("Buffer overflow read")              */
+/*      RSX_ERR_BAD_HUFFMAN_CODE 26 bits that begin no word of the book      */
+/*      RSX_ERR_VALUE_RANGE      value * quant outside int16_t (:714-718;    */
+/*                               the end marker itself is not multiplied)    */
+/*      RSX_ERR_INVALID_ARG      a count of 0 in front of the last           */
+/*                               coefficient, a run that reaches past it,    */
+/*                               anything but the end marker behind it       */
+/*    Each level turns its four bands into band 0 of the level below (the    */
+/*    last one into the channel plane): reconstructPass down the columns     */
+/*    (:183-232; band 2 over band 0, band 3 over band 1, results truncated   */
+/*    to int16_t), combineLowHighPass along the rows (:234-287) with         */
+/*    descaleShift = 2 where prescale[c][k - 1] == 2, else 0 (:364); level 1 */
+/*    clamps to 0..16383.  Band 0 of levels 2 and 1 is the 2 w_(k+1) x       */
+/*    2 h_(k+1) result of the level above, read as w_k x h_k.  The merge     */
+/*    (:875-931): per 2x2 cell gs = plane 0, rg / bg / gd = planes 1..3      */
+/*    minus 2048; r = gs + 2 rg, b = gs + 2 bg, g1 = gs + gd, g2 = gs - gd,  */
+/*    each through log_table[clamp(v, 0, 4095)]; RGGB stores r g1 / g2 b,    */
+/*    GBRG g1 b / r g2.  When any band fails NOTHING is written (the         */
+/*    reference throws before combineFinalLowpassBands); the job's status is */
+/*    that of its first failing band in (channel, subband) order.  Pitch     */
+/*    padding and everything outside the image are never written.            */
+/*    The code book: the caller's words with `value` already decompanded     */
+/*    (initPrefixCodeDecoder, :437-462); the library holds none.  Refused    */
+/*    (RSX_ERR_INVALID_ARG): more than 264 words or none, a size outside     */
+/*    1..26, bits that do not fit the size, a count above 511, |value| above */
+/*    1023 (the 10 bits a 19-bit code value leaves above the count; the      */
+/*    reference's book reaches 1023), words that are not prefix-free.        */
+/*    rsx_vc5_validate, in this order: desc, log_table or codes NULL; cpp    */
+/*    != 1; dim_x or dim_y <= 0, odd, or above 65534; pitch_bytes < 2 dim_x; */
+/*    phase not 0 / 1; a refused code book -> RSX_ERR_INVALID_ARG; dim_x or  */
+/*    dim_y < 34 -> RSX_ERR_UNSUPPORTED (a level narrower or shorter than 3: */
+/*    the reference's edge filters then read outside its arrays; the CPU     */
+/*    gets the tile); then per channel and subband: a low-pass precision     */
+/*    outside 8..16 -> RSX_ERR_INVALID_ARG; a band that does not lie inside  */
+/*    in_bytes, a low-pass band of fewer than 8 ceil(w_3 h_3 precision / 64) */
+/*    bytes, a high-pass chunk of fewer than 4 bytes (the bit reader's       */
+/*    minimum) -> RSX_ERR_IO.                                                */
+/*    The code book and the log table are copied during the call (or at plan */
+/*    creation).                                                             */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_vc5_code {
+  uint32_t bits;  /* the word, right-justified */
+  uint8_t size;   /* its length in bits */
+  uint16_t count; /* run length; 0: the end marker */
+  int16_t value;  /* decompanded */
+} rsx_vc5_code;
+
+typedef struct rsx_vc5_band {
+  uint64_t offset; /* of the chunk inside the tile's bytes */
+  uint32_t bytes;
+  int16_t quant;      /* high-pass bands */
+  uint16_t precision; /* the low-pass band */
+} rsx_vc5_band;
+
+typedef struct rsx_vc5_desc {
+  int32_t phase;             /* 0 RGGB, 1 GBRG */
+  const uint16_t* log_table; /* mVC5LogTable (:464-488), 4096 entries, white level included */
+  const rsx_vc5_code* codes;
+  int32_t n_codes;
+  rsx_vc5_band bands[4][10]; /* [channel][subband number] */
+  uint8_t prescale[4][3];    /* [channel][level - 1], as parseVC5 left them (:567-576) */
+} rsx_vc5_desc;
+
+int rsx_vc5_validate(const rsx_vc5_desc* desc, const rsx_image* img, size_t in_bytes);
+int rsx_vc5_decompress(rsx_ctx* ctx, const rsx_vc5_desc* desc, const uint8_t* in, size_t in_bytes,
+                       const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */
@@ -1028,6 +1120,22 @@ typedef struct rsx_nikon_snef_job {
   rsx_image img; /* .data ignored */
 } rsx_nikon_snef_job;
 
+/* one VC-5 tile (section 4c): band offsets count from in_offset; the code book and the log table
+ * are copied at plan creation.  Jobs of different geometry, book and table may share a plan; any
+ * in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset.  The band decode loads a
+ * chunk as the aligned dwords that hold a byte of it: up to 3 bytes in front of the chunk's first
+ * byte and up to 3 behind its last one are read (and ignored), never a dword without a byte of
+ * the chunk -- so the input allocation must begin and end on a 4-byte boundary of the address
+ * space, which every hipMalloc allocation does.  The plan owns the band storage of all its jobs
+ * (about 7 bytes a pixel) */
+typedef struct rsx_vc5_job {
+  rsx_vc5_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_vc5_job;
+
 /* one tile of a deflate DNG (section 4b): geometry in samples, as in rsx_dng_deflate_tile; any
  * in_offset, img_offset and pitch_bytes multiples of 4.  The plan owns the inflated bytes of all
  * its jobs (dstLen each, rounded up to 16); more than 1 GiB of them: RSX_ERR_UNSUPPORTED at
@@ -1084,6 +1192,13 @@ int rsx_nikon_snef_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_nikon_snef_jo
                                rsx_plan** out_plan);
 int rsx_dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job* jobs,
                                 rsx_plan** out_plan);
+int rsx_vc5_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_vc5_job* jobs, rsx_plan** out_plan);
+/* After rsx_plan_results of a VC-5 plan: per band of job `job` ([channel][subband], 40 entries
+ * each; any may be NULL) its status, and for the high-pass bands the 128-Kbit windows the band
+ * decode walked and the parse rounds it took over all of them (a round is one parse of every
+ * segment of a window; a window whose guessed entries were all right takes one). */
+int rsx_vc5_plan_bands(rsx_plan* plan, int job, int32_t* band_status, uint32_t* windows,
+                       uint32_t* rounds);
 /* Enqueue one pass of the plan on `stream`. */
 int rsx_plan_run(rsx_plan* plan, const void* in_dev, void* out_dev,
                  void* stream);

@@ -249,6 +249,54 @@ def nikon_snef_desc(inv_wb_r, inv_wb_b, table=None):
     return d, arr
 
 
+class Vc5Code(C.Structure):
+    _fields_ = [("bits", C.c_uint32), ("size", C.c_uint8), ("count", C.c_uint16),
+                ("value", C.c_int16)]
+
+
+class Vc5Band(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("quant", C.c_int16),
+                ("precision", C.c_uint16)]
+
+
+class Vc5Desc(C.Structure):
+    _fields_ = [("phase", C.c_int32), ("log_table", C.POINTER(C.c_uint16)),
+                ("codes", C.POINTER(Vc5Code)), ("n_codes", C.c_int32),
+                ("bands", (Vc5Band * 10) * 4), ("prescale", (C.c_uint8 * 3) * 4)]
+
+
+class Vc5Job(C.Structure):
+    _fields_ = [("desc", Vc5Desc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def vc5_desc(phase, log_table, codes, bands, prescale):
+    """(desc, keep-alive objects).  log_table: 4096 uint16 (None leaves the pointer NULL); codes:
+    rows (size, bits, count, value) (None: NULL); bands[c][s] = (offset, bytes, quant, precision);
+    prescale[c][level - 1]"""
+    d = Vc5Desc()
+    d.phase = phase
+    keep = []
+    if log_table is not None:
+        t = np.ascontiguousarray(log_table, dtype=np.uint16)
+        d.log_table = t.ctypes.data_as(C.POINTER(C.c_uint16))
+        keep.append(t)
+    if codes is not None:
+        arr = (Vc5Code * max(len(codes), 1))()
+        for k, (size, bits, count, value) in enumerate(codes):
+            arr[k].bits, arr[k].size, arr[k].count, arr[k].value = bits, size, count, value
+        d.codes = C.cast(arr, C.POINTER(Vc5Code))
+        d.n_codes = len(codes)
+        keep.append(arr)
+    for c in range(4):
+        for s in range(10):
+            b = d.bands[c][s]
+            b.offset, b.bytes, b.quant, b.precision = bands[c][s]
+        for k in range(3):
+            d.prescale[c][k] = prescale[c][k]
+    return d, keep
+
+
 class PanasonicDesc(C.Structure):
     _fields_ = [("version", C.c_int32), ("bps", C.c_int32)]
 

@@ -4,6 +4,8 @@
   rawspeed_amd/librsx_synth.so  host-side stream writers (gcc)
   rawspeed_amd/librsx_inflate_host.so, rawspeed_amd/rsx_inflate_host_check
                                 the inflate core of the deflate DNG kernel as host C++ (g++)
+  rawspeed_amd/librsx_vc5_host.so, rawspeed_amd/rsx_vc5_host_check
+                                the VC-5 core (rsx_vc5_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -21,16 +23,20 @@ LIB_CORE = os.path.join(PKG, "librsx.so")
 LIB_SYNTH = os.path.join(PKG, "librsx_synth.so")
 LIB_INFLATE_HOST = os.path.join(PKG, "librsx_inflate_host.so")
 BIN_INFLATE_CHECK = os.path.join(PKG, "rsx_inflate_host_check")
+LIB_VC5_HOST = os.path.join(PKG, "librsx_vc5_host.so")
+BIN_VC5_CHECK = os.path.join(PKG, "rsx_vc5_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
-                "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_host.cpp"]
+                "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_vc5.hip",
+                "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
                 "rsx_panasonic_dev.h", "rsx_panasonic_v4.h", "rsx_dng_deflate.h",
-                "rsx_inflate_core.h", "rsx_fp_widen.h", "rsx_dither_dev.h", "rsx_nikon_snef.h"]
+                "rsx_inflate_core.h", "rsx_fp_widen.h", "rsx_dither_dev.h", "rsx_nikon_snef.h",
+                "rsx_vc5.h", "rsx_vc5_core.h"]
 
 
 def _hipcc():
@@ -80,6 +86,25 @@ def build_inflate_host(force=False):
         except RuntimeError:
             _run(main)
     return LIB_INFLATE_HOST, BIN_INFLATE_CHECK
+
+
+def build_vc5_host(force=False):
+    """rsx_vc5_core.h as host C++ (rsx_vc5_host.cpp): the library the tests load, and the same
+    source as a program with AddressSanitizer and UBSan where g++ has their runtimes (it reads a
+    corpus file); without the runtimes the program is built plain."""
+    src = os.path.join(CSRC, "rsx_vc5_host.cpp")
+    deps = [src, os.path.join(CSRC, "rsx_vc5_core.h")]
+    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-I" + CSRC]
+    if force or _stale(LIB_VC5_HOST, deps):
+        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_VC5_HOST, src])
+    if force or _stale(BIN_VC5_CHECK, deps):
+        main = base + ["-O1", "-g", "-DRSX_VC5_HOST_MAIN", "-o", BIN_VC5_CHECK, src]
+        try:
+            _run(main + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                         "-static-libasan", "-static-libubsan"])
+        except RuntimeError:
+            _run(main)
+    return LIB_VC5_HOST, BIN_VC5_CHECK
 
 
 def _compile_objects(objdir, extra_flags, force=False):
@@ -135,7 +160,8 @@ def build_variant(name, extra_flags):
 
 
 def build_all(force=False):
-    return build_core(force), build_synth(force), build_inflate_host(force)
+    return (build_core(force), build_synth(force), build_inflate_host(force),
+            build_vc5_host(force))
 
 
 if __name__ == "__main__":

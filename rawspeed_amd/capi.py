@@ -37,6 +37,7 @@ EXPORTS = [
     "rsx_panasonic_v4_validate", "rsx_panasonic_v4_decompress", "rsx_panasonic_v4_plan_create",
     "rsx_panasonic_v4_plan_bad_pixels",
     "rsx_nikon_snef_validate", "rsx_nikon_snef_decompress", "rsx_nikon_snef_plan_create",
+    "rsx_vc5_validate", "rsx_vc5_decompress", "rsx_vc5_plan_create", "rsx_vc5_plan_bands",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
@@ -116,6 +117,9 @@ def lib():
         L.rsx_nikon_snef_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsx_nikon_snef_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 C.c_void_p]
+        L.rsx_vc5_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_vc5_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_vc5_plan_bands.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p]
@@ -144,7 +148,8 @@ def lib():
                      "rsx_sony_arw1_plan_create", "rsx_phase_one_plan_create",
                      "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
                      "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
-                     "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create"):
+                     "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
+                     "rsx_vc5_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -202,6 +207,12 @@ def nikon_snef_validate(inv_wb, table, img_view, in_bytes):
         return lib().rsx_nikon_snef_validate(None, C.byref(img_view), in_bytes)
     d, keep = abi.nikon_snef_desc(inv_wb[0], inv_wb[1], table)
     return lib().rsx_nikon_snef_validate(C.byref(d), C.byref(img_view), in_bytes)
+
+
+def vc5_validate(desc, img_view, in_bytes):
+    """rsx_vc5_validate; desc: abi.Vc5Desc (abi.vc5_desc), None passes a NULL desc"""
+    return lib().rsx_vc5_validate(None if desc is None else C.byref(desc), C.byref(img_view),
+                                  in_bytes)
 
 
 def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
@@ -411,6 +422,12 @@ class Context:
         return lib().rsx_nikon_snef_decompress(self._h, C.byref(d), a.ctypes.data, a.size,
                                                C.byref(img_view))
 
+    def vc5_decompress(self, desc, data, img_view):
+        """desc: abi.Vc5Desc with band offsets inside `data` (the tile's bytes)"""
+        a = _u8(data)
+        return lib().rsx_vc5_decompress(self._h, C.byref(desc), a.ctypes.data, a.size,
+                                        C.byref(img_view))
+
     def samsung_v0_decompress(self, data, offsets, img_view, rows=True):
         """data: the strip; offsets: one per image row.  Returns (status, per-row statuses)."""
         a = _u8(data)
@@ -510,6 +527,10 @@ class Context:
         """jobs: abi.NikonSnefJob (their tables are copied at plan creation)"""
         return Plan(self, "rsx_nikon_snef_plan_create", abi.NikonSnefJob, jobs)
 
+    def vc5_plan(self, jobs):
+        """jobs: abi.Vc5Job (their code books and log tables are copied at plan creation)"""
+        return Vc5Plan(self, "rsx_vc5_plan_create", abi.Vc5Job, jobs)
+
     def samsung_v0_plan(self, jobs):
         """jobs: abi.SamsungV0Job (their offset arrays are copied at plan creation)"""
         return Plan(self, "rsx_samsung_v0_plan_create", abi.SamsungV0Job, jobs)
@@ -595,3 +616,16 @@ class PanasonicV4Plan(Plan):
         st = lib().rsx_panasonic_v4_plan_bad_pixels(self._h, job, bad.ctypes.data if cap else None,
                                                     cap, C.byref(n))
         return st, n.value, (bad[:n.value].copy() if st == abi.RSX_OK else None)
+
+
+class Vc5Plan(Plan):
+    def bands(self, job):
+        """after results(): (band status, windows, parse rounds), each a (4, 10) array
+        [channel][subband]"""
+        st = np.zeros((4, 10), np.int32)
+        win = np.zeros((4, 10), np.uint32)
+        rnd = np.zeros((4, 10), np.uint32)
+        rc = lib().rsx_vc5_plan_bands(self._h, job, st.ctypes.data, win.ctypes.data, rnd.ctypes.data)
+        if rc != abi.RSX_OK:
+            raise RsxError(rc, "rsx_vc5_plan_bands")
+        return st, win, rnd

@@ -15,6 +15,7 @@
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
+#include "rsx_vc5.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2840,6 +2841,57 @@ extern "C" int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc
                            [desc](rsx_plan* plan, hipStream_t s) {
                              return nikon_snef_plan_set_table(plan->dec.get(), 0, desc, s);
                            });
+}
+
+// ---------------------------------------------------------------------------
+// VC5Decompressor (DNG compression 9)
+// ---------------------------------------------------------------------------
+extern "C" int rsx_vc5_validate(const rsx_vc5_desc* desc, const rsx_image* img, size_t in_bytes) {
+  if (!img)
+    return RSX_ERR_INVALID_ARG;
+  return vc5_validate(desc, *img, in_bytes);
+}
+
+extern "C" int rsx_vc5_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_vc5_job* jobs,
+                                   rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, vc5_plan_create);
+}
+
+extern "C" int rsx_vc5_plan_bands(rsx_plan* plan, int job, int32_t* band_status, uint32_t* windows,
+                                  uint32_t* rounds) {
+  if (!plan || plan->kind != PLAN_DECODER)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
+  return vc5_plan_bands(plan->dec.get(), job, band_status, windows, rounds);
+}
+
+// The host-pointer call (single_image_host): the tile's bytes go up as one copy.  The plan is
+// keyed by the whole descriptor, the code words and the log table included, so a plan the lane
+// held is this call's plan as it stands.
+extern "C" int rsx_vc5_decompress(rsx_ctx* ctx, const rsx_vc5_desc* desc, const uint8_t* in,
+                                  size_t in_bytes, const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = vc5_validate(desc, *img, in_bytes))
+    return st;
+  rsx_vc5_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *desc;
+  job.desc.log_table = nullptr;
+  job.desc.codes = nullptr;
+  job.in_bytes = in_bytes;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  key_create(key, rsx_vc5_plan_create);
+  key_append(key, &job);
+  key_append(key, desc->codes, size_t(desc->n_codes));
+  key_append(key, desc->log_table, size_t(4096));
+  job.desc.log_table = desc->log_table;
+  job.desc.codes = desc->codes;
+  return single_image_host(ctx, key, rsx_vc5_plan_create, job, in, in_bytes, img, nullptr,
+                           [](rsx_plan*, hipStream_t) { return int(RSX_OK); });
 }
 
 // ---------------------------------------------------------------------------

@@ -96,6 +96,51 @@ inline int nikon_snef(const ByteStream& input, const RawImage& img, const TableL
   return rsx_nikon_snef_decompress(rsx, &d, in.begin(), in.getSize(), &v);
 }
 
+// VC5Decompressor::decode(): what the constructor's tag parse found, handed
+// over.  The hunk sits inside the member function, behind initPrefixCodeDecoder() and
+// initVC5LogTable(), and feeds this collector from the members it can see: the code book's rows
+// with the value decompanded, the 4096 entries of mVC5LogTable, every band's input view with its
+// quantisation or precision, every level's prescale.  `tile` is the stream the constructor kept
+// (mBs): band offsets count from the first byte of its buffer.  parseVC5() has read that stream
+// to its end by now, so its remaining view (peekRemainingBuffer) is empty and lies behind every
+// band; Buffer::begin() and Buffer::getSize() are the whole tile whatever the position, and
+// every band's input is a view into it (getStream / getSubView never copy).
+struct Vc5 {
+  rsx_vc5_desc d{};
+  std::vector<rsx_vc5_code> codes;
+  std::vector<uint16_t> log;
+  const uint8_t* base;
+  size_t bytes;
+  Vc5(const ByteStream& tile, bool gbrg) : base(tile.begin()), bytes(tile.getSize()) {
+    d.phase = gbrg ? 1 : 0;
+    codes.reserve(264);
+    log.reserve(4096);
+  }
+  void code(uint32_t bits, unsigned size, unsigned count, int value) {
+    codes.push_back(rsx_vc5_code{bits, uint8_t(size), uint16_t(count), int16_t(value)});
+  }
+  // subband 0: the low-pass band of level 3 (its 8-byte-rounded input); 1-3 / 4-6 / 7-9: bands
+  // 1..3 of level 3 / 2 / 1
+  void band(int channel, int subband, Array1DRef<const uint8_t> input, int quant, int precision) {
+    rsx_vc5_band& b = d.bands[channel][subband];
+    b.offset = uint64_t(input.begin() - base);
+    b.bytes = uint32_t(input.size());
+    b.quant = int16_t(quant);
+    b.precision = uint16_t(precision);
+  }
+  void prescale(int channel, int level, int value) { d.prescale[channel][level - 1] = uint8_t(value); }
+  int run(const RawImage& img) {
+    rsx_ctx* rsx = context();
+    if (!rsx || log.size() != 4096)
+      return RSX_ERR_DEVICE;
+    d.log_table = log.data();
+    d.codes = codes.data();
+    d.n_codes = int(codes.size());
+    const rsx_image v = view(img);
+    return rsx_vc5_decompress(rsx, &d, base, bytes, &v);
+  }
+};
+
 // PanasonicV5Decompressor / V6 / V7::decompress(): the descriptor and the call;
 // `input` is the stream the constructor kept (exactly the bytes peekStream took)
 inline int panasonic(int version, uint32_t bps, const ByteStream& input, const RawImage& img) {
