@@ -445,8 +445,11 @@ int rsx_sony_arw1_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
 /*    (decompressors/PhaseOneDecompressor.cpp:156-170 -> decompressStrip     */
 /*    :85-136 for every strip).  IiqDecoder keeps its host work: container   */
 /*    parsing, computeSripes (IiqDecoder.cpp:75-118: a strip runs from its   */
-/*    offset to the next larger one, the last to the end of raw_data) and    */
-/*    CorrectPhaseOneC.  One strip per image row; each is a BitStreamerMSB32 */
+/*    offset to the next larger one, the last to the end of raw_data); the   */
+/*    pixel passes of CorrectPhaseOneC have a device path of their own       */
+/*    (section 3n: rsx_phase_one_decompress_corrected decodes, corrects and  */
+/*    downloads once), its parse, the defect list and correctBadColumn stay  */
+/*    on the host.  One strip per image row; each is a BitStreamerMSB32      */
 /*    over exactly its own bytes (bytes behind the strip read as zero, not   */
 /*    as the next row).  Per row: pred[2] = {0, 0}; for col < (w & ~7),      */
 /*    col % 8 == 0, a header for len[0] then len[1] (up to five 0-bits up to */
@@ -757,6 +760,97 @@ int rsx_nikon_snef_validate(const rsx_nikon_snef_desc* desc, const rsx_image* im
                             size_t in_bytes);
 int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc, const uint8_t* in,
                               size_t in_bytes, const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
+/* 3n. IiqDecoder::CorrectPhaseOneC: flat field and quadrant curves          */
+/*    replaces the pixel passes of PhaseOneFlatField (decoders/IiqDecoder    */
+/*    .cpp:410-479) and CorrectQuadrantMultipliersCombined (:335-405) behind */
+/*    PhaseOneDecompressor::decompress().  IiqDecoder keeps the parse of the */
+/*    correction block (:280-325), the spline (Spline<>::calculateCurve, its */
+/*    checks included), the defect list and correctBadColumn (which reads    */
+/*    neighbouring pixels).  The image is uint16, cpp 1.  Every operation    */
+/*    reads and writes only the pixel it stands on, so a list of them, in    */
+/*    file order, is ONE pass on the device: each pixel gets the whole list. */
+/*    RSX_IIQ_OP_FLAT_FIELD: `payload` is the entry's bytes as they are in   */
+/*    the file; nc = 2 (luma, entry 0x410) or 4 (`chroma`, entry 0x40b).     */
+/*    head[0..7] = eight little-endian u16.  Any of head[2..5] zero: the op  */
+/*    does nothing.  wide = ceil(head[2] / head[4]), high = ceil(head[3] /   */
+/*    head[5]); behind the head high x wide x nc/2 u16 values v(y, x, c),    */
+/*    num = v / 32768.0F.  mrow(x, c) = num at y = 0; at every y >= 1 the    */
+/*    slope mrow(x, c + 1) = (num - mrow(x, c)) / head[5], then for the rows */
+/*    head[1] + (y - 1) head[5] <= row < min(dim_y, head[1] + y head[5],     */
+/*    head[1] + head[3] - head[5]): for x = 1 .. wide - 1 mult[c] =          */
+/*    mrow(x - 1, c), step = (mrow(x, c) - mult[c]) / head[4], and for the   */
+/*    columns head[0] + (x - 1) head[4] <= col < min(dim_x, head[0] + x      */
+/*    head[4], head[0] + head[2] - head[4]): pixel = min(unsigned(float(     */
+/*    pixel) * mult[c]), 65535) (truncation; a product below 0 gives 0),     */
+/*    then mult[c] += step for every plane; after the row mrow(x, c) +=      */
+/*    mrow(x, c + 1).  All of it in binary32, every operation rounded on its */
+/*    own, the running sums as REPEATED additions (their drift feeds the     */
+/*    next slope).  Luma: c = 0 at every pixel.  Chroma: c = cfa[(row mod    */
+/*    cfa_w) + (col mod cfa_h) cfa_w] -- the reference's getColorAt(row,     */
+/*    col), row passed as x -- 0 (red) uses plane 0, 2 (blue) plane 2, odd   */
+/*    colours leave the pixel alone.                                         */
+/*    RSX_IIQ_OP_QUADRANT_CURVES: `curves` = four curves of 65536 u16,       */
+/*    [quadRow][quadCol]; quadRow = row >= split_row, quadCol = col >=       */
+/*    split_col; diff = pixel < black_level ? pixel : uint16(black_level);   */
+/*    pixel = uint16(curve[pixel - diff] + diff).                            */
+/*    rsx_iiq_correct_validate, in this order: corr or img NULL, cpp != 1,   */
+/*    dim_x or dim_y <= 0, pitch_bytes < 2 dim_x -> RSX_ERR_INVALID_ARG;     */
+/*    n_ops outside 0..16, an unknown kind, a NULL payload or curves ->      */
+/*    RSX_ERR_INVALID_ARG; then per op in list order: a payload shorter than */
+/*    16 bytes, or shorter than 16 + 2 high wide nc/2 when no head field     */
+/*    2..5 is zero -> RSX_ERR_IO (the reference throws half-way through the  */
+/*    image and the file fails); chroma with cfa_w cfa_h == 0 or > 64 ->     */
+/*    RSX_ERR_INVALID_ARG ("No CFA size set"); chroma with an even colour    */
+/*    other than 0 or 2 in the CFA -> RSX_ERR_UNSUPPORTED (the reference     */
+/*    indexes mult[4..] outside its array); split_row > dim_y or split_col   */
+/*    > dim_x -> RSX_ERR_INVALID_ARG; a flat field whose row table (touched  */
+/*    rows x cells in reach of the image x nc/2 floats) exceeds 2^26 floats  */
+/*    (256 MiB; 1 x 1 cells over a full 11976 x 8854 frame would take 848    */
+/*    MiB, cells of 4 x 4 and up fit; cells wider than 32 columns keep a     */
+/*    start value every 32 columns on top, rows x width / 32 x nc/2 floats)  */
+/*    -> RSX_ERR_UNSUPPORTED.                                                */
+/*    On any status but RSX_OK the image is untouched.  n_ops == 0 is        */
+/*    RSX_OK and writes nothing; pixels outside every op's area and pitch    */
+/*    padding are never written.  Payloads and curves are copied during the  */
+/*    call (or at plan creation).                                            */
+/*    rsx_iiq_correct works in place; img->data may be a host pointer (the   */
+/*    image goes up, is corrected and comes back) or a device pointer (the   */
+/*    call returns when the pass is done).                                   */
+/*    rsx_phase_one_decompress_corrected = rsx_phase_one_decompress, the     */
+/*    list applied to the decoded image on the device, ONE download.  A      */
+/*    failing strip or a refused list leaves the caller's image untouched.   */
+/* ------------------------------------------------------------------------ */
+#define RSX_IIQ_MAX_OPS 16
+typedef enum rsx_iiq_op_kind {
+  RSX_IIQ_OP_FLAT_FIELD = 0,
+  RSX_IIQ_OP_QUADRANT_CURVES = 1
+} rsx_iiq_op_kind;
+
+typedef struct rsx_iiq_op {
+  int32_t kind;           /* rsx_iiq_op_kind */
+  int32_t chroma;         /* flat field: 0 luma (0x410), 1 chroma (0x40b) */
+  const uint8_t* payload; /* flat field: the entry's bytes, head included */
+  uint32_t payload_bytes;
+  uint32_t black_level;   /* quadrant curves: IiqDecoder::black_level */
+  const uint16_t* curves; /* quadrant curves: 4 x 65536, [quadRow][quadCol] */
+  uint32_t split_row, split_col;
+} rsx_iiq_op;
+
+typedef struct rsx_iiq_corr {
+  int32_t n_ops;
+  int32_t cfa_w, cfa_h; /* mRaw->cfa.getSize(); 0 x 0: none */
+  uint8_t cfa[64];      /* CFAColor values, cfa[x + y cfa_w] */
+  rsx_iiq_op ops[RSX_IIQ_MAX_OPS];
+} rsx_iiq_corr;
+
+int rsx_iiq_correct_validate(const rsx_iiq_corr* corr, const rsx_image* img);
+int rsx_iiq_correct(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx_image* img);
+int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                       int n_strips, const rsx_phase_one_strip* strips,
+                                       const rsx_iiq_corr* corr, const rsx_image* img,
+                                       int32_t* strip_status);
 
 /* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
@@ -1120,6 +1214,18 @@ typedef struct rsx_nikon_snef_job {
   rsx_image img; /* .data ignored */
 } rsx_nikon_snef_job;
 
+/* one image's corrections (section 3n), in place: the pass reads and writes the plan's OUTPUT
+ * buffer (rsx_plan_run's in_dev is ignored and may equal out_dev), so a caller runs its Phase One
+ * plan and then this one on the same buffer and stream.  Jobs of different geometry and different
+ * lists may share a plan; img_offset and pitch_bytes even.  Payloads and curves are copied at plan
+ * creation.  Because the work is in place a plan never runs a part of its jobs: a job that fails
+ * rsx_iiq_correct_validate fails the creation with that status. */
+typedef struct rsx_iiq_correct_job {
+  rsx_iiq_corr corr;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_iiq_correct_job;
+
 /* one VC-5 tile (section 4c): band offsets count from in_offset; the code book and the log table
  * are copied at plan creation.  Jobs of different geometry, book and table may share a plan; any
  * in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset.  The band decode loads a
@@ -1193,6 +1299,8 @@ int rsx_nikon_snef_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_nikon_snef_jo
 int rsx_dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job* jobs,
                                 rsx_plan** out_plan);
 int rsx_vc5_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_vc5_job* jobs, rsx_plan** out_plan);
+int rsx_iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job* jobs,
+                                rsx_plan** out_plan);
 /* After rsx_plan_results of a VC-5 plan: per band of job `job` ([channel][subband], 40 entries
  * each; any may be NULL) its status, and for the high-pass bands the 128-Kbit windows the band
  * decode walked and the parse rounds it took over all of them (a round is one parse of every

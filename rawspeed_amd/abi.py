@@ -297,6 +297,60 @@ def vc5_desc(phase, log_table, codes, bands, prescale):
     return d, keep
 
 
+RSX_IIQ_MAX_OPS = 16
+RSX_IIQ_OP_FLAT_FIELD, RSX_IIQ_OP_QUADRANT_CURVES = 0, 1
+
+
+class IiqOp(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("chroma", C.c_int32), ("payload", C.c_void_p),
+                ("payload_bytes", C.c_uint32), ("black_level", C.c_uint32),
+                ("curves", C.c_void_p), ("split_row", C.c_uint32), ("split_col", C.c_uint32)]
+
+
+class IiqCorr(C.Structure):
+    _fields_ = [("n_ops", C.c_int32), ("cfa_w", C.c_int32), ("cfa_h", C.c_int32),
+                ("cfa", C.c_uint8 * 64), ("ops", IiqOp * RSX_IIQ_MAX_OPS)]
+
+
+class IiqCorrectJob(C.Structure):
+    _fields_ = [("corr", IiqCorr), ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def iiq_corr(ops, cfa=None, n_ops=None):
+    """(rsx_iiq_corr, keep-alive objects).  ops: ("ff", payload bytes, chroma[, payload_bytes]) or
+    ("quad", curves (4, 65536) uint16, split_row, split_col, black_level) or ("kind", k) for an
+    unknown kind; a payload or curves of None leaves the pointer NULL.  cfa: (cfa_w, cfa_h,
+    colours).  n_ops overrides the count (the list itself holds at most 16)."""
+    d = IiqCorr()
+    keep = []
+    d.n_ops = len(ops) if n_ops is None else n_ops
+    if cfa is not None:
+        d.cfa_w, d.cfa_h = cfa[0], cfa[1]
+        for k, c in enumerate(list(cfa[2])[:64]):
+            d.cfa[k] = c
+    for k, op in enumerate(ops[:RSX_IIQ_MAX_OPS]):
+        o = d.ops[k]
+        if op[0] == "ff":
+            o.kind, o.chroma = RSX_IIQ_OP_FLAT_FIELD, int(op[2])
+            if op[1] is not None:
+                a = np.frombuffer(bytes(op[1]), dtype=np.uint8).copy()
+                if a.size == 0:
+                    a = np.zeros(1, np.uint8)
+                o.payload = a.ctypes.data
+                o.payload_bytes = len(op[1]) if len(op) < 4 else op[3]
+                keep.append(a)
+        elif op[0] == "quad":
+            o.kind = RSX_IIQ_OP_QUADRANT_CURVES
+            if op[1] is not None:
+                a = np.ascontiguousarray(op[1], dtype=np.uint16).reshape(4 * 65536)
+                o.curves = a.ctypes.data
+                keep.append(a)
+            o.split_row, o.split_col, o.black_level = op[2], op[3], op[4]
+        else:
+            o.kind = op[1]
+    return d, keep
+
+
 class PanasonicDesc(C.Structure):
     _fields_ = [("version", C.c_int32), ("bps", C.c_int32)]
 

@@ -38,6 +38,8 @@ EXPORTS = [
     "rsx_panasonic_v4_plan_bad_pixels",
     "rsx_nikon_snef_validate", "rsx_nikon_snef_decompress", "rsx_nikon_snef_plan_create",
     "rsx_vc5_validate", "rsx_vc5_decompress", "rsx_vc5_plan_create", "rsx_vc5_plan_bands",
+    "rsx_iiq_correct_validate", "rsx_iiq_correct", "rsx_phase_one_decompress_corrected",
+    "rsx_iiq_correct_plan_create",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
@@ -119,6 +121,11 @@ def lib():
                                                 C.c_void_p]
         L.rsx_vc5_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsx_vc5_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_iiq_correct_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_iiq_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_phase_one_decompress_corrected.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]
         L.rsx_vc5_plan_bands.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -149,7 +156,7 @@ def lib():
                      "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
                      "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
                      "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
-                     "rsx_vc5_plan_create"):
+                     "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -213,6 +220,12 @@ def vc5_validate(desc, img_view, in_bytes):
     """rsx_vc5_validate; desc: abi.Vc5Desc (abi.vc5_desc), None passes a NULL desc"""
     return lib().rsx_vc5_validate(None if desc is None else C.byref(desc), C.byref(img_view),
                                   in_bytes)
+
+
+def iiq_correct_validate(corr, img_view):
+    """rsx_iiq_correct_validate; corr: abi.IiqCorr (abi.iiq_corr), None passes a NULL list"""
+    return lib().rsx_iiq_correct_validate(None if corr is None else C.byref(corr),
+                                          C.byref(img_view))
 
 
 def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
@@ -388,6 +401,20 @@ class Context:
                                             C.byref(img_view), rows)
         return st, list(rows)[:img_view.dim_y]
 
+    def iiq_correct(self, corr, img_view):
+        """corr: abi.IiqCorr; img_view.data a host or a device pointer; in place"""
+        return lib().rsx_iiq_correct(self._h, C.byref(corr), C.byref(img_view))
+
+    def phase_one_decompress_corrected(self, data, strips, corr, img_view):
+        """phase_one_decompress, then the list `corr` (abi.IiqCorr) on the device, one download.
+        Returns (status, per-row statuses)."""
+        a = _u8(data)
+        arr = abi.phase_one_strips(strips)
+        rows = (C.c_int32 * max(1, img_view.dim_y))()
+        st = lib().rsx_phase_one_decompress_corrected(self._h, a.ctypes.data, a.size, len(strips),
+                                                      arr, C.byref(corr), C.byref(img_view), rows)
+        return st, list(rows)[:img_view.dim_y]
+
     def sony_arw2_decompress(self, mode, table, data, img_view, rows=True):
         """Returns (status, per-row statuses or None)."""
         a = _u8(data)
@@ -510,6 +537,11 @@ class Context:
     def phase_one_plan(self, jobs):
         """jobs: abi.PhaseOneJob (their strip arrays are copied at plan creation)"""
         return Plan(self, "rsx_phase_one_plan_create", abi.PhaseOneJob, jobs)
+
+    def iiq_correct_plan(self, jobs):
+        """jobs: abi.IiqCorrectJob (payloads and curves are copied at plan creation); runs in
+        place on the output buffer"""
+        return Plan(self, "rsx_iiq_correct_plan_create", abi.IiqCorrectJob, jobs)
 
     def sony_arw2_plan(self, jobs):
         """jobs: abi.SonyArw2Job (their tables are copied at plan creation)"""

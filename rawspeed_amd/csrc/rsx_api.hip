@@ -16,6 +16,7 @@
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
 #include "rsx_vc5.h"
+#include "rsx_iiq_corr.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2431,10 +2432,13 @@ int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_byte
 // on_done(plan, rc): what the call takes from the plan besides the image, behind the results; the
 // status it returns decides about the download (Panasonic V4: the list, and an image that is
 // complete although the list did not fit).
-template <typename JobT, typename ReuseFn, typename DoneFn>
+// before_download(device image, stream): what the call does to the decoded image on the device in
+// front of the download (Phase One with corrections); a status but RSX_OK ends the call with it.
+template <typename JobT, typename ReuseFn, typename DoneFn, typename PostFn>
 int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
                       const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
-                      int32_t* row_status, ReuseFn on_reuse, DoneFn on_done) {
+                      int32_t* row_status, ReuseFn on_reuse, DoneFn on_done,
+                      PostFn before_download) {
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   LaneGuard lane(ctx, &key);
   if (!lane.lane)
@@ -2472,11 +2476,21 @@ int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT
   }
   if (rc != RSX_OK)
     return rc; // (a failing row: nothing goes back into the caller's image)
+  if (int e = before_download(lane.lane->d_out.ptr, s))
+    return e;
   DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
               static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
               size_t(img->dim_x) * size_t(img->cpp) * 2, size_t(img->dim_y)};
   std::lock_guard<std::mutex> down_lock(ctx->download_mu);
   return download_rects(ctx, lane.lane, s, &dr, 1);
+}
+
+template <typename JobT, typename ReuseFn, typename DoneFn>
+int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
+                      const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
+                      int32_t* row_status, ReuseFn on_reuse, DoneFn on_done) {
+  return single_image_host(ctx, key, create, job, src, span, img, row_status, on_reuse, on_done,
+                           [](void*, hipStream_t) { return int(RSX_OK); });
 }
 
 template <typename JobT, typename ReuseFn>
@@ -2723,14 +2737,10 @@ extern "C" int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_pha
 
 // The host-pointer call (single_image_host): the bytes the strips cover go up as one copy; the
 // plan's key holds the strip table.
-extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
-                                        int n_strips, const rsx_phase_one_strip* strips,
-                                        const rsx_image* img, int32_t* strip_status) {
-  if (!ctx || !in || !strips || !img || !img->data)
-    return RSX_ERR_INVALID_ARG;
-  ++ctx->host_calls;
-  if (int st = phase_one_validate(n_strips, strips, in_bytes, *img))
-    return st;
+namespace {
+template <typename PostFn>
+int phase_one_host(rsx_ctx* ctx, const uint8_t* in, int n_strips, const rsx_phase_one_strip* strips,
+                   const rsx_image* img, int32_t* strip_status, PostFn before_download) {
   uint64_t lo = ~uint64_t(0), hi = 0;
   for (int i = 0; i < n_strips; ++i) {
     lo = std::min<uint64_t>(lo, strips[i].offset);
@@ -2752,7 +2762,125 @@ extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t 
   key_append(key, local.data(), local.size());
   job.strips = local.data();
   return single_image_host(ctx, key, rsx_phase_one_plan_create, job, in + lo, span, img,
-                           strip_status, [](rsx_plan*, hipStream_t) { return RSX_OK; });
+                           strip_status, [](rsx_plan*, hipStream_t) { return int(RSX_OK); },
+                           [](rsx_plan*, int rc) { return rc; }, before_download);
+}
+} // namespace
+
+extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                        int n_strips, const rsx_phase_one_strip* strips,
+                                        const rsx_image* img, int32_t* strip_status) {
+  if (!ctx || !in || !strips || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = phase_one_validate(n_strips, strips, in_bytes, *img))
+    return st;
+  return phase_one_host(ctx, in, n_strips, strips, img, strip_status,
+                        [](void*, hipStream_t) { return int(RSX_OK); });
+}
+
+// ---------------------------------------------------------------------------
+// IiqDecoder::CorrectPhaseOneC (flat field, quadrant curves)
+// ---------------------------------------------------------------------------
+extern "C" int rsx_iiq_correct_validate(const rsx_iiq_corr* corr, const rsx_image* img) {
+  return iiq_correct_validate(corr, img);
+}
+
+extern "C" int rsx_iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs,
+                                           const rsx_iiq_correct_job* jobs, rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, iiq_correct_plan_create);
+}
+
+namespace {
+// the one-job plan of a host call: made for the call, not kept in a lane (its key would be the
+// payloads and 512 KiB a curve set)
+struct IiqCallPlan {
+  rsx_plan* plan = nullptr;
+  ~IiqCallPlan() { rsx_plan_destroy(plan); }
+  int create(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx_image* img) {
+    auto job = std::make_unique<rsx_iiq_correct_job>();
+    job->corr = *corr;
+    job->img_offset = 0;
+    job->img = *img;
+    job->img.data = nullptr;
+    return rsx_iiq_correct_plan_create(ctx, 1, job.get(), &plan);
+  }
+  // in place on `dev`; returns when the pass is done
+  int run(void* dev, hipStream_t s) {
+    if (int st = rsx_plan_run(plan, dev, dev, s))
+      return st;
+    return rsx_plan_results(plan, nullptr, nullptr);
+  }
+};
+} // namespace
+
+// In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
+// work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
+// and come back through download_rects.
+extern "C" int rsx_iiq_correct(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx_image* img) {
+  if (!ctx || !corr || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = iiq_correct_validate(corr, img))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  if (corr->n_ops == 0)
+    return RSX_OK;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof attr);
+  bool on_device = false;
+  if (hipPointerGetAttributes(&attr, img->data) == hipSuccess)
+    on_device = attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+  else
+    (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
+  IiqCallPlan call;
+  if (int st = call.create(ctx, corr, img))
+    return st;
+  if (on_device)
+    return call.run(img->data, nullptr);
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t row_bytes = size_t(img->dim_x) * 2;
+  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
+  if (int e = lane.lane->d_out.ensure(bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice, s));
+  }
+  if (int st = call.run(lane.lane->d_out.ptr, s))
+    return st;
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
+              size_t(img->dim_y)};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  return download_rects(ctx, lane.lane, s, &dr, 1);
+}
+
+// rsx_phase_one_decompress with the corrections on the decoded image in front of the download
+extern "C" int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                                  int n_strips, const rsx_phase_one_strip* strips,
+                                                  const rsx_iiq_corr* corr, const rsx_image* img,
+                                                  int32_t* strip_status) {
+  if (!ctx || !in || !strips || !corr || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = phase_one_validate(n_strips, strips, in_bytes, *img))
+    return st;
+  if (int st = iiq_correct_validate(corr, img))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  IiqCallPlan call;
+  if (corr->n_ops != 0)
+    if (int st = call.create(ctx, corr, img))
+      return st;
+  return phase_one_host(ctx, in, n_strips, strips, img, strip_status,
+                        [&](void* dev, hipStream_t s) { return call.plan ? call.run(dev, s) : int(RSX_OK); });
 }
 
 // ---------------------------------------------------------------------------

@@ -27,6 +27,7 @@
 #include "io/Buffer.h"
 #include "io/ByteStream.h"
 #include "io/IOException.h"
+#include "metadata/ColorFilterArray.h"
 
 #include <atomic>
 #include <cstddef>
@@ -138,6 +139,76 @@ struct Vc5 {
     d.n_codes = int(codes.size());
     const rsx_image v = view(img);
     return rsx_vc5_decompress(rsx, &d, base, bytes, &v);
+  }
+};
+
+// IiqDecoder::decodeRawInternal(): the correction entries of the 0x110 block as
+// an op list, in file order, for rsx_phase_one_decompress_corrected.  The hunk parses the block
+// first (what CorrectPhaseOneC's switch does, without touching a pixel) and feeds this collector:
+// a flat-field entry is handed over as the bytes of its sub-stream; a quadrant entry as the four
+// curves the reference's own Spline<>::calculateCurve() gave for the control points of
+// :338-373 (its checks have thrown by then, as they would have); the CFA as mRaw->cfa holds it.
+// More than RSX_IIQ_MAX_OPS entries, or a CFA of more than 64 positions: `usable` goes false and
+// the hunk keeps the host path.
+struct IiqCorrections {
+  rsx_iiq_corr d{};
+  std::vector<std::vector<uint16_t>> curves; // [op]: 4 x 65536, [quadRow][quadCol]
+  bool usable = true;
+  IiqCorrections() { curves.reserve(RSX_IIQ_MAX_OPS); }
+  rsx_iiq_op* next(int kind) {
+    if (d.n_ops >= RSX_IIQ_MAX_OPS) {
+      usable = false;
+      return nullptr;
+    }
+    rsx_iiq_op* op = &d.ops[d.n_ops++];
+    op->kind = kind;
+    return op;
+  }
+  void flat_field(const ByteStream& entry, bool chroma) {
+    if (rsx_iiq_op* op = next(RSX_IIQ_OP_FLAT_FIELD)) {
+      const Buffer b = entry.peekRemainingBuffer();
+      op->chroma = chroma ? 1 : 0;
+      op->payload = b.begin();
+      op->payload_bytes = b.getSize();
+    }
+  }
+  // quad[quadRow][quadCol]: 65536 entries each
+  void quadrant(const std::vector<uint16_t> (&quad)[2][2], uint32_t split_row, uint32_t split_col,
+                uint32_t black_level) {
+    if (rsx_iiq_op* op = next(RSX_IIQ_OP_QUADRANT_CURVES)) {
+      std::vector<uint16_t>& all = curves.emplace_back();
+      all.reserve(4 * 65536);
+      for (const auto& row : quad)
+        for (const std::vector<uint16_t>& c : row)
+          all.insert(all.end(), c.begin(), c.end());
+      usable = usable && all.size() == 4 * 65536;
+      op->curves = all.data();
+      op->split_row = split_row;
+      op->split_col = split_col;
+      op->black_level = black_level;
+    }
+  }
+  void cfa(const ColorFilterArray& c) {
+    const iPoint2D size = c.getSize();
+    if (size.area() > 64) {
+      usable = false;
+      return;
+    }
+    d.cfa_w = size.x;
+    d.cfa_h = size.y;
+    for (int y = 0; y < size.y; ++y)
+      for (int x = 0; x < size.x; ++x)
+        d.cfa[x + y * size.x] = static_cast<uint8_t>(c.getColorAt(x, y));
+  }
+  // decode + corrections + the one download; `table` and [lo, hi) as in the hunk of 3h
+  int run(const uint8_t* lo, size_t bytes, const std::vector<rsx_phase_one_strip>& table,
+          const RawImage& img) {
+    rsx_ctx* rsx = context();
+    if (!rsx || !usable)
+      return RSX_ERR_DEVICE;
+    const rsx_image v = view(img);
+    return rsx_phase_one_decompress_corrected(rsx, lo, bytes, implicit_cast<int>(table.size()),
+                                              table.data(), &d, &v, nullptr);
   }
 };
 
