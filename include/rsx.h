@@ -1043,6 +1043,187 @@ int rsx_vc5_decompress(rsx_ctx* ctx, const rsx_vc5_desc* desc, const uint8_t* in
                        const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 4d. DngDecoder behind the tiles: OpcodeList1 and the LinearizationTable   */
+/*    replaces, in DngDecoder::handleMetadata (decoders/DngDecoder.cpp       */
+/*    :591-615), DngOpcodes::applyOpCodes (common/DngOpcodes.cpp) and        */
+/*    RawImageData::sixteenBitLookup() -> RawImageDataU16::doLookup          */
+/*    (common/RawImageDataU16.cpp:488-519).  Every opcode the reference      */
+/*    implements reads and writes only the sample it stands on, so the list  */
+/*    and the look-up are ONE pass on the device.                            */
+/*    The caller hands over the OpcodeList1 entry's bytes as they are in the */
+/*    file (big-endian; NULL / 0 bytes: none, as for an entry of count 0),   */
+/*    the LinearizationTable's values (1..65536; NULL / 0: none -- also what */
+/*    a caller with uncorrectedRawValues passes), the UNCROPPED image (uint16 */
+/*    or, is_f32, binary32) and the image's crop in pixels as it stands      */
+/*    behind handleMetadata's ActiveArea and DefaultCrop subFrames.          */
+/*    The list is parsed here, with the reference's checks in its order.     */
+/*    What a check throws decides the outcome: DngDecoder catches only       */
+/*    RawDecoderException around the list (:593-604), logs it and goes on to */
+/*    the look-up; an IOException of the ByteStream fails the file.          */
+/*    IOException -> the call returns RSX_ERR_IO, nothing is applied, the    */
+/*    image is untouched: the list shorter than its count field; in the      */
+/*    first walk over the list an opcode header or an opcode's size that     */
+/*    leaves the list (skipBytes); any getU32 / getU16 / get<float> /        */
+/*    get<double> of an opcode that leaves the opcode's own bytes (getStream */
+/*    gave it exactly `size`); FixBadPixelsList's skipBytes(points, 8) and   */
+/*    skipBytes(rects, 16); MapPolynomial's check(8 (degree + 1));           */
+/*    Delta / Scale's check(count, 4).                                       */
+/*    RawDecoderException while the list is CONSTRUCTED -> RSX_OK, the       */
+/*    result's list_status = RSX_ERR_INVALID_ARG with a reason, n_applied =  */
+/*    0: a rectangle not inside the crop the opcode meets, or bottom < top,  */
+/*    right < left (REASON_ROI; TrimBounds, every pixel opcode, the          */
+/*    rectangles of FixBadPixelsList against the uncropped image); planes == */
+/*    0 or firstPlane + planes > cpp (REASON_PLANES); a pitch of 0 or above  */
+/*    the ROI's extent (REASON_PITCH); MapTable with 0 or more than 65536    */
+/*    entries (REASON_TABLE_SIZE); MapPolynomial of degree above 8           */
+/*    (REASON_POLY_DEGREE); a delta count other than ceil(extent / pitch)    */
+/*    (REASON_DELTA_COUNT); a non-finite delta (REASON_DELTA_NOT_FINITE); a  */
+/*    point of FixBadPixelsList outside the uncropped image                  */
+/*    (REASON_BAD_POINT); a code of 0 or above 13 (REASON_UNKNOWN_OPCODE);   */
+/*    WarpRectilinear, WarpFisheye, FixVignetteRadial or GainMap (1, 2, 3,   */
+/*    9) without flag bit 0 (REASON_UNSUPPORTED_OPCODE); bytes of an opcode  */
+/*    left unread (REASON_INCONSISTENT_LENGTH -- which is also what an       */
+/*    OPTIONAL opcode 1, 2, 3 or 9 gets unless it is empty: the reference    */
+/*    skips its constructor, not its bytes).                                 */
+/*    RawDecoderException from an opcode's setup() or apply() -> RSX_OK,     */
+/*    list_status = RSX_ERR_INVALID_ARG, n_applied = the number of list      */
+/*    entries in front of it, and those STAY applied: MapTable,              */
+/*    MapPolynomial or FixBadPixelsConstant on an F32 image                  */
+/*    (REASON_SETUP_NOT_U16); FixBadPixelsConstant with cpp > 1              */
+/*    (REASON_SETUP_CPP); on a uint16 image an offset with |f| > 1.0 or a    */
+/*    scale outside 0 .. (2^31 - 513) / 65535 / 1024 (REASON_SETUP_DELTA_    */
+/*    RANGE); a TrimBounds of no area (REASON_TRIM_EMPTY: subFrame's "No     */
+/*    positive crop area").                                                  */
+/*    Either way the look-up follows.                                        */
+/*    The opcodes.  ROI (top, left, bottom, right), firstPlane, planes,      */
+/*    rowPitch, colPitch; PixelOpcode::applyOP (:391-407) touches row crop.y */
+/*    + top + rowPitch y, sample firstPlane + (left + colPitch x) cpp + p of */
+/*    the cropped row, y < ceil(height / rowPitch), x < ceil(width /         */
+/*    colPitch), p < planes; the delta index is x or y.  MapTable (7): the   */
+/*    table, filled up with its last entry.  MapPolynomial (8): a table of   */
+/*    uint16(clamp(sum_j c_j pow(i / 65536.0, j) 65535.5, 0, 65535)) in      */
+/*    binary64 (a NaN gives 0 here; the reference's conversion is            */
+/*    undefined).  DeltaPerRow / Column (10, 11): uint16 clampBits(int(      */
+/*    65535.0F f) + v, 16); F32 f + v.  ScalePerRow / Column (12, 13):       */
+/*    uint16 clampBits((int(1024.0F f) v + 512) >> 10, 16); F32 f v.         */
+/*    FixBadPixelsConstant (4) changes no pixel: every pixel of the crop it  */
+/*    meets whose value equals the constant is listed as (crop.x | crop.y << */
+/*    16) + (row << 16 | col), row-major.  TrimBounds (6) moves the crop for */
+/*    every later opcode; the result carries the crop behind the applied     */
+/*    part of the list, for the caller's subFrame.  FixBadPixelsList (5):    */
+/*    y << 16 | x of its points and of every pixel of its rectangles, in     */
+/*    uncropped coordinates.                                                 */
+/*    The bad-pixel positions: what mRaw->mBadPixelPositions gains, in the   */
+/*    reference's final order -- FixBadPixelsConstant appends, FixBadPixels- */
+/*    List inserts its entries at the FRONT, in file order.  result->n_bad   */
+/*    is always the exact count; when it exceeds bad_cap the image is still  */
+/*    complete and correct, the call reports RSX_ERR_UNSUPPORTED and the     */
+/*    list's contents are unspecified (rsx_panasonic_v4_decompress's         */
+/*    contract).  `bad` NULL with bad_cap 0 is allowed.                      */
+/*    The look-up.  The table is TableLookUp::setTable with dither (common/  */
+/*    TableLookUp.cpp:68-84): base = clampBits(center - (upper - lower + 2)  */
+/*    / 4, 16), delta = upper - lower with lower / upper clamped against the */
+/*    centre; behind the table its last value, delta 0.  doLookup differs    */
+/*    from the store-time look-up of sections 3i and 3m: per row v = (dim_x  */
+/*    + 13 y) ^ 0x45694584, per sample FIRST v = 15700 (v & 65535) + (v >>   */
+/*    16), then pixel = clampBits(base + ((delta (v & 2047) + 1024) >> 12),  */
+/*    16).  It covers EVERY row of the UNCROPPED image at the full uncropped */
+/*    width x cpp, whatever the crop: sixteenBitLookup passes cropped = true */
+/*    to startWorker, but APPLY_LOOKUP carries RawImageWorkerTask::          */
+/*    FULL_IMAGE (common/RawImage.h:61, RawImage.cpp:270-279), and doLookup  */
+/*    indexes the uncropped array.  Neither ActiveArea nor a TrimBounds      */
+/*    keeps a row or a column out of it.                                     */
+/*    rsx_dng_post_validate, in this order: desc or img NULL; cpp outside    */
+/*    1..4, dim_x or dim_y <= 0; pitch_bytes < dim_x cpp (2 or 4) or not a   */
+/*    multiple of the sample size; a crop of no area or outside the image;   */
+/*    opcodes NULL with opcodes_bytes != 0, table NULL with table_count !=   */
+/*    0, table_count > 65536 -> RSX_ERR_INVALID_ARG; a table on an F32 image */
+/*    (the reference logs "not implemented" from a worker), dim_x cpp or     */
+/*    dim_y >= 2^24, dim_x + 13 dim_y >= 2^20 -> RSX_ERR_UNSUPPORTED; then   */
+/*    the list: RSX_ERR_IO as above; more than 2^26 FixBadPixelsList         */
+/*    positions, more than 16 tables, more than RSX_DNG_POST_MAX_PIXEL_OPS   */
+/*    pixel opcodes (4, 7, 8, 10..13) in the applied part ->                 */
+/*    RSX_ERR_UNSUPPORTED (the caller keeps the host path).  It fills the    */
+/*    result and hands out the positions that need no pixel (FixBadPixels-   */
+/*    List); no device.                                                      */
+/*    On any status but RSX_OK (and RSX_ERR_UNSUPPORTED for bad_cap) the     */
+/*    image is untouched.  Pitch padding is never written.                   */
+/*    rsx_dng_post works in place; img->data may be a host pointer (the rows */
+/*    go up, are processed and come back) or a device pointer (the call      */
+/*    returns when the pass is done).  Through host pointers the pass costs  */
+/*    a round trip over the link; deflate and VC-5 images, whose host calls  */
+/*    download their tiles, use it on a device pointer or as a plan behind   */
+/*    their own plans.                                                       */
+/* ------------------------------------------------------------------------ */
+#define RSX_DNG_POST_MAX_PIXEL_OPS 16
+typedef enum rsx_dng_post_reason {
+  RSX_DNG_POST_REASON_NONE = 0,
+  RSX_DNG_POST_REASON_ROI = 1,
+  RSX_DNG_POST_REASON_PLANES = 2,
+  RSX_DNG_POST_REASON_PITCH = 3,
+  RSX_DNG_POST_REASON_DELTA_COUNT = 4,
+  RSX_DNG_POST_REASON_DELTA_NOT_FINITE = 5,
+  RSX_DNG_POST_REASON_TABLE_SIZE = 6,
+  RSX_DNG_POST_REASON_POLY_DEGREE = 7,
+  RSX_DNG_POST_REASON_UNKNOWN_OPCODE = 8,
+  RSX_DNG_POST_REASON_UNSUPPORTED_OPCODE = 9,
+  RSX_DNG_POST_REASON_INCONSISTENT_LENGTH = 10,
+  RSX_DNG_POST_REASON_BAD_POINT = 11,
+  RSX_DNG_POST_REASON_SETUP_NOT_U16 = 12,
+  RSX_DNG_POST_REASON_SETUP_CPP = 13,
+  RSX_DNG_POST_REASON_SETUP_DELTA_RANGE = 14,
+  RSX_DNG_POST_REASON_TRIM_EMPTY = 15
+} rsx_dng_post_reason;
+
+typedef struct rsx_dng_post_desc {
+  const uint8_t* opcodes; /* the OpcodeList1 entry's bytes */
+  uint32_t opcodes_bytes;
+  uint32_t table_count;   /* LinearizationTable entries */
+  const uint16_t* table;
+  int32_t is_f32;         /* RawImageType::F32 */
+  int32_t crop_x, crop_y, crop_w, crop_h; /* mOffset and dim, pixels */
+  int32_t reserved;
+} rsx_dng_post_desc;
+
+typedef struct rsx_dng_post_result {
+  int32_t list_status; /* RSX_OK, or RSX_ERR_INVALID_ARG: the reference logs it and goes on */
+  int32_t list_reason; /* rsx_dng_post_reason */
+  int32_t n_opcodes;   /* entries of a list that constructed */
+  int32_t n_applied;   /* entries applied */
+  int32_t crop_x, crop_y, crop_w, crop_h; /* behind the applied TrimBounds */
+  uint64_t n_bad;
+} rsx_dng_post_result;
+
+int rsx_dng_post_validate(const rsx_dng_post_desc* desc, const rsx_image* img,
+                          rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap);
+int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                 rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap);
+/* The tile fan-outs of section 4 with the pass on the decoded image on the device and ONE
+ * download -- the form the pass is for.  The tiles, any number of them, must tile the image: each
+ * inside it, no two sharing a sample, all of it covered (RSX_ERR_UNSUPPORTED otherwise, before
+ * anything is uploaded or decoded).  tile_status (and tile_consumed) are written only by a call
+ * that wrote the image -- RSX_OK, RSX_ERR_TILE_ERRORS, or RSX_ERR_UNSUPPORTED for a position
+ * list past bad_cap; with any other status nothing was downloaded and they are as the caller
+ * set them, so a caller falls back to the plain call on anything but RSX_OK and
+ * RSX_ERR_TILE_ERRORS.  If any tile fails the call behaves exactly like the plain call:
+ * the good tiles are written, it returns the plain call's status, NOTHING of the list or the
+ * look-up is applied and the result carries the parse alone; the caller's CPU path, list
+ * included, takes over as it does for the plain call.  A list that fails the file (RSX_ERR_IO)
+ * or that this core refuses is returned before anything is decoded.  The uncompressed form also
+ * refuses (RSX_ERR_UNSUPPORTED, nothing written) packed tiles with crop_x != 0: the reference's
+ * packed paths write them from column 0, on top of their neighbours, and only the plain call
+ * keeps the order in which they land. */
+int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles, const rsx_dng_ljpeg_tile* tiles,
+                                  const rsx_dng_post_desc* desc, const rsx_image* img,
+                                  int32_t* tile_status, uint32_t* tile_consumed,
+                                  rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap);
+int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
+                                         const rsx_dng_unpack_tile* tiles,
+                                         const rsx_dng_post_desc* desc, const rsx_image* img,
+                                         int32_t* tile_status, rsx_dng_post_result* result,
+                                         uint32_t* bad, uint32_t bad_cap);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */
@@ -1226,6 +1407,23 @@ typedef struct rsx_iiq_correct_job {
   rsx_image img; /* .data ignored */
 } rsx_iiq_correct_job;
 
+/* one image's opcode list and look-up (section 4d), in place: the pass reads and writes the plan's
+ * OUTPUT buffer (rsx_plan_run's in_dev is ignored and may equal out_dev), so a caller runs its
+ * decode plan and then this one on the same buffer and stream.  Jobs of different geometry, lists
+ * and tables, uint16 and F32, may share a plan; img_offset a multiple of the sample size.  The
+ * list and the table are parsed and copied at plan creation.  Because the work is in place a plan
+ * never runs a part of its jobs: a job that rsx_dng_post_validate refuses (RSX_ERR_IO included)
+ * fails the creation with that status.  The plan owns min(bad_cap, pixels the job's
+ * FixBadPixelsConstant opcodes look at) hit entries per job; a job whose hits exceed them reports
+ * RSX_ERR_UNSUPPORTED in rsx_plan_results, its image is complete. */
+typedef struct rsx_dng_post_job {
+  rsx_dng_post_desc desc;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+  uint32_t bad_cap;
+  uint32_t reserved;
+} rsx_dng_post_job;
+
 /* one VC-5 tile (section 4c): band offsets count from in_offset; the code book and the log table
  * are copied at plan creation.  Jobs of different geometry, book and table may share a plan; any
  * in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset.  The band decode loads a
@@ -1301,6 +1499,15 @@ int rsx_dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_
 int rsx_vc5_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_vc5_job* jobs, rsx_plan** out_plan);
 int rsx_iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job* jobs,
                                 rsx_plan** out_plan);
+int rsx_dng_post_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_post_job* jobs,
+                             rsx_plan** out_plan);
+/* DNG post plans: the verdict, the crop and the count of job `job` (any time after creation;
+ * n_bad counts the FixBadPixelsConstant hits of the last run once rsx_plan_results has run), and,
+ * after rsx_plan_results, its bad-pixel positions in the reference's order with the contract of
+ * rsx_panasonic_v4_plan_bad_pixels. */
+int rsx_dng_post_plan_result(rsx_plan* plan, int job, rsx_dng_post_result* out);
+int rsx_dng_post_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
+                                 uint64_t* n_bad);
 /* After rsx_plan_results of a VC-5 plan: per band of job `job` ([channel][subband], 40 entries
  * each; any may be NULL) its status, and for the high-pass bands the 128-Kbit windows the band
  * decode walked and the parse rounds it took over all of them (a round is one parse of every

@@ -351,6 +351,60 @@ def iiq_corr(ops, cfa=None, n_ops=None):
     return d, keep
 
 
+RSX_DNG_POST_MAX_PIXEL_OPS = 16
+(DNG_POST_REASON_NONE, DNG_POST_REASON_ROI, DNG_POST_REASON_PLANES, DNG_POST_REASON_PITCH,
+ DNG_POST_REASON_DELTA_COUNT, DNG_POST_REASON_DELTA_NOT_FINITE, DNG_POST_REASON_TABLE_SIZE,
+ DNG_POST_REASON_POLY_DEGREE, DNG_POST_REASON_UNKNOWN_OPCODE, DNG_POST_REASON_UNSUPPORTED_OPCODE,
+ DNG_POST_REASON_INCONSISTENT_LENGTH, DNG_POST_REASON_BAD_POINT, DNG_POST_REASON_SETUP_NOT_U16,
+ DNG_POST_REASON_SETUP_CPP, DNG_POST_REASON_SETUP_DELTA_RANGE,
+ DNG_POST_REASON_TRIM_EMPTY) = range(16)
+
+
+class DngPostDesc(C.Structure):
+    _fields_ = [("opcodes", C.c_void_p), ("opcodes_bytes", C.c_uint32),
+                ("table_count", C.c_uint32), ("table", C.c_void_p), ("is_f32", C.c_int32),
+                ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_w", C.c_int32),
+                ("crop_h", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DngPostResult(C.Structure):
+    _fields_ = [("list_status", C.c_int32), ("list_reason", C.c_int32),
+                ("n_opcodes", C.c_int32), ("n_applied", C.c_int32), ("crop_x", C.c_int32),
+                ("crop_y", C.c_int32), ("crop_w", C.c_int32), ("crop_h", C.c_int32),
+                ("n_bad", C.c_uint64)]
+
+    def crop(self):
+        return (self.crop_x, self.crop_y, self.crop_w, self.crop_h)
+
+
+class DngPostJob(C.Structure):
+    _fields_ = [("desc", DngPostDesc), ("img_offset", C.c_uint64), ("img", Image),
+                ("bad_cap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def dng_post_desc(opcodes, table, crop, is_f32=False, opcodes_bytes=None, table_count=None):
+    """(rsx_dng_post_desc, keep-alive objects).  opcodes: the OpcodeList1 entry's bytes or None;
+    table: the LinearizationTable's values or None; crop: (x, y, w, h) in pixels.  opcodes_bytes /
+    table_count override the sizes (a NULL pointer with a size)."""
+    d = DngPostDesc()
+    keep = []
+    if opcodes is not None and len(opcodes):
+        a = np.frombuffer(bytes(opcodes), dtype=np.uint8).copy()
+        d.opcodes, d.opcodes_bytes = a.ctypes.data, a.size
+        keep.append(a)
+    if table is not None and len(table):
+        t = np.ascontiguousarray(table, dtype=np.uint16)
+        d.table, d.table_count = t.ctypes.data, t.size
+        keep.append(t)
+    if opcodes_bytes is not None:
+        d.opcodes_bytes = opcodes_bytes
+    if table_count is not None:
+        d.table_count = table_count
+    d.is_f32 = 1 if is_f32 else 0
+    d.crop_x, d.crop_y, d.crop_w, d.crop_h = crop
+    return d, keep
+
+
 class PanasonicDesc(C.Structure):
     _fields_ = [("version", C.c_int32), ("bps", C.c_int32)]
 

@@ -40,6 +40,9 @@ EXPORTS = [
     "rsx_vc5_validate", "rsx_vc5_decompress", "rsx_vc5_plan_create", "rsx_vc5_plan_bands",
     "rsx_iiq_correct_validate", "rsx_iiq_correct", "rsx_phase_one_decompress_corrected",
     "rsx_iiq_correct_plan_create",
+    "rsx_dng_post_validate", "rsx_dng_post", "rsx_dng_decompress_ljpeg_post",
+    "rsx_dng_decompress_uncompressed_post", "rsx_dng_post_plan_create",
+    "rsx_dng_post_plan_result", "rsx_dng_post_plan_bad_pixels",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
@@ -126,6 +129,19 @@ def lib():
         L.rsx_phase_one_decompress_corrected.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                          C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p]
+        L.rsx_dng_post_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint32]
+        L.rsx_dng_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_uint32]
+        L.rsx_dng_decompress_ljpeg_post.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rsx_dng_decompress_uncompressed_post.argtypes = [C.c_void_p, C.c_int, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rsx_dng_post_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_dng_post_plan_bad_pixels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
+                                                   C.c_void_p]
         L.rsx_vc5_plan_bands.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -156,7 +172,8 @@ def lib():
                      "rsx_sony_arw2_plan_create", "rsx_panasonic_plan_create",
                      "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
                      "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
-                     "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create"):
+                     "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
+                     "rsx_dng_post_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -226,6 +243,24 @@ def iiq_correct_validate(corr, img_view):
     """rsx_iiq_correct_validate; corr: abi.IiqCorr (abi.iiq_corr), None passes a NULL list"""
     return lib().rsx_iiq_correct_validate(None if corr is None else C.byref(corr),
                                           C.byref(img_view))
+
+
+def _bad_out(result, buf, st):
+    """the positions a call handed out: None when the list did not fit (or the call failed)"""
+    if st != abi.RSX_OK:
+        return None
+    return [int(v) for v in buf[:result.n_bad]]
+
+
+def dng_post_validate(desc, img_view, bad_cap=1 << 16):
+    """rsx_dng_post_validate; desc: abi.DngPostDesc (abi.dng_post_desc), None passes NULL.
+    Returns (status, abi.DngPostResult, host-side positions or None)."""
+    r = abi.DngPostResult()
+    buf = (C.c_uint32 * max(1, bad_cap))()
+    st = lib().rsx_dng_post_validate(None if desc is None else C.byref(desc),
+                                     None if img_view is None else C.byref(img_view),
+                                     C.byref(r), buf, bad_cap)
+    return st, r, _bad_out(r, buf, st)
 
 
 def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
@@ -415,6 +450,43 @@ class Context:
                                                       arr, C.byref(corr), C.byref(img_view), rows)
         return st, list(rows)[:img_view.dim_y]
 
+    def dng_post(self, desc, img_view, bad_cap=1 << 16):
+        """desc: abi.DngPostDesc; img_view.data a host or a device pointer; in place.  Returns
+        (status, abi.DngPostResult, positions or None)."""
+        r = abi.DngPostResult()
+        buf = (C.c_uint32 * max(1, bad_cap))()
+        st = lib().rsx_dng_post(self._h, C.byref(desc), C.byref(img_view), C.byref(r), buf, bad_cap)
+        return st, r, _bad_out(r, buf, st)
+
+    def _dng_post_call(self, fn, tile_type, descs, datas, desc, img_view, bad_cap, consumed):
+        n = len(descs)
+        arrs = [_u8(d) for d in datas]
+        tiles = (tile_type * n)()
+        for i in range(n):
+            tiles[i].desc = descs[i]
+            tiles[i].in_ = arrs[i].ctypes.data
+            tiles[i].in_bytes = arrs[i].size
+        # (-1: the call did not write the statuses -- it returned without writing the image)
+        st = (C.c_int32 * n)(*([-1] * n))
+        r = abi.DngPostResult()
+        buf = (C.c_uint32 * max(1, bad_cap))()
+        args = [self._h, n, tiles, C.byref(desc), C.byref(img_view), st]
+        if consumed:
+            args.append(None)
+        rc = fn(*args, C.byref(r), buf, bad_cap)
+        return rc, list(st), r, _bad_out(r, buf, rc)
+
+    def dng_decompress_ljpeg_post(self, descs, datas, desc, img_view, bad_cap=1 << 16):
+        """dng_decompress_ljpeg, then the list and the look-up of `desc` (abi.DngPostDesc) on the
+        device, one download.  Returns (status, tile statuses, result, positions or None)."""
+        return self._dng_post_call(lib().rsx_dng_decompress_ljpeg_post, abi.DngLJpegTile, descs,
+                                   datas, desc, img_view, bad_cap, True)
+
+    def dng_decompress_uncompressed_post(self, descs, datas, desc, img_view, bad_cap=1 << 16):
+        """dng_decompress_uncompressed, then the list and the look-up on the device, one download"""
+        return self._dng_post_call(lib().rsx_dng_decompress_uncompressed_post, abi.DngUnpackTile,
+                                   descs, datas, desc, img_view, bad_cap, False)
+
     def sony_arw2_decompress(self, mode, table, data, img_view, rows=True):
         """Returns (status, per-row statuses or None)."""
         a = _u8(data)
@@ -543,6 +615,11 @@ class Context:
         place on the output buffer"""
         return Plan(self, "rsx_iiq_correct_plan_create", abi.IiqCorrectJob, jobs)
 
+    def dng_post_plan(self, jobs):
+        """jobs: abi.DngPostJob (lists and tables are parsed and copied at plan creation); runs in
+        place on the output buffer"""
+        return DngPostPlan(self, "rsx_dng_post_plan_create", abi.DngPostJob, jobs)
+
     def sony_arw2_plan(self, jobs):
         """jobs: abi.SonyArw2Job (their tables are copied at plan creation)"""
         return Plan(self, "rsx_sony_arw2_plan_create", abi.SonyArw2Job, jobs)
@@ -638,6 +715,20 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class DngPostPlan(Plan):
+    def result(self, job):
+        r = abi.DngPostResult()
+        st = lib().rsx_dng_post_plan_result(self._h, job, C.byref(r))
+        return st, r
+
+    def bad_pixels(self, job, cap):
+        """(status, exact count, positions or None) of job `job` behind results()"""
+        buf = (C.c_uint32 * max(1, cap))()
+        n = C.c_uint64(0)
+        st = lib().rsx_dng_post_plan_bad_pixels(self._h, job, buf if cap else None, cap, C.byref(n))
+        return st, n.value, ([int(v) for v in buf[:n.value]] if st == abi.RSX_OK else None)
 
 
 class PanasonicV4Plan(Plan):

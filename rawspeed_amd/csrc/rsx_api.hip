@@ -17,8 +17,10 @@
 #include "rsx_nikon_snef.h"
 #include "rsx_vc5.h"
 #include "rsx_iiq_corr.h"
+#include "rsx_dng_post.h"
 
 #include <algorithm>
+#include <map>
 #include <atomic>
 #include <thread>
 #include <cstring>
@@ -1990,6 +1992,40 @@ namespace {
 struct HostRect {
   size_t row0, rows, byte0, bytes;
 };
+// true iff the rectangles lie inside an image of `rows` rows of `row_bytes` bytes, no two of them
+// share a byte and together they are the whole image -- any number of them: a sweep down the rows
+// over the rectangles that are still open, keyed by their first byte
+bool rects_tile_image(std::vector<HostRect> rects, size_t rows, size_t row_bytes) {
+  unsigned __int128 area = 0;
+  for (const HostRect& r : rects) {
+    if (r.rows == 0 || r.bytes == 0 || r.row0 >= rows || r.rows > rows - r.row0 ||
+        r.byte0 >= row_bytes || r.bytes > row_bytes - r.byte0)
+      return false;
+    area += (unsigned __int128)r.rows * r.bytes;
+  }
+  if (area != (unsigned __int128)rows * row_bytes)
+    return false;
+  std::sort(rects.begin(), rects.end(), [](const HostRect& a, const HostRect& b) {
+    return a.row0 != b.row0 ? a.row0 < b.row0 : a.byte0 < b.byte0;
+  });
+  std::map<size_t, std::pair<size_t, size_t>> open; // byte0 -> (byte end, row end)
+  for (const HostRect& r : rects) {
+    auto it = open.lower_bound(r.byte0);
+    if (it != open.begin())
+      --it;
+    while (it != open.end() && it->first < r.byte0 + r.bytes) {
+      if (it->second.first > r.byte0) {
+        if (it->second.second > r.row0)
+          return false; // (two rectangles share a byte)
+        it = open.erase(it);
+      } else {
+        ++it;
+      }
+    }
+    open[r.byte0] = {r.byte0 + r.bytes, r.row0 + r.rows};
+  }
+  return true; // (inside, disjoint, and the areas add up to the image)
+}
 HostRect out_rect(const rsx_ljpeg_job& j) {
   return {size_t(j.desc.tile_y), size_t(j.desc.tile_h),
           size_t(j.desc.tile_x) * j.img.cpp * 2, size_t(j.desc.tile_w) * j.img.cpp * 2};
@@ -2248,11 +2284,19 @@ int ljpeg_chunked_host(rsx_ctx* ctx, rsx_ctx::HostLane* L, rsx_plan* plan, size_
   return rc;
 }
 
+// before_download (may be NULL): what a call does to the decoded image on the device in front of
+// the download (the DNG opcode list and look-up), given the address row 0 of the image has and
+// the stream.  The jobs' rectangles must tile the whole image (rects_tile_image, any number of
+// them): a call whose jobs do not returns RSX_ERR_UNSUPPORTED before anything is uploaded or
+// decoded, statuses untouched.  It runs only when every job decoded, and the whole image then goes
+// back as one rectangle.  With a failing job the call is the plain call.
+typedef std::function<int(uint8_t*, hipStream_t)> DevicePostFn;
+
 template <typename JobT>
 int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
                       const uint8_t* const* ins, const rsx_image* img,
                       PlanCreateFn<JobT> create, int32_t* statuses, uint32_t* consumed,
-                      bool count_call = true) {
+                      bool count_call = true, const DevicePostFn* before_download = nullptr) {
   if (count_call)
     ++ctx->host_calls;
 #ifdef RSX_FORCE_UNSUPPORTED
@@ -2274,6 +2318,14 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
     in_total += align_up(size_t(jobs[i].in_bytes) + 64, 16);
     jobs[i].img = *img;
     jobs[i].img_offset = 0;
+  }
+  if (before_download) {
+    std::vector<HostRect> all(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i)
+      all[size_t(i)] = out_rect(jobs[i]);
+    if (img->cpp < 1 || !rects_tile_image(std::move(all), size_t(img->dim_y),
+                                          size_t(img->dim_x) * size_t(img->cpp) * 2))
+      return RSX_ERR_UNSUPPORTED;
   }
   // the output staging holds the image ROWS the jobs write (a DNG tile call: the tile's
   // rows, not the image); the kernels get the address row 0 would have
@@ -2307,7 +2359,7 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
   // ONE large stream of the single-pass kernel whose plan the lane holds (a frame decoded
   // again: a burst, a folder of one camera's files): in chunks -- see ljpeg_chunked_host.
   rsx_plan* const held = lane.lane->holds_plan(key) ? lane.lane->cached_plan : nullptr;
-  if (n == 1 && ctx->host_overlap && jobs[0].in_bytes >= (size_t(8) << 20) && held &&
+  if (n == 1 && !before_download && ctx->host_overlap && jobs[0].in_bytes >= (size_t(8) << 20) && held &&
       !held->timing && ljpeg_of(held) && ljpeg_plan_chunkable(ljpeg_of(held))) {
     int32_t st1 = RSX_OK;
     uint32_t cons1 = 0;
@@ -2361,6 +2413,7 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
     if (st[i] == RSX_OK)
       rects.push_back(out_rect(jobs[i]));
   }
+  const bool all_decoded = rects.size() == size_t(n);
   // Tiles that together fill their bounding box (the rule: every tile of a DNG decoded)
   // go back as ONE rectangle -- a pageable 2D copy per tile cost 2 ms more on the four
   // tiles of an 8192x5464 frame than the copy of the whole frame.
@@ -2383,6 +2436,12 @@ int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
       }
     if (disjoint && rects.size() <= 64 && area == (r1 - r0) * (b1 - b0))
       rects.assign(1, HostRect{r0, r1 - r0, b0, b1 - b0});
+  }
+  if (before_download && all_decoded) {
+    if (int e = (*before_download)(out_row0, s))
+      return e;
+    // (the jobs tile the image, checked on the way in: one rectangle, however many tiles)
+    rects.assign(1, HostRect{0, size_t(img->dim_y), 0, size_t(img->dim_x) * size_t(img->cpp) * 2});
   }
   // Back into the caller's image: rectangles on the 16-byte grid straight, everything ragged
   // (3-sample pixels, odd widths, tiles of unequal heights) through the lane's page-locked
@@ -2881,6 +2940,274 @@ extern "C" int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* i
       return st;
   return phase_one_host(ctx, in, n_strips, strips, img, strip_status,
                         [&](void* dev, hipStream_t s) { return call.plan ? call.run(dev, s) : int(RSX_OK); });
+}
+
+// ---------------------------------------------------------------------------
+// DngDecoder behind the tiles: OpcodeList1 and the LinearizationTable look-up
+// ---------------------------------------------------------------------------
+extern "C" int rsx_dng_post_validate(const rsx_dng_post_desc* desc, const rsx_image* img,
+                                     rsx_dng_post_result* result, uint32_t* bad,
+                                     uint32_t bad_cap) {
+  return dng_post_validate(desc, img, result, bad, bad_cap);
+}
+
+extern "C" int rsx_dng_post_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_post_job* jobs,
+                                        rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, dng_post_plan_create);
+}
+
+extern "C" int rsx_dng_post_plan_result(rsx_plan* plan, int job, rsx_dng_post_result* out) {
+  if (!plan || plan->kind != PLAN_DECODER)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
+  return plan->dec->dng_post_result(job, out);
+}
+
+extern "C" int rsx_dng_post_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
+                                            uint64_t* n_bad) {
+  if (n_bad)
+    *n_bad = 0;
+  if (!plan || plan->kind != PLAN_DECODER)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
+  return plan->dec->bad_pixels(job, out, cap, n_bad);
+}
+
+namespace {
+// the one-job plan of a host call: made for the call, not kept in a lane (its key would be the
+// list, up to 16 tables and the look-up table)
+struct DngPostCall {
+  rsx_plan* plan = nullptr;
+  ~DngPostCall() { rsx_plan_destroy(plan); }
+  int create(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img, uint32_t bad_cap) {
+    rsx_dng_post_job job{};
+    job.desc = *desc;
+    job.img = *img;
+    job.img.data = nullptr;
+    job.bad_cap = bad_cap;
+    return rsx_dng_post_plan_create(ctx, 1, &job, &plan);
+  }
+  // in place on `dev`; returns when the pass is done.  A hit list past its capacity is no
+  // failure of the pass: finish() reports it.
+  int run(void* dev, hipStream_t s) {
+    if (int st = rsx_plan_run(plan, dev, dev, s))
+      return st;
+    const int st = rsx_plan_results(plan, nullptr, nullptr);
+    return st == RSX_ERR_UNSUPPORTED ? int(RSX_OK) : st;
+  }
+  // the result and the positions behind run(); without a run (a failing tile) the parse's result
+  int finish(rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap, bool ran) {
+    if (result)
+      plan->dec->dng_post_result(0, result);
+    if (!ran)
+      return RSX_OK;
+    uint64_t n = 0;
+    return plan->dec->bad_pixels(0, bad, bad_cap, &n);
+  }
+};
+} // namespace
+
+// In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
+// work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
+// and come back through download_rects.
+extern "C" int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                            rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap) {
+  if (!ctx || !desc || !img || !img->data || (!bad && bad_cap != 0))
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  DngPostCall call;
+  if (int st = call.create(ctx, desc, img, bad_cap))
+    return st;
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof attr);
+  bool on_device = false;
+  if (hipPointerGetAttributes(&attr, img->data) == hipSuccess)
+    on_device = attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+  else
+    (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
+  if (on_device) {
+    if (int st = call.run(img->data, nullptr))
+      return st;
+    return call.finish(result, bad, bad_cap, true);
+  }
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t row_bytes = size_t(img->dim_x) * size_t(img->cpp) * (desc->is_f32 ? 4 : 2);
+  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
+  if (int e = lane.lane->d_out.ensure(bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice, s));
+  }
+  if (int st = call.run(lane.lane->d_out.ptr, s))
+    return st;
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
+              size_t(img->dim_y)};
+  {
+    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+    if (int e = download_rects(ctx, lane.lane, s, &dr, 1))
+      return e;
+  }
+  return call.finish(result, bad, bad_cap, true);
+}
+
+// rsx_dng_decompress_ljpeg, the list and the look-up on the decoded image on the device, ONE
+// download.  The tiles go up as one call (no bands: the pass needs the whole image).
+extern "C" int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles,
+                                             const rsx_dng_ljpeg_tile* tiles,
+                                             const rsx_dng_post_desc* desc, const rsx_image* img,
+                                             int32_t* tile_status, uint32_t* tile_consumed,
+                                             rsx_dng_post_result* result, uint32_t* bad,
+                                             uint32_t bad_cap) {
+  if (!ctx || !tiles || n_tiles < 1 || !desc || !img || !img->data || (!bad && bad_cap != 0))
+    return RSX_ERR_INVALID_ARG;
+  if (desc->is_f32)
+    return RSX_ERR_INVALID_ARG; // (LJPEG tiles decode to uint16)
+  DngPostCall call;
+  if (int st = call.create(ctx, desc, img, bad_cap))
+    return st;
+  std::vector<rsx_ljpeg_job> jobs(n_tiles);
+  std::vector<const uint8_t*> ins(n_tiles);
+  for (int i = 0; i < n_tiles; ++i) {
+    jobs[i].desc = tiles[i].desc;
+    jobs[i].in_bytes = tiles[i].in_bytes;
+    ins[i] = tiles[i].in;
+  }
+  constexpr int32_t ST_UNSET = INT32_MIN;
+  std::vector<int32_t> st(n_tiles, ST_UNSET);
+  std::vector<uint32_t> cons(n_tiles, 0);
+  bool ran = false;
+  const DevicePostFn post = [&](uint8_t* dev, hipStream_t s) {
+    const int e = call.run(dev, s);
+    ran = e == RSX_OK;
+    return e;
+  };
+  const int rc = ljpeg_family_host(ctx, n_tiles, jobs, ins.data(), img, rsx_ljpeg_plan_create,
+                                   st.data(), cons.data(), true, &post);
+  bool tile_failed = false, reached = true;
+  for (int32_t& v : st) {
+    reached = reached && v != ST_UNSET; // (unset: the call came back before its plan's results)
+    tile_failed = tile_failed || (v != RSX_OK && v != ST_UNSET);
+  }
+  // tile_status and tile_consumed are written only by a call that wrote the image: every tile
+  // decoded and the pass ran, or a tile failed and the call was the plain call.  A call that
+  // returns without a download (tiles that do not tile the image, a device failure, a failure
+  // of the pass) leaves them as the caller set them.
+  if (!reached || rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || (rc != RSX_OK && !tile_failed) ||
+      (rc == RSX_OK && !tile_failed && !ran))
+    return rc != RSX_OK ? rc : int(RSX_ERR_DEVICE);
+  if (tile_status)
+    std::copy(st.begin(), st.end(), tile_status);
+  if (tile_consumed)
+    std::copy(cons.begin(), cons.end(), tile_consumed);
+  if (tile_failed) {
+    call.finish(result, nullptr, 0, false);
+    return RSX_ERR_TILE_ERRORS; // (the plain call's verdict; nothing of the list was applied)
+  }
+  return call.finish(result, bad, bad_cap, true);
+}
+
+// rsx_dng_decompress_uncompressed, the list and the look-up on the device, ONE download.  The
+// tiles are unpacked into the image's own layout on the device (the plain call keeps a compact
+// rectangle per tile and downloads in bands); tiles that do not all
+// validate make this the plain call (a tile fails: nothing of the list is applied); tiles that do
+// not cover the image are RSX_ERR_UNSUPPORTED, nothing written.
+extern "C" int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
+                                                    const rsx_dng_unpack_tile* tiles,
+                                                    const rsx_dng_post_desc* desc,
+                                                    const rsx_image* img, int32_t* tile_status,
+                                                    rsx_dng_post_result* result, uint32_t* bad,
+                                                    uint32_t bad_cap) {
+  if (!ctx || !tiles || n_tiles < 1 || !desc || !img || !img->data || (!bad && bad_cap != 0))
+    return RSX_ERR_INVALID_ARG;
+  if (desc->is_f32)
+    return RSX_ERR_INVALID_ARG; // (rsx_unpack_f32 images: rsx_dng_post on the result)
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  DngPostCall call;
+  if (int st = call.create(ctx, desc, img, bad_cap))
+    return st;
+  std::vector<rsx_unpack_job> jobs(n_tiles);
+  size_t in_total = 0;
+  std::vector<HostRect> rects(static_cast<size_t>(n_tiles));
+  bool plain = img->pitch_bytes % 2 != 0;
+  for (int i = 0; i < n_tiles && !plain; ++i) {
+    const rsx_unpack_desc& d = tiles[i].desc;
+    if (!tiles[i].in || validate_unpack(d, *img, tiles[i].in_bytes) != RSX_OK) {
+      plain = true;
+      break;
+    }
+    // (a packed tile is written from column 0 whatever its crop_x, as the reference's packed
+    // paths do: tiles side by side land on each other, in the plain call one after the other --
+    // one launch over the image's own layout has no such order)
+    if (d.crop_x != 0 && !(d.bit_order == RSX_ORDER_LSB && d.bits_per_pixel == 16))
+      return RSX_ERR_UNSUPPORTED;
+    jobs[i].desc = d;
+    jobs[i].in_offset = in_total;
+    jobs[i].in_bytes = size_t(d.crop_h) * size_t(d.input_pitch_bytes);
+    jobs[i].img_offset = 0;
+    jobs[i].img = *img;
+    jobs[i].img.data = nullptr;
+    in_total += align_up(size_t(jobs[i].in_bytes), 16);
+    const int64_t rows = std::min<int64_t>(d.crop_h, int64_t(img->dim_y) - d.crop_y);
+    rects[size_t(i)] = HostRect{size_t(d.crop_y), size_t(std::max<int64_t>(rows, 0)),
+                                size_t(d.crop_x) * size_t(img->cpp) * 2,
+                                size_t(d.crop_w) * size_t(img->cpp) * 2};
+  }
+  if (plain) {
+    call.finish(result, nullptr, 0, false);
+    return rsx_dng_decompress_uncompressed(ctx, n_tiles, tiles, img, tile_status);
+  }
+  // (inside the image, disjoint, all of it: the pass needs the whole image, and a byte no tile
+  // wrote would be looked up and downloaded)
+  if (!rects_tile_image(std::move(rects), size_t(img->dim_y),
+                        size_t(img->dim_x) * size_t(img->cpp) * 2))
+    return RSX_ERR_UNSUPPORTED; // (nothing decoded, nothing written, tile_status untouched)
+  ++ctx->host_calls;
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t row_bytes = size_t(img->dim_x) * size_t(img->cpp) * 2;
+  const size_t out_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y);
+  if (int e = lane.lane->d_in.ensure(in_total + 64))
+    return e;
+  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    for (int i = 0; i < n_tiles; ++i)
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(lane.lane->d_in.ptr) + jobs[i].in_offset,
+                                        tiles[i].in, jobs[i].in_bytes, hipMemcpyHostToDevice, s));
+  }
+  rsx_plan* unpack = nullptr;
+  if (int e = rsx_unpack_plan_create(ctx, n_tiles, jobs.data(), &unpack))
+    return e;
+  std::vector<int32_t> st(n_tiles, RSX_OK);
+  int rc = rsx_plan_run(unpack, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
+  if (rc == RSX_OK)
+    rc = rsx_plan_results(unpack, st.data(), nullptr);
+  rsx_plan_destroy(unpack);
+  if (rc != RSX_OK)
+    return rc; // (every tile validated: a device failure; tile_status untouched)
+  if (int e = call.run(lane.lane->d_out.ptr, s))
+    return e;
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
+              size_t(img->dim_y)};
+  {
+    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+    if (int e = download_rects(ctx, lane.lane, s, &dr, 1))
+      return e;
+  }
+  // (tile_status is written only by a call that wrote the image)
+  if (tile_status)
+    std::copy(st.begin(), st.end(), tile_status);
+  return call.finish(result, bad, bad_cap, true);
 }
 
 // ---------------------------------------------------------------------------

@@ -188,6 +188,10 @@ struct DecoderPlan {
   virtual int bad_pixels(int /*job*/, uint32_t* /*out*/, uint32_t /*cap*/, uint64_t* /*n_bad*/) {
     return RSX_ERR_INVALID_ARG;
   }
+  // the verdict, the crop and the position count of job `job` (DNG post plans)
+  virtual int dng_post_result(int /*job*/, rsx_dng_post_result* /*out*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };

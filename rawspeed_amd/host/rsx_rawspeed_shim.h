@@ -29,6 +29,7 @@
 #include "io/IOException.h"
 #include "metadata/ColorFilterArray.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
@@ -270,6 +271,70 @@ inline int samsung_v0(const std::vector<ByteStream>& stripes, const RawImage& im
                                    implicit_cast<int>(offsets.size()), &v, nullptr);
 }
 
+// DngDecoder::decodeRawInternal() / handleMetadata(): what follows the tiles --
+// OpcodeList1 and the LinearizationTable look-up -- handed to the tile fan-out so that it runs on
+// the device in front of the ONE download.  The hunk fills this BEFORE decodeData (the entries,
+// and the crop handleMetadata's ActiveArea / DefaultCrop subFrames will leave), hangs it on the
+// DngBatch, and after the decode calls finish(): the logged error, the list's TrimBounds as a
+// subFrame, the bad-pixel positions.  `applied` false: the device did not run the stage (a failing
+// tile, a list or an image this core refuses) and handleMetadata does what it always did.
+struct DngPost {
+  static constexpr uint32_t MaxConstantHits = 1U << 16; // (real files hold a handful)
+  rsx_dng_post_desc d{};
+  std::vector<uint16_t> table;
+  rsx_dng_post_result result{};
+  std::vector<uint32_t> bad;
+  bool applied = false;
+  // opcodes: the OPCODELIST1 entry's bytes (nullptr: no entry, or one of count 0, or
+  // !applyStage1DngOpcodes); lin: the LINEARIZATIONTABLE (empty: none, or uncorrectedRawValues)
+  // `img`: mRaw with dim and cpp set (no pixel is looked at; createData may still be ahead).  Room
+  // for positions is made only when the list can produce any: what FixBadPixelsList holds, which
+  // rsx_dng_post_validate counts, plus MaxConstantHits when the list is there and the image is
+  // one FixBadPixelsConstant runs on.  A list past that room leaves the stage to the host.
+  void set(const Buffer* opcodes, std::vector<uint16_t> lin, const iRectangle2D& crop,
+           bool is_f32, const RawImage& img) {
+    table = std::move(lin);
+    d.opcodes = opcodes ? opcodes->begin() : nullptr;
+    d.opcodes_bytes = opcodes ? opcodes->getSize() : 0;
+    d.table = table.empty() ? nullptr : table.data();
+    d.table_count = implicit_cast<uint32_t>(table.size());
+    d.is_f32 = is_f32 ? 1 : 0;
+    d.crop_x = crop.pos.x;
+    d.crop_y = crop.pos.y;
+    d.crop_w = crop.dim.x;
+    d.crop_h = crop.dim.y;
+    bad.clear();
+    if (d.opcodes_bytes != 0) {
+      rsx_image v{};
+      v.dim_x = img->dim.x;
+      v.dim_y = img->dim.y;
+      v.cpp = implicit_cast<int32_t>(img->getCpp());
+      v.pitch_bytes = implicit_cast<uint32_t>(v.dim_x) * implicit_cast<uint32_t>(v.cpp) *
+                      (is_f32 ? 4U : 2U);
+      rsx_dng_post_result r{};
+      (void)rsx_dng_post_validate(&d, &v, &r, nullptr, 0); // (the count; no room yet)
+      const uint64_t room = r.n_bad + (!is_f32 && v.cpp == 1 ? MaxConstantHits : 0U);
+      bad.resize(implicit_cast<size_t>(std::min<uint64_t>(room, 1U << 26)));
+    }
+  }
+  bool wanted() const { return d.opcodes_bytes != 0 || d.table_count != 0; }
+  // behind handleMetadata's own subFrames (the image's crop is the one set() was given)
+  void finish(const RawImage& img) const {
+    if (result.list_status != RSX_OK)
+      img->setError("rsx: DNG opcode list refused as the reference's parser refuses it");
+    const iPoint2D off = img->getCropOffset();
+    const iRectangle2D trimmed(result.crop_x - off.x, result.crop_y - off.y, result.crop_w,
+                               result.crop_h);
+    if (!(trimmed.pos == iPoint2D(0, 0)) || !(trimmed.dim == img->dim))
+      img->subFrame(trimmed);
+    if (result.n_bad != 0) {
+      MutexLocker guard(&img->mBadPixelMutex);
+      img->mBadPixelPositions.insert(img->mBadPixelPositions.begin(), bad.begin(),
+                                     bad.begin() + implicit_cast<std::ptrdiff_t>(result.n_bad));
+    }
+  }
+};
+
 // status -> the exception the reference would have thrown
 [[noreturn]] inline void raise(int st) {
   switch (st) {
@@ -343,6 +408,9 @@ public:
   }
 
   bool replaying = false;
+  //  the stage behind the tiles, if DngDecoder hung one here: a batch of one
+  // kind of tiles then takes the _post call -- decode, list, look-up, one download
+  DngPost* post = nullptr;
 
   // true: every recorded tile is done; false: a second (CPU) pass is needed
   bool run(const rsx_image& img) {
@@ -359,11 +427,26 @@ public:
       }
     }
     bool all = true;
+    const bool with_post = post && post->wanted() && (lj.empty() != up.empty()) &&
+                           lj.size() + up.size() == slots.size();
     if (!lj.empty()) {
       std::vector<int32_t> st(lj.size(), RSX_ERR_DEVICE);
       std::vector<uint32_t> cons(lj.size(), 0);
-      (void)rsx_dng_decompress_ljpeg(context(), implicit_cast<int>(lj.size()), lj.data(), &img,
-                                     st.data(), cons.data());
+      int post_rc = RSX_ERR_UNSUPPORTED;
+      if (with_post) {
+        post_rc = rsx_dng_decompress_ljpeg_post(
+            context(), implicit_cast<int>(lj.size()), lj.data(), &post->d, &img, st.data(),
+            cons.data(), &post->result, post->bad.empty() ? nullptr : post->bad.data(),
+            implicit_cast<uint32_t>(post->bad.size()));
+        post->applied = post_rc == RSX_OK;
+      }
+      // Only RSX_OK and RSX_ERR_TILE_ERRORS wrote the image and the statuses (the _post call was
+      // then the whole decode, or the plain call).  Anything else -- a list or tiles the stage
+      // refuses, a device failure, a position list past its room -- gets the plain call now, so
+      // that no tile is ever marked done without its pixels in the caller's image.
+      if (post_rc != RSX_OK && post_rc != RSX_ERR_TILE_ERRORS)
+        (void)rsx_dng_decompress_ljpeg(context(), implicit_cast<int>(lj.size()), lj.data(), &img,
+                                       st.data(), cons.data());
       for (size_t i = 0; i < ljs.size(); ++i) {
         ljs[i]->status = st[i];
         // LJpegDecoder's marker walk went on from the end of the scan (endOfScan()).  A
@@ -381,8 +464,17 @@ public:
     }
     if (!up.empty()) {
       std::vector<int32_t> st(up.size(), RSX_ERR_DEVICE);
-      (void)rsx_dng_decompress_uncompressed(context(), implicit_cast<int>(up.size()), up.data(),
-                                            &img, st.data());
+      int post_rc = RSX_ERR_UNSUPPORTED;
+      if (with_post) {
+        post_rc = rsx_dng_decompress_uncompressed_post(
+            context(), implicit_cast<int>(up.size()), up.data(), &post->d, &img, st.data(),
+            &post->result, post->bad.empty() ? nullptr : post->bad.data(),
+            implicit_cast<uint32_t>(post->bad.size()));
+        post->applied = post_rc == RSX_OK;
+      }
+      if (post_rc != RSX_OK && post_rc != RSX_ERR_TILE_ERRORS) // (as above)
+        (void)rsx_dng_decompress_uncompressed(context(), implicit_cast<int>(up.size()), up.data(),
+                                              &img, st.data());
       for (size_t i = 0; i < ups.size(); ++i) {
         ups[i]->status = st[i];
         all = done(st[i]) && all;
