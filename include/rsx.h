@@ -1224,6 +1224,114 @@ int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
                                          uint32_t* bad, uint32_t bad_cap);
 
 /* ------------------------------------------------------------------------ */
+/* 5. RawImageData::fixBadPixels: the last step of RawDecoder::decodeRaw     */
+/*    (decoders/RawDecoder.cpp:327-328; common/RawImage.cpp:201-239,         */
+/*    :297-323, common/RawImageDataU16.cpp:399-485,                          */
+/*    common/RawImageDataFloat.cpp:177-260).                                 */
+/*                                                                           */
+/*    A position is y << 16 | x in UNCROPPED coordinates (mBadPixelPositions)*/
+/*    and the map is mBadPixelMap: rows of map_pitch = roundUp(ceil(dim_x /  */
+/*    8), 16) bytes, bit x & 7 of byte x >> 3 (createBadPixelMap).  The      */
+/*    stage ORs the positions into the map (duplicates are harmless, the map */
+/*    may already hold bits: map_in), then gives every marked pixel with     */
+/*    x < 32 ((dim_x + 15) / 32) -- fixBadPixelsThread scans that many       */
+/*    blocks of 32, so the marked pixels of a last partial block of 1..16    */
+/*    columns stay as they are, and stay marked -- the value of              */
+/*    fixBadPixel: from the nearest unmarked pixel to the left, to the       */
+/*    right, above and below, stepping by 2 when img->is_cfa, by 1           */
+/*    otherwise, weighted by distance.  uint16: truncating integer weights   */
+/*    of 256ths, a shift of 7 plus one per axis with a neighbour, clamped to */
+/*    16 bits; a pixel without any neighbour becomes 0.  F32 (is_f32): the   */
+/*    walk passes unmarked pixels with a negative value (their distance      */
+/*    counts, their value does not; -0.0 and NaN stop it), every binary32    */
+/*    operation is rounded on its own, and a NaN result is stored as         */
+/*    0xFFC00000, what the reference's invalid operation gives on x86-64.    */
+/*    The stage reads only unmarked pixels and writes only marked ones, so   */
+/*    its result does not depend on the order of the pixels.  It always      */
+/*    works on the uncropped image, after everything else: for DNG behind    */
+/*    the opcode list and the look-up of section 4d.  Bit-exact against the  */
+/*    reference (tests/golden/bad_pixels_ref.json).                          */
+/*                                                                           */
+/*    cpp > 1 is RSX_ERR_UNSUPPORTED and the caller keeps the host path: the */
+/*    reference indexes img(y, x + component) with the PIXEL's x, not x cpp, */
+/*    so its writes land on samples other fixes read, and its row-split      */
+/*    threads race on them -- there is no result to be bit-exact with.       */
+/*                                                                           */
+/*    rsx_bad_pixels_validate, in this order: desc or img NULL (or positions */
+/*    NULL with n_positions != 0); cpp < 1, dim_x or dim_y <= 0, pitch_bytes */
+/*    below dim_x cpp samples or no multiple of the sample size (2, or 4 for */
+/*    is_f32) -> RSX_ERR_INVALID_ARG; cpp > 1 -> RSX_ERR_UNSUPPORTED; dim_x  */
+/*    or dim_y > 65536 -> RSX_ERR_UNSUPPORTED; map_pitch other than          */
+/*    createBadPixelMap's (0 is allowed when neither map_in nor map_out is   */
+/*    given) -> RSX_ERR_INVALID_ARG; a position, or a bit of map_in, at x >= */
+/*    dim_x or y >= dim_y -> RSX_ERR_INVALID_ARG (the reference only asserts */
+/*    and would write outside its map).  On any status but RSX_OK the image  */
+/*    and map_out are untouched.                                             */
+/*    With no positions and no map_in the reference makes no map and touches */
+/*    nothing: RSX_OK, n_bad = n_fixed = 0, map_made = 0, map_out untouched. */
+/*    Otherwise map_made = 1 and map_out (if given) receives the map as      */
+/*    mBadPixelMap holds it afterwards: map_pitch dim_y bytes.               */
+/*    rsx_bad_pixels_fix works in place; img->data may be a host pointer     */
+/*    (the rows go up and come back) or a device pointer (the call returns   */
+/*    when the pass is done); positions, map_in and map_out are host memory. */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_bad_pixels_desc {
+  const uint32_t* positions; /* may be NULL with n_positions 0 */
+  uint32_t n_positions;
+  uint32_t map_pitch;
+  const uint8_t* map_in; /* may be NULL */
+  uint8_t* map_out;      /* may be NULL */
+  int32_t is_f32;
+  int32_t reserved;
+} rsx_bad_pixels_desc;
+
+typedef struct rsx_bad_pixels_result {
+  uint64_t n_bad;   /* distinct marked pixels */
+  uint64_t n_fixed; /* ... of which were given a value */
+  int32_t map_made; /* 0: the reference would have made no map */
+  int32_t reserved;
+} rsx_bad_pixels_result;
+
+int rsx_bad_pixels_validate(const rsx_bad_pixels_desc* desc, const rsx_image* img);
+int rsx_bad_pixels_fix(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc, const rsx_image* img,
+                       rsx_bad_pixels_result* result);
+/* rsx_panasonic_v4_decompress (section 3l), then the stage on the decoded image on the device,
+ * ONE download.  With desc->zero_is_bad the bad pixels are exactly the zero pixels of the decoded
+ * image, so the map is marked from the image and the call depends on no list capacity; without
+ * the flag, or with no zero pixel in the image, the reference makes no map (map_made = 0, map_out
+ * untouched).  map_out (may be NULL; map_pitch as above,
+ * 0 allowed without map_out) receives the map for the caller's mBadPixelMap, result (may be NULL)
+ * the counts.  Statuses as rsx_panasonic_v4_decompress, plus the stage's image checks (an odd
+ * pitch_bytes, a dimension past 65536); on anything but RSX_OK nothing is written. */
+int rsx_panasonic_v4_decompress_fixed(rsx_ctx* ctx, const rsx_panasonic_v4_desc* desc,
+                                      const uint8_t* in, size_t in_bytes, const rsx_image* img,
+                                      uint8_t* map_out, uint32_t map_pitch,
+                                      rsx_bad_pixels_result* result);
+
+/* rsx_dng_post, rsx_dng_decompress_ljpeg_post and rsx_dng_decompress_uncompressed_post (section
+ * 4d) with the bad-pixel stage behind the look-up, on the positions the pass composed, in front
+ * of the one download: the same arguments plus map_out (may be NULL; createBadPixelMap's pitch
+ * times dim_y bytes, written only when the positions are not empty -- the reference makes no map
+ * otherwise).  Each obeys every status rule of the call it extends: a failing tile, a list that
+ * fails the file or a refused list apply nothing, fix included.  A position list past bad_cap
+ * leaves the image as the _post call leaves it, UNFIXED, with RSX_ERR_UNSUPPORTED: the caller runs
+ * fixBadPixels itself.  An image with cpp > 1 whose list yields positions (FixBadPixelsList
+ * entries; FixBadPixelsConstant refuses such images itself) returns RSX_ERR_UNSUPPORTED before
+ * anything is decoded or written, and the caller uses the _post call and the host pass. */
+int rsx_dng_finish(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                   rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap, uint8_t* map_out);
+int rsx_dng_decompress_ljpeg_finish(rsx_ctx* ctx, int n_tiles, const rsx_dng_ljpeg_tile* tiles,
+                                    const rsx_dng_post_desc* desc, const rsx_image* img,
+                                    int32_t* tile_status, uint32_t* tile_consumed,
+                                    rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap,
+                                    uint8_t* map_out);
+int rsx_dng_decompress_uncompressed_finish(rsx_ctx* ctx, int n_tiles,
+                                           const rsx_dng_unpack_tile* tiles,
+                                           const rsx_dng_post_desc* desc, const rsx_image* img,
+                                           int32_t* tile_status, rsx_dng_post_result* result,
+                                           uint32_t* bad, uint32_t bad_cap, uint8_t* map_out);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */
@@ -1424,6 +1532,26 @@ typedef struct rsx_dng_post_job {
   uint32_t reserved;
 } rsx_dng_post_job;
 
+/* one image's bad-pixel stage (section 5), in place on the plan's OUTPUT buffer at img_offset (a
+ * multiple of the sample size), so it runs behind a decode plan on the same buffer and stream.
+ * The positions, n_positions of them, are read from the plan's INPUT buffer at in_offset (a
+ * multiple of 4) by every run; map_in (host memory, may be NULL; map_pitch as in section 5) is
+ * copied at plan creation.  Jobs of different geometry, CFA or not, uint16 and F32, may share a
+ * plan.  A job the image checks or the map checks of rsx_bad_pixels_validate refuse fails the
+ * creation with that status.  The positions are checked on the device: one outside the image
+ * makes the job RSX_ERR_INVALID_ARG in rsx_plan_results and leaves its image untouched.  A job
+ * without positions and without map_in does nothing.  The plan owns both maps of every job. */
+typedef struct rsx_bad_pixels_job {
+  uint64_t in_offset;
+  uint32_t n_positions;
+  uint32_t map_pitch;
+  const uint8_t* map_in;
+  int32_t is_f32;
+  int32_t reserved;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_bad_pixels_job;
+
 /* one VC-5 tile (section 4c): band offsets count from in_offset; the code book and the log table
  * are copied at plan creation.  Jobs of different geometry, book and table may share a plan; any
  * in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset.  The band decode loads a
@@ -1508,6 +1636,11 @@ int rsx_dng_post_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_post_job* j
 int rsx_dng_post_plan_result(rsx_plan* plan, int job, rsx_dng_post_result* out);
 int rsx_dng_post_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
                                  uint64_t* n_bad);
+int rsx_bad_pixels_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_bad_pixels_job* jobs,
+                               rsx_plan** out_plan);
+/* Bad-pixel plans, after rsx_plan_results: the counts of job `job` of the last run.
+ * RSX_ERR_INVALID_ARG for another plan, a job out of range or before results. */
+int rsx_bad_pixels_plan_result(rsx_plan* plan, int job, rsx_bad_pixels_result* out);
 /* After rsx_plan_results of a VC-5 plan: per band of job `job` ([channel][subband], 40 entries
  * each; any may be NULL) its status, and for the high-pass bands the 128-Kbit windows the band
  * decode walked and the parse rounds it took over all of them (a round is one parse of every

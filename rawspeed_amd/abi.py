@@ -425,6 +425,50 @@ def panasonic_consumed(version, bps, dim_x, dim_y):
     return -(-packets // 1024) * 0x4000 if version == 5 else 16 * packets
 
 
+class BadPixelsDesc(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("n_positions", C.c_uint32), ("map_pitch", C.c_uint32),
+                ("map_in", C.c_void_p), ("map_out", C.c_void_p), ("is_f32", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class BadPixelsResult(C.Structure):
+    _fields_ = [("n_bad", C.c_uint64), ("n_fixed", C.c_uint64), ("map_made", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class BadPixelsJob(C.Structure):
+    _fields_ = [("in_offset", C.c_uint64), ("n_positions", C.c_uint32), ("map_pitch", C.c_uint32),
+                ("map_in", C.c_void_p), ("is_f32", C.c_int32), ("reserved", C.c_int32),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def bad_pixels_map_pitch(dim_x):
+    """RawImageData::createBadPixelMap's pitch in bytes"""
+    return (-(-dim_x // 8) + 15) // 16 * 16
+
+
+def bad_pixels_desc(positions, dim, map_in=None, is_f32=False, want_map=True, map_pitch=None):
+    """(rsx_bad_pixels_desc, keep-alive objects, the map_out array or None).  positions: y << 16 | x
+    values; dim: (dim_x, dim_y); map_in: (dim_y, pitch) uint8 or None; map_pitch overrides."""
+    d = BadPixelsDesc()
+    keep = []
+    p = np.ascontiguousarray(positions, dtype=np.uint32)
+    if p.size:
+        d.positions, d.n_positions = p.ctypes.data, p.size
+        keep.append(p)
+    d.map_pitch = bad_pixels_map_pitch(dim[0]) if map_pitch is None else map_pitch
+    if map_in is not None:
+        m = np.ascontiguousarray(map_in, dtype=np.uint8)
+        d.map_in = m.ctypes.data
+        keep.append(m)
+    out = None
+    if want_map:
+        out = np.full((dim[1], bad_pixels_map_pitch(dim[0])), 0xA5, np.uint8)
+        d.map_out = out.ctypes.data
+    d.is_f32 = int(is_f32)
+    return d, keep, out
+
+
 class PanasonicV4Desc(C.Structure):
     _fields_ = [("section_split_offset", C.c_uint32), ("zero_is_bad", C.c_int32)]
 

@@ -10,6 +10,8 @@
                                 the IIQ correction core (rsx_iiq_corr_core.h) as host C++ (g++)
   rawspeed_amd/librsx_dng_post_host.so, rawspeed_amd/rsx_dng_post_host_check
                                 the DNG opcode / look-up core (rsx_dng_post_core.h) as host C++ (g++)
+  rawspeed_amd/librsx_bad_pixels_host.so, rawspeed_amd/rsx_bad_pixels_host_check
+                                the bad-pixel core (rsx_bad_pixels_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -33,19 +35,22 @@ LIB_IIQ_CORR_HOST = os.path.join(PKG, "librsx_iiq_corr_host.so")
 BIN_IIQ_CORR_CHECK = os.path.join(PKG, "rsx_iiq_corr_host_check")
 LIB_DNG_POST_HOST = os.path.join(PKG, "librsx_dng_post_host.so")
 BIN_DNG_POST_CHECK = os.path.join(PKG, "rsx_dng_post_host_check")
+LIB_BAD_PIXELS_HOST = os.path.join(PKG, "librsx_bad_pixels_host.so")
+BIN_BAD_PIXELS_CHECK = os.path.join(PKG, "rsx_bad_pixels_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
                 "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_vc5.hip",
-                "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_host.cpp"]
+                "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
                 "rsx_panasonic_dev.h", "rsx_panasonic_v4.h", "rsx_dng_deflate.h",
                 "rsx_inflate_core.h", "rsx_fp_widen.h", "rsx_dither_dev.h", "rsx_nikon_snef.h",
                 "rsx_vc5.h", "rsx_vc5_core.h", "rsx_iiq_corr.h", "rsx_iiq_corr_core.h",
-                "rsx_dng_post.h", "rsx_dng_post_core.h"]
+                "rsx_dng_post.h", "rsx_dng_post_core.h", "rsx_bad_pixels.h",
+                "rsx_bad_pixels_core.h"]
 
 
 def _hipcc():
@@ -67,6 +72,22 @@ def _run(cmd):
     if r.returncode != 0:
         raise RuntimeError("build failed: %s\n%s" % (" ".join(cmd), r.stdout))
     return r.stdout
+
+
+SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+            "-static-libubsan"]
+
+
+def _links_with_sanitizers():
+    """whether g++ has the runtimes of SANITIZE: an empty program links with them"""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "t.cpp")
+        with open(src, "w") as f:
+            f.write("int main() { return 0; }\n")
+        r = subprocess.run(["g++", src, "-o", os.path.join(d, "t")] + SANITIZE,
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return r.returncode == 0
 
 
 def build_synth(force=False):
@@ -158,6 +179,25 @@ def build_dng_post_host(force=False):
     return LIB_DNG_POST_HOST, BIN_DNG_POST_CHECK
 
 
+def build_bad_pixels_host(force=False):
+    """rsx_bad_pixels_core.h as host C++ (rsx_bad_pixels_host.cpp), without contraction: the
+    library the tests load, and the same source as a program with AddressSanitizer and UBSan where
+    g++ has their runtimes (built-in cases and the case file a test hands it against a
+    pixel-at-a-time restatement); only where an empty program does not link with them is the
+    program built plain."""
+    src = os.path.join(CSRC, "rsx_bad_pixels_host.cpp")
+    deps = [src, os.path.join(CSRC, "rsx_bad_pixels_core.h"), os.path.join(INCLUDE, "rsx.h")]
+    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-ffp-contract=off",
+            "-pthread", "-I" + CSRC, "-I" + INCLUDE]
+    if force or _stale(LIB_BAD_PIXELS_HOST, deps):
+        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_BAD_PIXELS_HOST, src])
+    if force or _stale(BIN_BAD_PIXELS_CHECK, deps):
+        main = base + ["-O1", "-g", "-DRSX_BAD_PIXELS_HOST_MAIN", "-o", BIN_BAD_PIXELS_CHECK, src]
+        # (plain only where g++ lacks the runtimes: an error of the instrumented build is an error)
+        _run(main + SANITIZE if _links_with_sanitizers() else main)
+    return LIB_BAD_PIXELS_HOST, BIN_BAD_PIXELS_CHECK
+
+
 def _compile_objects(objdir, extra_flags, force=False):
     """One object per source under `objdir`, rebuilt when the source or any header is newer;
     the stale ones in parallel (the sources are independent translation units: one hipcc run
@@ -212,7 +252,8 @@ def build_variant(name, extra_flags):
 
 def build_all(force=False):
     return (build_core(force), build_synth(force), build_inflate_host(force),
-            build_vc5_host(force), build_iiq_corr_host(force), build_dng_post_host(force))
+            build_vc5_host(force), build_iiq_corr_host(force), build_dng_post_host(force),
+            build_bad_pixels_host(force))
 
 
 if __name__ == "__main__":

@@ -43,6 +43,9 @@ EXPORTS = [
     "rsx_dng_post_validate", "rsx_dng_post", "rsx_dng_decompress_ljpeg_post",
     "rsx_dng_decompress_uncompressed_post", "rsx_dng_post_plan_create",
     "rsx_dng_post_plan_result", "rsx_dng_post_plan_bad_pixels",
+    "rsx_bad_pixels_validate", "rsx_bad_pixels_fix", "rsx_panasonic_v4_decompress_fixed",
+    "rsx_bad_pixels_plan_create", "rsx_bad_pixels_plan_result",
+    "rsx_dng_finish", "rsx_dng_decompress_ljpeg_finish", "rsx_dng_decompress_uncompressed_finish",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
@@ -142,6 +145,22 @@ def lib():
         L.rsx_dng_post_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_dng_post_plan_bad_pixels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
                                                    C.c_void_p]
+        L.rsx_bad_pixels_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_bad_pixels_fix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_panasonic_v4_decompress_fixed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_size_t, C.c_void_p, C.c_void_p,
+                                                        C.c_uint32, C.c_void_p]
+        L.rsx_bad_pixels_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_dng_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint32, C.c_void_p]
+        L.rsx_dng_decompress_ljpeg_finish.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_uint32,
+                                                      C.c_void_p]
+        L.rsx_dng_decompress_uncompressed_finish.argtypes = [C.c_void_p, C.c_int, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_uint32,
+                                                             C.c_void_p]
         L.rsx_vc5_plan_bands.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v0_validate.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
         L.rsx_samsung_v0_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -173,7 +192,7 @@ def lib():
                      "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
                      "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
                      "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
-                     "rsx_dng_post_plan_create"):
+                     "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -261,6 +280,12 @@ def dng_post_validate(desc, img_view, bad_cap=1 << 16):
                                      None if img_view is None else C.byref(img_view),
                                      C.byref(r), buf, bad_cap)
     return st, r, _bad_out(r, buf, st)
+
+
+def bad_pixels_validate(desc, img_view):
+    """rsx_bad_pixels_validate; desc: abi.BadPixelsDesc (abi.bad_pixels_desc), None passes NULL"""
+    return lib().rsx_bad_pixels_validate(None if desc is None else C.byref(desc),
+                                         None if img_view is None else C.byref(img_view))
 
 
 def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
@@ -458,7 +483,18 @@ class Context:
         st = lib().rsx_dng_post(self._h, C.byref(desc), C.byref(img_view), C.byref(r), buf, bad_cap)
         return st, r, _bad_out(r, buf, st)
 
-    def _dng_post_call(self, fn, tile_type, descs, datas, desc, img_view, bad_cap, consumed):
+    def dng_finish(self, desc, img_view, bad_cap=1 << 16):
+        """dng_post, then the bad-pixel stage on the device.  Returns (status, abi.DngPostResult,
+        positions or None, the map as (dim_y, map_pitch) uint8 -- untouched 0xA5 unless made)."""
+        r = abi.DngPostResult()
+        buf = (C.c_uint32 * max(1, bad_cap))()
+        m = np.full((img_view.dim_y, abi.bad_pixels_map_pitch(img_view.dim_x)), 0xA5, np.uint8)
+        st = lib().rsx_dng_finish(self._h, C.byref(desc), C.byref(img_view), C.byref(r), buf, bad_cap,
+                                  m.ctypes.data)
+        return st, r, _bad_out(r, buf, st), m
+
+    def _dng_post_call(self, fn, tile_type, descs, datas, desc, img_view, bad_cap, consumed,
+                       with_map=False):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
         tiles = (tile_type * n)()
@@ -473,8 +509,23 @@ class Context:
         args = [self._h, n, tiles, C.byref(desc), C.byref(img_view), st]
         if consumed:
             args.append(None)
+        if with_map:
+            m = np.full((img_view.dim_y, abi.bad_pixels_map_pitch(img_view.dim_x)), 0xA5, np.uint8)
+            rc = fn(*args, C.byref(r), buf, bad_cap, m.ctypes.data)
+            return rc, list(st), r, _bad_out(r, buf, rc), m
         rc = fn(*args, C.byref(r), buf, bad_cap)
         return rc, list(st), r, _bad_out(r, buf, rc)
+
+    def dng_decompress_ljpeg_finish(self, descs, datas, desc, img_view, bad_cap=1 << 16):
+        """dng_decompress_ljpeg_post with the bad-pixel stage behind the look-up.  Returns (status,
+        tile statuses, result, positions or None, the map -- 0xA5 unless made)."""
+        return self._dng_post_call(lib().rsx_dng_decompress_ljpeg_finish, abi.DngLJpegTile, descs,
+                                   datas, desc, img_view, bad_cap, True, True)
+
+    def dng_decompress_uncompressed_finish(self, descs, datas, desc, img_view, bad_cap=1 << 16):
+        """dng_decompress_uncompressed_post with the bad-pixel stage behind the look-up"""
+        return self._dng_post_call(lib().rsx_dng_decompress_uncompressed_finish, abi.DngUnpackTile,
+                                   descs, datas, desc, img_view, bad_cap, False, True)
 
     def dng_decompress_ljpeg_post(self, descs, datas, desc, img_view, bad_cap=1 << 16):
         """dng_decompress_ljpeg, then the list and the look-up of `desc` (abi.DngPostDesc) on the
@@ -486,6 +537,26 @@ class Context:
         """dng_decompress_uncompressed, then the list and the look-up on the device, one download"""
         return self._dng_post_call(lib().rsx_dng_decompress_uncompressed_post, abi.DngUnpackTile,
                                    descs, datas, desc, img_view, bad_cap, False)
+
+    def bad_pixels_fix(self, desc, img_view):
+        """desc: abi.BadPixelsDesc; img_view.data a host or a device pointer; in place.  Returns
+        (status, abi.BadPixelsResult)."""
+        r = abi.BadPixelsResult()
+        st = lib().rsx_bad_pixels_fix(self._h, C.byref(desc), C.byref(img_view), C.byref(r))
+        return st, r
+
+    def panasonic_v4_decompress_fixed(self, split, zero_is_bad, data, img_view, want_map=True):
+        """panasonic_v4_decompress, then the bad-pixel stage on the device, one download.  Returns
+        (status, abi.BadPixelsResult, the map as (dim_y, map_pitch) uint8 -- None unless made)."""
+        a = _u8(data)
+        d = abi.PanasonicV4Desc(split, int(zero_is_bad))
+        pitch = abi.bad_pixels_map_pitch(img_view.dim_x)
+        m = np.full((max(1, img_view.dim_y), pitch), 0xA5, np.uint8)
+        r = abi.BadPixelsResult()
+        st = lib().rsx_panasonic_v4_decompress_fixed(
+            self._h, C.byref(d), a.ctypes.data, a.size, C.byref(img_view),
+            m.ctypes.data if want_map else None, pitch if want_map else 0, C.byref(r))
+        return st, r, (m if st == abi.RSX_OK and r.map_made and want_map else None)
 
     def sony_arw2_decompress(self, mode, table, data, img_view, rows=True):
         """Returns (status, per-row statuses or None)."""
@@ -620,6 +691,11 @@ class Context:
         place on the output buffer"""
         return DngPostPlan(self, "rsx_dng_post_plan_create", abi.DngPostJob, jobs)
 
+    def bad_pixels_plan(self, jobs):
+        """jobs: abi.BadPixelsJob (positions in the input buffer; map_in is copied at plan
+        creation); runs in place on the output buffer"""
+        return BadPixelsPlan(self, "rsx_bad_pixels_plan_create", abi.BadPixelsJob, jobs)
+
     def sony_arw2_plan(self, jobs):
         """jobs: abi.SonyArw2Job (their tables are copied at plan creation)"""
         return Plan(self, "rsx_sony_arw2_plan_create", abi.SonyArw2Job, jobs)
@@ -729,6 +805,14 @@ class DngPostPlan(Plan):
         n = C.c_uint64(0)
         st = lib().rsx_dng_post_plan_bad_pixels(self._h, job, buf if cap else None, cap, C.byref(n))
         return st, n.value, ([int(v) for v in buf[:n.value]] if st == abi.RSX_OK else None)
+
+
+class BadPixelsPlan(Plan):
+    def result(self, job):
+        """after results(): (status, abi.BadPixelsResult) of job `job`"""
+        r = abi.BadPixelsResult()
+        st = lib().rsx_bad_pixels_plan_result(self._h, job, C.byref(r))
+        return st, r
 
 
 class PanasonicV4Plan(Plan):

@@ -18,6 +18,7 @@
 #include "rsx_vc5.h"
 #include "rsx_iiq_corr.h"
 #include "rsx_dng_post.h"
+#include "rsx_bad_pixels.h"
 
 #include <algorithm>
 #include <map>
@@ -2943,6 +2944,195 @@ extern "C" int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* i
 }
 
 // ---------------------------------------------------------------------------
+// RawImageData::fixBadPixels
+// ---------------------------------------------------------------------------
+extern "C" int rsx_bad_pixels_validate(const rsx_bad_pixels_desc* desc, const rsx_image* img) {
+  return bad_pixels_validate(desc, img);
+}
+
+extern "C" int rsx_bad_pixels_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_bad_pixels_job* jobs,
+                                          rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, bad_pixels_plan_create);
+}
+
+extern "C" int rsx_bad_pixels_plan_result(rsx_plan* plan, int job, rsx_bad_pixels_result* out) {
+  if (!plan || plan->kind != PLAN_DECODER)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
+  return plan->dec->bad_pixels_result(job, out);
+}
+
+namespace {
+// the one-job plan of a host call: made for the call (it owns the call's two maps)
+struct BadPixelsCall {
+  rsx_plan* plan = nullptr;
+  ~BadPixelsCall() { rsx_plan_destroy(plan); }
+  int create(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc, const rsx_image* img) {
+    rsx_bad_pixels_job job{};
+    job.n_positions = desc->n_positions;
+    job.map_in = desc->map_in;
+    job.map_pitch = desc->map_in ? desc->map_pitch : 0u;
+    job.is_f32 = desc->is_f32;
+    job.img = *img;
+    job.img.data = nullptr;
+    return rsx_bad_pixels_plan_create(ctx, 1, &job, &plan);
+  }
+  // the map from the zero pixels of a uint16 image
+  int create_zero(rsx_ctx* ctx, const rsx_image* img) {
+    rsx_bad_pixels_job job{};
+    return decoder_plan_create(
+        ctx, 1, &job, &plan,
+        [&](rsx_ctx* c, int, const rsx_bad_pixels_job*, std::unique_ptr<DecoderPlan>* out) {
+          return bad_pixels_zero_plan_create(c, img, out);
+        });
+  }
+  // in place on `dev`, the positions at `pos_dev`; returns when the pass is done
+  int run(const void* pos_dev, void* dev, hipStream_t s) {
+    if (int st = rsx_plan_run(plan, pos_dev ? pos_dev : dev, dev, s))
+      return st;
+    return rsx_plan_results(plan, nullptr, nullptr);
+  }
+  // the counts and the map behind run()
+  int finish(rsx_bad_pixels_result* result, uint8_t* map_out) {
+    rsx_bad_pixels_result r;
+    if (int st = plan->dec->bad_pixels_result(0, &r))
+      return st;
+    if (result)
+      *result = r;
+    if (map_out && r.map_made)
+      return plan->dec->bad_pixels_map(0, map_out, plan->last_stream);
+    return RSX_OK;
+  }
+};
+} // namespace
+
+// In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
+// work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
+// and come back through download_rects.  The positions go up in front of the pass in both cases.
+extern "C" int rsx_bad_pixels_fix(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc,
+                                  const rsx_image* img, rsx_bad_pixels_result* result) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !desc || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = bad_pixels_validate(desc, img))
+    return st;
+  if (desc->n_positions == 0 && !desc->map_in)
+    return RSX_OK; // (the reference makes no map and touches nothing)
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  BadPixelsCall call;
+  if (int st = call.create(ctx, desc, img))
+    return st;
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof attr);
+  bool on_device = false;
+  if (hipPointerGetAttributes(&attr, img->data) == hipSuccess)
+    on_device = attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+  else
+    (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
+  const size_t pos_bytes = size_t(desc->n_positions) * 4;
+  if (on_device) {
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    DeviceBuffer d_pos;
+    if (pos_bytes) {
+      if (int e = d_pos.ensure(pos_bytes + 16))
+        return e;
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.ptr, desc->positions, pos_bytes, hipMemcpyHostToDevice,
+                                        ctx->stream));
+    }
+    if (int st = call.run(d_pos.ptr, img->data, nullptr))
+      return st;
+    return call.finish(result, desc->map_out);
+  }
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  const size_t row_bytes = size_t(img->dim_x) * (desc->is_f32 ? 4 : 2);
+  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
+  if (int e = lane.lane->d_in.ensure(pos_bytes + 64))
+    return e;
+  if (int e = lane.lane->d_out.ensure(bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    if (pos_bytes)
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, desc->positions, pos_bytes,
+                                        hipMemcpyHostToDevice, s));
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice, s));
+  }
+  if (int st = call.run(lane.lane->d_in.ptr, lane.lane->d_out.ptr, s))
+    return st;
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
+              size_t(img->dim_y)};
+  {
+    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+    if (int e = download_rects(ctx, lane.lane, s, &dr, 1))
+      return e;
+  }
+  return call.finish(result, desc->map_out);
+}
+
+// rsx_panasonic_v4_decompress, the map marked from the zero pixels of the decoded image and the
+// fix on the device, ONE download.  The decode runs without its list: the map needs no capacity.
+extern "C" int rsx_panasonic_v4_decompress_fixed(rsx_ctx* ctx, const rsx_panasonic_v4_desc* desc,
+                                                 const uint8_t* in, size_t in_bytes,
+                                                 const rsx_image* img, uint8_t* map_out,
+                                                 uint32_t map_pitch,
+                                                 rsx_bad_pixels_result* result) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  uint64_t span = 0;
+  if (int st = panasonic_v4_validate(desc, *img, in_bytes, &span))
+    return st;
+  if (int st = bad_pixels_validate_image(img, false))
+    return st;
+  if ((map_out || map_pitch != 0) && map_pitch != bad_pixels_map_pitch(uint32_t(img->dim_x)))
+    return RSX_ERR_INVALID_ARG;
+  BadPixelsCall call;
+  if (desc->zero_is_bad)
+    if (int st = call.create_zero(ctx, img))
+      return st;
+  rsx_panasonic_v4_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc.section_split_offset = desc->section_split_offset;
+  job.desc.zero_is_bad = 0;
+  job.in_bytes = span;
+  job.img = *img;
+  job.img.data = nullptr;
+  std::vector<uint8_t> key;
+  key_create(key, rsx_panasonic_v4_plan_create);
+  key_append(key, &job);
+  bool ran = false;
+  const int rc = single_image_host(
+      ctx, key, rsx_panasonic_v4_plan_create, job, in, size_t(span), img, nullptr,
+      [](rsx_plan*, hipStream_t) { return RSX_OK; }, [](rsx_plan*, int st) { return st; },
+      [&](void* dev, hipStream_t s) {
+        if (!call.plan)
+          return int(RSX_OK);
+        const int e = call.run(nullptr, dev, s);
+        ran = e == RSX_OK;
+        return e;
+      });
+  if (rc != RSX_OK || !ran)
+    return rc;
+  // (an image without a zero pixel leaves mBadPixelPositions empty: the reference makes no map)
+  rsx_bad_pixels_result r;
+  if (int st = call.finish(&r, nullptr))
+    return st;
+  if (r.n_bad == 0)
+    return RSX_OK;
+  if (result)
+    *result = r;
+  return map_out ? call.finish(nullptr, map_out) : int(RSX_OK);
+}
+
+// ---------------------------------------------------------------------------
 // DngDecoder behind the tiles: OpcodeList1 and the LinearizationTable look-up
 // ---------------------------------------------------------------------------
 extern "C" int rsx_dng_post_validate(const rsx_dng_post_desc* desc, const rsx_image* img,
@@ -3005,17 +3195,72 @@ struct DngPostCall {
     return plan->dec->bad_pixels(0, bad, bad_cap, &n);
   }
 };
+
+// The bad-pixel stage behind a pass (the _finish calls): the positions the pass composed go back
+// up and the fix runs on the same image and stream, in front of the download.  A list past
+// bad_cap leaves the image as the pass left it (the call then reports RSX_ERR_UNSUPPORTED, as the
+// _post call does).  `on` false: the _post calls themselves, nothing happens.
+struct DngFixStage {
+  bool on = false;
+  uint8_t* map_out = nullptr;
+  BadPixelsCall fix;
+  DeviceBuffer d_pos;
+  bool ran = false;
+  // cpp > 1 with positions: refused before anything is decoded (section 5)
+  static int refuse(const rsx_dng_post_desc* desc, const rsx_image* img) {
+    if (img->cpp <= 1)
+      return RSX_OK;
+    rsx_dng_post_result r{};
+    const int st = dng_post_validate(desc, img, &r, nullptr, 0);
+    if (st != RSX_OK && st != RSX_ERR_UNSUPPORTED)
+      return RSX_OK; // (the call itself reports it)
+    return r.n_bad != 0 ? int(RSX_ERR_UNSUPPORTED) : int(RSX_OK);
+  }
+  int run(rsx_ctx* ctx, DngPostCall& call, const rsx_dng_post_desc* desc, const rsx_image* img,
+          uint32_t* bad, uint32_t bad_cap, void* dev, hipStream_t s) {
+    if (!on)
+      return RSX_OK;
+    uint64_t n = 0;
+    const int st = call.plan->dec->bad_pixels(0, bad, bad_cap, &n);
+    if (st == RSX_ERR_UNSUPPORTED)
+      return RSX_OK;
+    if (st != RSX_OK)
+      return st;
+    if (n == 0)
+      return RSX_OK; // (the reference makes no map)
+    rsx_bad_pixels_desc d{};
+    d.positions = bad;
+    d.n_positions = uint32_t(n);
+    d.is_f32 = desc->is_f32;
+    if (int e = fix.create(ctx, &d, img))
+      return e;
+    if (int e = d_pos.ensure(size_t(n) * 4 + 16))
+      return e;
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.ptr, bad, size_t(n) * 4, hipMemcpyHostToDevice,
+                                      s ? s : ctx->stream));
+    if (int e = fix.run(d_pos.ptr, dev, s))
+      return e;
+    ran = true;
+    return RSX_OK;
+  }
+  // the map, behind the download
+  int finish() { return ran && map_out ? fix.finish(nullptr, map_out) : int(RSX_OK); }
+};
 } // namespace
 
 // In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
 // work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
 // and come back through download_rects.
-extern "C" int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
-                            rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap) {
+namespace {
+int dng_post_call(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                  rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap, DngFixStage& fix) {
   if (!ctx || !desc || !img || !img->data || (!bad && bad_cap != 0))
     return RSX_ERR_INVALID_ARG;
   ++ctx->host_calls;
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (fix.on)
+    if (int st = DngFixStage::refuse(desc, img))
+      return st;
   DngPostCall call;
   if (int st = call.create(ctx, desc, img, bad_cap))
     return st;
@@ -3028,6 +3273,10 @@ extern "C" int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const r
     (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
   if (on_device) {
     if (int st = call.run(img->data, nullptr))
+      return st;
+    if (int st = fix.run(ctx, call, desc, img, bad, bad_cap, img->data, nullptr))
+      return st;
+    if (int st = fix.finish())
       return st;
     return call.finish(result, bad, bad_cap, true);
   }
@@ -3045,6 +3294,8 @@ extern "C" int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const r
   }
   if (int st = call.run(lane.lane->d_out.ptr, s))
     return st;
+  if (int st = fix.run(ctx, call, desc, img, bad, bad_cap, lane.lane->d_out.ptr, s))
+    return st;
   DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
               static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
               size_t(img->dim_y)};
@@ -3053,21 +3304,43 @@ extern "C" int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const r
     if (int e = download_rects(ctx, lane.lane, s, &dr, 1))
       return e;
   }
+  if (int st = fix.finish())
+    return st;
   return call.finish(result, bad, bad_cap, true);
+}
+} // namespace
+
+extern "C" int rsx_dng_post(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                            rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap) {
+  DngFixStage none;
+  return dng_post_call(ctx, desc, img, result, bad, bad_cap, none);
+}
+
+// rsx_dng_post, then the bad-pixel stage on the positions the pass composed, in front of the
+// download (a device pointer: in place)
+extern "C" int rsx_dng_finish(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                              rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap,
+                              uint8_t* map_out) {
+  DngFixStage fix;
+  fix.on = true;
+  fix.map_out = map_out;
+  return dng_post_call(ctx, desc, img, result, bad, bad_cap, fix);
 }
 
 // rsx_dng_decompress_ljpeg, the list and the look-up on the decoded image on the device, ONE
 // download.  The tiles go up as one call (no bands: the pass needs the whole image).
-extern "C" int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles,
-                                             const rsx_dng_ljpeg_tile* tiles,
-                                             const rsx_dng_post_desc* desc, const rsx_image* img,
-                                             int32_t* tile_status, uint32_t* tile_consumed,
-                                             rsx_dng_post_result* result, uint32_t* bad,
-                                             uint32_t bad_cap) {
+namespace {
+int dng_ljpeg_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_ljpeg_tile* tiles,
+                        const rsx_dng_post_desc* desc, const rsx_image* img, int32_t* tile_status,
+                        uint32_t* tile_consumed, rsx_dng_post_result* result, uint32_t* bad,
+                        uint32_t bad_cap, DngFixStage& fix) {
   if (!ctx || !tiles || n_tiles < 1 || !desc || !img || !img->data || (!bad && bad_cap != 0))
     return RSX_ERR_INVALID_ARG;
   if (desc->is_f32)
     return RSX_ERR_INVALID_ARG; // (LJPEG tiles decode to uint16)
+  if (fix.on)
+    if (int st = DngFixStage::refuse(desc, img))
+      return st;
   DngPostCall call;
   if (int st = call.create(ctx, desc, img, bad_cap))
     return st;
@@ -3083,7 +3356,9 @@ extern "C" int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles,
   std::vector<uint32_t> cons(n_tiles, 0);
   bool ran = false;
   const DevicePostFn post = [&](uint8_t* dev, hipStream_t s) {
-    const int e = call.run(dev, s);
+    int e = call.run(dev, s);
+    if (e == RSX_OK)
+      e = fix.run(ctx, call, desc, img, bad, bad_cap, dev, s);
     ran = e == RSX_OK;
     return e;
   };
@@ -3109,7 +3384,35 @@ extern "C" int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles,
     call.finish(result, nullptr, 0, false);
     return RSX_ERR_TILE_ERRORS; // (the plain call's verdict; nothing of the list was applied)
   }
+  if (int e = fix.finish())
+    return e;
   return call.finish(result, bad, bad_cap, true);
+}
+} // namespace
+
+extern "C" int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles,
+                                             const rsx_dng_ljpeg_tile* tiles,
+                                             const rsx_dng_post_desc* desc, const rsx_image* img,
+                                             int32_t* tile_status, uint32_t* tile_consumed,
+                                             rsx_dng_post_result* result, uint32_t* bad,
+                                             uint32_t bad_cap) {
+  DngFixStage none;
+  return dng_ljpeg_post_call(ctx, n_tiles, tiles, desc, img, tile_status, tile_consumed, result, bad,
+                             bad_cap, none);
+}
+
+// rsx_dng_decompress_ljpeg_post with the bad-pixel stage behind the look-up, in front of the download
+extern "C" int rsx_dng_decompress_ljpeg_finish(rsx_ctx* ctx, int n_tiles,
+                                               const rsx_dng_ljpeg_tile* tiles,
+                                               const rsx_dng_post_desc* desc, const rsx_image* img,
+                                               int32_t* tile_status, uint32_t* tile_consumed,
+                                               rsx_dng_post_result* result, uint32_t* bad,
+                                               uint32_t bad_cap, uint8_t* map_out) {
+  DngFixStage fix;
+  fix.on = true;
+  fix.map_out = map_out;
+  return dng_ljpeg_post_call(ctx, n_tiles, tiles, desc, img, tile_status, tile_consumed, result, bad,
+                             bad_cap, fix);
 }
 
 // rsx_dng_decompress_uncompressed, the list and the look-up on the device, ONE download.  The
@@ -3117,17 +3420,19 @@ extern "C" int rsx_dng_decompress_ljpeg_post(rsx_ctx* ctx, int n_tiles,
 // rectangle per tile and downloads in bands); tiles that do not all
 // validate make this the plain call (a tile fails: nothing of the list is applied); tiles that do
 // not cover the image are RSX_ERR_UNSUPPORTED, nothing written.
-extern "C" int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
-                                                    const rsx_dng_unpack_tile* tiles,
-                                                    const rsx_dng_post_desc* desc,
-                                                    const rsx_image* img, int32_t* tile_status,
-                                                    rsx_dng_post_result* result, uint32_t* bad,
-                                                    uint32_t bad_cap) {
+namespace {
+int dng_uncompressed_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_unpack_tile* tiles,
+                               const rsx_dng_post_desc* desc, const rsx_image* img,
+                               int32_t* tile_status, rsx_dng_post_result* result, uint32_t* bad,
+                               uint32_t bad_cap, DngFixStage& fix) {
   if (!ctx || !tiles || n_tiles < 1 || !desc || !img || !img->data || (!bad && bad_cap != 0))
     return RSX_ERR_INVALID_ARG;
   if (desc->is_f32)
     return RSX_ERR_INVALID_ARG; // (rsx_unpack_f32 images: rsx_dng_post on the result)
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (fix.on)
+    if (int st = DngFixStage::refuse(desc, img))
+      return st;
   DngPostCall call;
   if (int st = call.create(ctx, desc, img, bad_cap))
     return st;
@@ -3196,6 +3501,8 @@ extern "C" int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
     return rc; // (every tile validated: a device failure; tile_status untouched)
   if (int e = call.run(lane.lane->d_out.ptr, s))
     return e;
+  if (int e = fix.run(ctx, call, desc, img, bad, bad_cap, lane.lane->d_out.ptr, s))
+    return e;
   DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
               static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
               size_t(img->dim_y)};
@@ -3207,7 +3514,36 @@ extern "C" int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
   // (tile_status is written only by a call that wrote the image)
   if (tile_status)
     std::copy(st.begin(), st.end(), tile_status);
+  if (int e = fix.finish())
+    return e;
   return call.finish(result, bad, bad_cap, true);
+}
+} // namespace
+
+extern "C" int rsx_dng_decompress_uncompressed_post(rsx_ctx* ctx, int n_tiles,
+                                                    const rsx_dng_unpack_tile* tiles,
+                                                    const rsx_dng_post_desc* desc,
+                                                    const rsx_image* img, int32_t* tile_status,
+                                                    rsx_dng_post_result* result, uint32_t* bad,
+                                                    uint32_t bad_cap) {
+  DngFixStage none;
+  return dng_uncompressed_post_call(ctx, n_tiles, tiles, desc, img, tile_status, result, bad,
+                                    bad_cap, none);
+}
+
+// rsx_dng_decompress_uncompressed_post with the bad-pixel stage behind the look-up, in front of
+// the download
+extern "C" int rsx_dng_decompress_uncompressed_finish(rsx_ctx* ctx, int n_tiles,
+                                                      const rsx_dng_unpack_tile* tiles,
+                                                      const rsx_dng_post_desc* desc,
+                                                      const rsx_image* img, int32_t* tile_status,
+                                                      rsx_dng_post_result* result, uint32_t* bad,
+                                                      uint32_t bad_cap, uint8_t* map_out) {
+  DngFixStage fix;
+  fix.on = true;
+  fix.map_out = map_out;
+  return dng_uncompressed_post_call(ctx, n_tiles, tiles, desc, img, tile_status, result, bad,
+                                    bad_cap, fix);
 }
 
 // ---------------------------------------------------------------------------

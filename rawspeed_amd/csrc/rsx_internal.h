@@ -192,6 +192,14 @@ struct DecoderPlan {
   virtual int dng_post_result(int /*job*/, rsx_dng_post_result* /*out*/) {
     return RSX_ERR_INVALID_ARG;
   }
+  // the counts of job `job` of the last run, after results (bad-pixel plans), and its map as
+  // mBadPixelMap holds it (map_pitch dim_y bytes to host memory; returns when they are there)
+  virtual int bad_pixels_result(int /*job*/, rsx_bad_pixels_result* /*out*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
+  virtual int bad_pixels_map(int /*job*/, uint8_t* /*out*/, hipStream_t) {
+    return RSX_ERR_INVALID_ARG;
+  }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };
