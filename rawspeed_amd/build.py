@@ -98,104 +98,61 @@ def build_synth(force=False):
     return LIB_SYNTH
 
 
+def _build_host_core(lib, check_bin, src, deps, main_macro, extra_flags, force=False):
+    """A kernel's core header as host C++ (csrc/`src`; `deps`: what it includes): the library the
+    tests load, and the same source with -D`main_macro` as a program with AddressSanitizer and
+    UBSan (an instrumented library cannot be loaded into an uninstrumented Python; the program
+    runs its built-in cases and the corpus or case file a test hands it).  Only where an empty
+    program does not link with the runtimes is the program built plain: an error of the
+    instrumented build is an error."""
+    src = os.path.join(CSRC, src)
+    deps = [src] + [os.path.join(CSRC, d) for d in deps]
+    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-I" + CSRC,
+            *extra_flags]
+    if force or _stale(lib, deps):
+        _run(base + ["-O2", "-fPIC", "-shared", "-o", lib, src])
+    if force or _stale(check_bin, deps):
+        main = base + ["-O1", "-g", "-D" + main_macro, "-o", check_bin, src]
+        _run(main + SANITIZE if _links_with_sanitizers() else main)
+    return lib, check_bin
+
+
+# binary32 as the device computes it (no contraction), and the public header
+_NO_CONTRACT = ["-ffp-contract=off", "-I" + INCLUDE]
+_RSX_H = os.path.join(INCLUDE, "rsx.h")
+
+
 def build_inflate_host(force=False):
-    """rsx_inflate_core.h with a wave of one lane: the library the tests load, and the same
-    source as a program with AddressSanitizer and UBSan where g++ has their runtimes (an
-    instrumented library cannot be loaded into an uninstrumented Python; the program reads a
-    corpus file).  Without the runtimes the program is built plain."""
-    src = os.path.join(CSRC, "rsx_inflate_host.cpp")
-    deps = [src, os.path.join(CSRC, "rsx_inflate_core.h")]
-    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-I" + CSRC]
-    if force or _stale(LIB_INFLATE_HOST, deps):
-        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_INFLATE_HOST, src])
-    if force or _stale(BIN_INFLATE_CHECK, deps):
-        main = base + ["-O1", "-g", "-DRSX_INFLATE_HOST_MAIN", "-o", BIN_INFLATE_CHECK, src]
-        try:
-            _run(main + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-static-libasan", "-static-libubsan"])
-        except RuntimeError:
-            _run(main)
-    return LIB_INFLATE_HOST, BIN_INFLATE_CHECK
+    """rsx_inflate_core.h with a wave of one lane"""
+    return _build_host_core(LIB_INFLATE_HOST, BIN_INFLATE_CHECK, "rsx_inflate_host.cpp",
+                            ["rsx_inflate_core.h"], "RSX_INFLATE_HOST_MAIN", [], force)
 
 
 def build_vc5_host(force=False):
-    """rsx_vc5_core.h as host C++ (rsx_vc5_host.cpp): the library the tests load, and the same
-    source as a program with AddressSanitizer and UBSan where g++ has their runtimes (it reads a
-    corpus file); without the runtimes the program is built plain."""
-    src = os.path.join(CSRC, "rsx_vc5_host.cpp")
-    deps = [src, os.path.join(CSRC, "rsx_vc5_core.h")]
-    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-I" + CSRC]
-    if force or _stale(LIB_VC5_HOST, deps):
-        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_VC5_HOST, src])
-    if force or _stale(BIN_VC5_CHECK, deps):
-        main = base + ["-O1", "-g", "-DRSX_VC5_HOST_MAIN", "-o", BIN_VC5_CHECK, src]
-        try:
-            _run(main + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-static-libasan", "-static-libubsan"])
-        except RuntimeError:
-            _run(main)
-    return LIB_VC5_HOST, BIN_VC5_CHECK
+    """rsx_vc5_core.h"""
+    return _build_host_core(LIB_VC5_HOST, BIN_VC5_CHECK, "rsx_vc5_host.cpp",
+                            ["rsx_vc5_core.h"], "RSX_VC5_HOST_MAIN", [], force)
 
 
 def build_iiq_corr_host(force=False):
-    """rsx_iiq_corr_core.h as host C++ (rsx_iiq_corr_host.cpp), binary32 without contraction: the
-    library the tests load, and the same source as a program with AddressSanitizer and UBSan where
-    g++ has their runtimes (it runs the validation and the clipped-area cases against a
-    pass-per-entry restatement); without the runtimes the program is built plain."""
-    src = os.path.join(CSRC, "rsx_iiq_corr_host.cpp")
-    deps = [src, os.path.join(CSRC, "rsx_iiq_corr_core.h"), os.path.join(INCLUDE, "rsx.h")]
-    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-ffp-contract=off",
-            "-I" + CSRC, "-I" + INCLUDE]
-    if force or _stale(LIB_IIQ_CORR_HOST, deps):
-        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_IIQ_CORR_HOST, src])
-    if force or _stale(BIN_IIQ_CORR_CHECK, deps):
-        main = base + ["-O1", "-g", "-DRSX_IIQ_CORR_HOST_MAIN", "-o", BIN_IIQ_CORR_CHECK, src]
-        try:
-            _run(main + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-static-libasan", "-static-libubsan"])
-        except RuntimeError:
-            _run(main)
-    return LIB_IIQ_CORR_HOST, BIN_IIQ_CORR_CHECK
+    """rsx_iiq_corr_core.h, binary32 without contraction"""
+    return _build_host_core(LIB_IIQ_CORR_HOST, BIN_IIQ_CORR_CHECK, "rsx_iiq_corr_host.cpp",
+                            ["rsx_iiq_corr_core.h", _RSX_H], "RSX_IIQ_CORR_HOST_MAIN", _NO_CONTRACT,
+                            force)
 
 
 def build_dng_post_host(force=False):
-    """rsx_dng_post_core.h as host C++ (rsx_dng_post_host.cpp), without contraction: the library
-    the tests load, and the same source as a program with AddressSanitizer and UBSan where g++ has
-    their runtimes (built-in and damaged lists against a pass-per-opcode restatement, and the case
-    files a test hands it); without the runtimes the program is built plain."""
-    src = os.path.join(CSRC, "rsx_dng_post_host.cpp")
-    deps = [src, os.path.join(CSRC, "rsx_dng_post_core.h"), os.path.join(INCLUDE, "rsx.h")]
-    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-ffp-contract=off",
-            "-I" + CSRC, "-I" + INCLUDE]
-    if force or _stale(LIB_DNG_POST_HOST, deps):
-        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_DNG_POST_HOST, src])
-    if force or _stale(BIN_DNG_POST_CHECK, deps):
-        main = base + ["-O1", "-g", "-DRSX_DNG_POST_HOST_MAIN", "-o", BIN_DNG_POST_CHECK, src]
-        try:
-            _run(main + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-static-libasan", "-static-libubsan"])
-        except RuntimeError:
-            _run(main)
-    return LIB_DNG_POST_HOST, BIN_DNG_POST_CHECK
+    """rsx_dng_post_core.h, without contraction"""
+    return _build_host_core(LIB_DNG_POST_HOST, BIN_DNG_POST_CHECK, "rsx_dng_post_host.cpp",
+                            ["rsx_dng_post_core.h", _RSX_H], "RSX_DNG_POST_HOST_MAIN", _NO_CONTRACT,
+                            force)
 
 
 def build_bad_pixels_host(force=False):
-    """rsx_bad_pixels_core.h as host C++ (rsx_bad_pixels_host.cpp), without contraction: the
-    library the tests load, and the same source as a program with AddressSanitizer and UBSan where
-    g++ has their runtimes (built-in cases and the case file a test hands it against a
-    pixel-at-a-time restatement); only where an empty program does not link with them is the
-    program built plain."""
-    src = os.path.join(CSRC, "rsx_bad_pixels_host.cpp")
-    deps = [src, os.path.join(CSRC, "rsx_bad_pixels_core.h"), os.path.join(INCLUDE, "rsx.h")]
-    base = ["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-ffp-contract=off",
-            "-pthread", "-I" + CSRC, "-I" + INCLUDE]
-    if force or _stale(LIB_BAD_PIXELS_HOST, deps):
-        _run(base + ["-O2", "-fPIC", "-shared", "-o", LIB_BAD_PIXELS_HOST, src])
-    if force or _stale(BIN_BAD_PIXELS_CHECK, deps):
-        main = base + ["-O1", "-g", "-DRSX_BAD_PIXELS_HOST_MAIN", "-o", BIN_BAD_PIXELS_CHECK, src]
-        # (plain only where g++ lacks the runtimes: an error of the instrumented build is an error)
-        _run(main + SANITIZE if _links_with_sanitizers() else main)
-    return LIB_BAD_PIXELS_HOST, BIN_BAD_PIXELS_CHECK
+    """rsx_bad_pixels_core.h, without contraction; the row bands run on threads"""
+    return _build_host_core(LIB_BAD_PIXELS_HOST, BIN_BAD_PIXELS_CHECK, "rsx_bad_pixels_host.cpp",
+                            ["rsx_bad_pixels_core.h", _RSX_H], "RSX_BAD_PIXELS_HOST_MAIN",
+                            ["-pthread"] + _NO_CONTRACT, force)
 
 
 def _compile_objects(objdir, extra_flags, force=False):

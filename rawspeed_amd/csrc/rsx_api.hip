@@ -1620,6 +1620,32 @@ int decoder_plan_create(rsx_ctx* ctx, int n_jobs, const JobT* jobs, rsx_plan** o
   return RSX_OK;
 }
 
+// The frame of a decoder plan's per-job getters: a decoder plan, the context's lock, and what
+// `get` takes from its DecoderPlan.
+template <typename GetFn>
+int decoder_plan_get(rsx_plan* plan, GetFn get) {
+  if (!plan || plan->kind != PLAN_DECODER)
+    return RSX_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
+  return get(plan->dec.get());
+}
+
+// The plan a host call makes for itself and destroys on its way out, not kept in a lane (a
+// stage's key would be its payloads, lists, tables or maps).
+struct CallPlan {
+  rsx_plan* plan = nullptr;
+  CallPlan() = default;
+  CallPlan(const CallPlan&) = delete;
+  ~CallPlan() { rsx_plan_destroy(plan); }
+  // in place on `dev`, a side input (the bad-pixel positions) at `in_dev` or none; returns when
+  // the pass is done
+  int run(const void* in_dev, void* dev, hipStream_t s) {
+    if (int st = rsx_plan_run(plan, in_dev ? in_dev : dev, dev, s))
+      return st;
+    return rsx_plan_results(plan, nullptr, nullptr);
+  }
+};
+
 // An LJPEG-family plan: `fill(job, in)` turns each job into its LJpegJobIn, status included.
 template <typename JobT, typename FillFn>
 int ljpeg_family_plan_create(rsx_ctx* ctx, int n_jobs, const JobT* jobs, rsx_plan** out_plan,
@@ -1798,18 +1824,15 @@ extern "C" int rsx_sraw_interpolate(rsx_ctx* ctx, const rsx_sraw_desc* d,
   RSX_HIP_CHECK(ctx, hipMemcpy2DAsync(lane.lane->d_in.ptr, job.in.pitch_bytes, in->data,
                                       in->pitch_bytes, in_w, size_t(in->dim_y),
                                       hipMemcpyHostToDevice, s));
-  rsx_plan* plan = nullptr;
-  if (int st = rsx_sraw_plan_create(ctx, 1, &job, &plan))
+  CallPlan call;
+  if (int st = rsx_sraw_plan_create(ctx, 1, &job, &call.plan))
     return st;
-  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
-  if (rc == RSX_OK) {
-    const DownRect dr{static_cast<uint8_t*>(out->data), out->pitch_bytes,
-                      static_cast<uint8_t*>(lane.lane->d_out.ptr), job.img.pitch_bytes, out_w,
-                      size_t(out->dim_y)};
-    rc = download_rects(ctx, lane.lane, s, &dr, 1);
-  }
-  rsx_plan_destroy(plan);
-  return rc;
+  if (int rc = rsx_plan_run(call.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s))
+    return rc;
+  const DownRect dr{static_cast<uint8_t*>(out->data), out->pitch_bytes,
+                    static_cast<uint8_t*>(lane.lane->d_out.ptr), job.img.pitch_bytes, out_w,
+                    size_t(out->dim_y)};
+  return download_rects(ctx, lane.lane, s, &dr, 1);
 }
 
 extern "C" int rsx_nikon_validate(const rsx_nikon_desc* d, const rsx_image* img) {
@@ -2103,6 +2126,25 @@ void key_job<rsx_nikon_job>(std::vector<uint8_t>& key, const rsx_nikon_job& job)
     key_append(key, job.desc.curve, size_t(job.desc.curve_size));
 }
 
+// The job of a call of one job (single_image_host): all zeros, then the input size and the image
+// without its host pointer.  The caller adds its descriptor's fields, leaving host pointers NULL ...
+template <typename JobT>
+void one_job_init(JobT& job, size_t in_bytes, const rsx_image* img) {
+  std::memset(&job, 0, sizeof job);
+  job.in_bytes = in_bytes;
+  job.img = *img;
+  job.img.data = nullptr;
+}
+// ... and starts its key from the create function and that job; the contents behind the host
+// pointers follow (key_append), and the pointers go into the job last.
+template <typename JobT>
+std::vector<uint8_t> one_job_key(PlanCreateFn<JobT> create, const JobT& job) {
+  std::vector<uint8_t> key;
+  key_create(key, create);
+  key_append(key, &job);
+  return key;
+}
+
 // The lane's plan for `key` (*reused: the one it held), else a new one from create(ctx, n,
 // jobs) in place of the one it held; when create fails, the lane holds none.
 template <typename JobT>
@@ -2285,14 +2327,15 @@ int ljpeg_chunked_host(rsx_ctx* ctx, rsx_ctx::HostLane* L, rsx_plan* plan, size_
   return rc;
 }
 
-// before_download (may be NULL): what a call does to the decoded image on the device in front of
-// the download (the DNG opcode list and look-up), given the address row 0 of the image has and
-// the stream.  The jobs' rectangles must tile the whole image (rects_tile_image, any number of
-// them): a call whose jobs do not returns RSX_ERR_UNSUPPORTED before anything is uploaded or
-// decoded, statuses untouched.  It runs only when every job decoded, and the whole image then goes
-// back as one rectangle.  With a failing job the call is the plain call.
+// What a call does to the decoded image on the device in front of the download, given the address
+// row 0 of the image has and the stream (ljpeg_family_host, single_image_host).
 typedef std::function<int(uint8_t*, hipStream_t)> DevicePostFn;
 
+// before_download (may be NULL): the DNG opcode list and look-up.  The jobs' rectangles must tile
+// the whole image (rects_tile_image, any number of them): a call whose jobs do not returns
+// RSX_ERR_UNSUPPORTED before anything is uploaded or decoded, statuses untouched.  It runs only
+// when every job decoded, and the whole image then goes back as one rectangle.  With a failing job
+// the call is the plain call.
 template <typename JobT>
 int ljpeg_family_host(rsx_ctx* ctx, int n, std::vector<JobT>& jobs,
                       const uint8_t* const* ins, const rsx_image* img,
@@ -2484,21 +2527,27 @@ int one_job_host(rsx_ctx* ctx, const DescT* d, const uint8_t* in, size_t in_byte
   return rc;
 }
 
-// One image through a host-pointer call of Phase One, ARW2, Panasonic, Panasonic V4, SamsungV0 or sNEF: `span` bytes from `src` up as one
-// copy, the lane's plan for `key` run on them (on_reuse(plan, stream): this call's data onto a
-// plan the lane held), the row statuses out, and the image back as one rectangle through
-// download_rects -- only when every row decoded (the reference throws otherwise, and the
-// caller's image stays as it was).
+// One image through a host-pointer call of Phase One, ARW2, Panasonic, Panasonic V4, SamsungV0,
+// sNEF or VC-5: `span` bytes from `src` up as one copy, the lane's plan for `key` run on them, the
+// row statuses out, and the image back as one rectangle through download_rects -- only when
+// every row decoded (the reference throws otherwise, and the caller's image stays as it was).
+// The hooks of a call, an empty one skipped:
+// on_reuse(plan, stream): this call's data onto a plan the lane held.
 // on_done(plan, rc): what the call takes from the plan besides the image, behind the results; the
 // status it returns decides about the download (Panasonic V4: the list, and an image that is
 // complete although the list did not fit).
 // before_download(device image, stream): what the call does to the decoded image on the device in
 // front of the download (Phase One with corrections); a status but RSX_OK ends the call with it.
-template <typename JobT, typename ReuseFn, typename DoneFn, typename PostFn>
+struct SingleImageHooks {
+  std::function<int(rsx_plan*, hipStream_t)> on_reuse;
+  std::function<int(rsx_plan*, int)> on_done;
+  DevicePostFn before_download;
+};
+
+template <typename JobT>
 int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
                       const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
-                      int32_t* row_status, ReuseFn on_reuse, DoneFn on_done,
-                      PostFn before_download) {
+                      int32_t* row_status, const SingleImageHooks& hooks = SingleImageHooks()) {
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   LaneGuard lane(ctx, &key);
   if (!lane.lane)
@@ -2517,11 +2566,15 @@ int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT
   bool reused = false;
   if (int st = lane_plan(ctx, lane.lane, key, create, 1, &job, &plan, &reused))
     return st;
-  if (reused)
-    if (int st = on_reuse(plan, s))
-      return st;
+  // (the hooks' calls are inlined here: an out-of-line std::function::operator() would be one
+  // more weak symbol in the library's dynamic table)
+  int rc = RSX_OK;
+  if (reused && hooks.on_reuse)
+    [[clang::always_inline]] rc = hooks.on_reuse(plan, s);
+  if (rc != RSX_OK)
+    return rc;
   int32_t st = RSX_OK;
-  int rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
+  rc = rsx_plan_run(plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
   if (rc == RSX_OK)
     rc = rsx_plan_results(plan, &st, nullptr);
   if (rc == RSX_OK || rc == st) {
@@ -2529,36 +2582,22 @@ int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT
       if (int e = plan->dec->row_status(s, 0, row_status))
         rc = e;
   }
-  rc = on_done(plan, rc);
+  if (hooks.on_done)
+    [[clang::always_inline]] rc = hooks.on_done(plan, rc);
   if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM || rc == RSX_ERR_INVALID_ARG) {
     evict_plan(lane.lane);
     return rc;
   }
   if (rc != RSX_OK)
     return rc; // (a failing row: nothing goes back into the caller's image)
-  if (int e = before_download(lane.lane->d_out.ptr, s))
-    return e;
-  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
-              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes,
+  uint8_t* const dev = static_cast<uint8_t*>(lane.lane->d_out.ptr);
+  if (hooks.before_download)
+    if (int e = hooks.before_download(dev, s))
+      return e;
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes, dev, img->pitch_bytes,
               size_t(img->dim_x) * size_t(img->cpp) * 2, size_t(img->dim_y)};
   std::lock_guard<std::mutex> down_lock(ctx->download_mu);
   return download_rects(ctx, lane.lane, s, &dr, 1);
-}
-
-template <typename JobT, typename ReuseFn, typename DoneFn>
-int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
-                      const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
-                      int32_t* row_status, ReuseFn on_reuse, DoneFn on_done) {
-  return single_image_host(ctx, key, create, job, src, span, img, row_status, on_reuse, on_done,
-                           [](void*, hipStream_t) { return int(RSX_OK); });
-}
-
-template <typename JobT, typename ReuseFn>
-int single_image_host(rsx_ctx* ctx, std::vector<uint8_t>& key, PlanCreateFn<JobT> create,
-                      const JobT& job, const uint8_t* src, size_t span, const rsx_image* img,
-                      int32_t* row_status, ReuseFn on_reuse) {
-  return single_image_host(ctx, key, create, job, src, span, img, row_status, on_reuse,
-                           [](rsx_plan*, int rc) { return rc; });
 }
 
 } // namespace
@@ -2798,9 +2837,9 @@ extern "C" int rsx_phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_pha
 // The host-pointer call (single_image_host): the bytes the strips cover go up as one copy; the
 // plan's key holds the strip table.
 namespace {
-template <typename PostFn>
 int phase_one_host(rsx_ctx* ctx, const uint8_t* in, int n_strips, const rsx_phase_one_strip* strips,
-                   const rsx_image* img, int32_t* strip_status, PostFn before_download) {
+                   const rsx_image* img, int32_t* strip_status,
+                   const SingleImageHooks& hooks = SingleImageHooks()) {
   uint64_t lo = ~uint64_t(0), hi = 0;
   for (int i = 0; i < n_strips; ++i) {
     lo = std::min<uint64_t>(lo, strips[i].offset);
@@ -2811,19 +2850,13 @@ int phase_one_host(rsx_ctx* ctx, const uint8_t* in, int n_strips, const rsx_phas
     s.offset -= lo;
   const size_t span = size_t(hi - lo);
   rsx_phase_one_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.n_strips = n_strips;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_phase_one_plan_create);
-  key_append(key, &job);
+  std::vector<uint8_t> key = one_job_key(rsx_phase_one_plan_create, job);
   key_append(key, local.data(), local.size());
   job.strips = local.data();
   return single_image_host(ctx, key, rsx_phase_one_plan_create, job, in + lo, span, img,
-                           strip_status, [](rsx_plan*, hipStream_t) { return int(RSX_OK); },
-                           [](rsx_plan*, int rc) { return rc; }, before_download);
+                           strip_status, hooks);
 }
 } // namespace
 
@@ -2835,8 +2868,7 @@ extern "C" int rsx_phase_one_decompress(rsx_ctx* ctx, const uint8_t* in, size_t 
   ++ctx->host_calls;
   if (int st = phase_one_validate(n_strips, strips, in_bytes, *img))
     return st;
-  return phase_one_host(ctx, in, n_strips, strips, img, strip_status,
-                        [](void*, hipStream_t) { return int(RSX_OK); });
+  return phase_one_host(ctx, in, n_strips, strips, img, strip_status);
 }
 
 // ---------------------------------------------------------------------------
@@ -2852,31 +2884,84 @@ extern "C" int rsx_iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs,
 }
 
 namespace {
-// the one-job plan of a host call: made for the call, not kept in a lane (its key would be the
-// payloads and 512 KiB a curve set)
-struct IiqCallPlan {
-  rsx_plan* plan = nullptr;
-  ~IiqCallPlan() { rsx_plan_destroy(plan); }
-  int create(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx_image* img) {
-    auto job = std::make_unique<rsx_iiq_correct_job>();
-    job->corr = *corr;
-    job->img_offset = 0;
-    job->img = *img;
-    job->img.data = nullptr;
-    return rsx_iiq_correct_plan_create(ctx, 1, job.get(), &plan);
-  }
-  // in place on `dev`; returns when the pass is done
-  int run(void* dev, hipStream_t s) {
-    if (int st = rsx_plan_run(plan, dev, dev, s))
+// true iff the runtime knows `p` as device (or managed) memory
+bool is_device_pointer(const void* p) {
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof attr);
+  if (hipPointerGetAttributes(&attr, p) == hipSuccess)
+    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+  (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
+  return false;
+}
+
+// A stage in place on the caller's image of rows of `row_bytes` bytes (rsx_iiq_correct,
+// rsx_bad_pixels_fix, rsx_dng_post, rsx_dng_finish).  A device pointer: run(side, image, NULL),
+// which puts the pass on the context's stream, behind the null stream's work so far, and returns
+// when it is done.  A host pointer: the rows go up as one copy, run(side, rows, stream) on a lane,
+// and the rows come back through download_rects.  The side input (the bad-pixel positions;
+// side_bytes 0: none, run gets NULL) goes up in front of the pass in both cases: into a buffer of
+// the call's own, or into the lane's input staging.  after (may be empty): what the call takes
+// from its plans behind the pass and the download.
+typedef std::function<int(const void* side_dev, void* dev, hipStream_t s)> InPlaceRunFn;
+int in_place_call(rsx_ctx* ctx, const rsx_image* img, size_t row_bytes, const void* side,
+                  size_t side_bytes, const InPlaceRunFn& run,
+                  const std::function<int()>& after = nullptr) {
+  if (is_device_pointer(img->data)) {
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    DeviceBuffer d_side;
+    if (side_bytes) {
+      if (int e = d_side.ensure(side_bytes + 16))
+        return e;
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(d_side.ptr, side, side_bytes, hipMemcpyHostToDevice,
+                                        ctx->stream));
+    }
+    if (int st = run(d_side.ptr, img->data, nullptr))
       return st;
-    return rsx_plan_results(plan, nullptr, nullptr);
+    return after ? after() : int(RSX_OK);
   }
-};
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  rsx_ctx::HostLane* L = lane.lane;
+  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
+  if (side_bytes)
+    if (int e = L->d_in.ensure(side_bytes + 64))
+      return e;
+  if (int e = L->d_out.ensure(bytes + 64))
+    return e;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    if (side_bytes)
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr, side, side_bytes, hipMemcpyHostToDevice,
+                                        L->stream));
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice,
+                                      L->stream));
+  }
+  if (int st = run(side_bytes ? L->d_in.ptr : nullptr, L->d_out.ptr, L->stream))
+    return st;
+  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
+              static_cast<const uint8_t*>(L->d_out.ptr), img->pitch_bytes, row_bytes,
+              size_t(img->dim_y)};
+  {
+    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+    if (int e = download_rects(ctx, L, L->stream, &dr, 1))
+      return e;
+  }
+  return after ? after() : int(RSX_OK);
+}
+
+// the correction plan of a host call (a CallPlan: a curve set alone is 512 KiB)
+int iiq_call_create(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx_image* img, CallPlan& call) {
+  auto job = std::make_unique<rsx_iiq_correct_job>();
+  job->corr = *corr;
+  job->img_offset = 0;
+  job->img = *img;
+  job->img.data = nullptr;
+  return rsx_iiq_correct_plan_create(ctx, 1, job.get(), &call.plan);
+}
 } // namespace
 
-// In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
-// work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
-// and come back through download_rects.
+// In place (in_place_call).
 extern "C" int rsx_iiq_correct(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx_image* img) {
   if (!ctx || !corr || !img || !img->data)
     return RSX_ERR_INVALID_ARG;
@@ -2888,37 +2973,11 @@ extern "C" int rsx_iiq_correct(rsx_ctx* ctx, const rsx_iiq_corr* corr, const rsx
   if (corr->n_ops == 0)
     return RSX_OK;
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  hipPointerAttribute_t attr;
-  std::memset(&attr, 0, sizeof attr);
-  bool on_device = false;
-  if (hipPointerGetAttributes(&attr, img->data) == hipSuccess)
-    on_device = attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-  else
-    (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
-  IiqCallPlan call;
-  if (int st = call.create(ctx, corr, img))
+  CallPlan call;
+  if (int st = iiq_call_create(ctx, corr, img, call))
     return st;
-  if (on_device)
-    return call.run(img->data, nullptr);
-  LaneGuard lane(ctx);
-  if (!lane.lane)
-    return RSX_ERR_DEVICE;
-  const size_t row_bytes = size_t(img->dim_x) * 2;
-  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
-  if (int e = lane.lane->d_out.ensure(bytes + 64))
-    return e;
-  hipStream_t s = lane.lane->stream;
-  {
-    std::lock_guard<std::mutex> up(ctx->upload_mu);
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice, s));
-  }
-  if (int st = call.run(lane.lane->d_out.ptr, s))
-    return st;
-  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
-              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
-              size_t(img->dim_y)};
-  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
-  return download_rects(ctx, lane.lane, s, &dr, 1);
+  return in_place_call(ctx, img, size_t(img->dim_x) * 2, nullptr, 0,
+                       [&](const void*, void* dev, hipStream_t s) { return call.run(nullptr, dev, s); });
 }
 
 // rsx_phase_one_decompress with the corrections on the decoded image in front of the download
@@ -2935,12 +2994,14 @@ extern "C" int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* i
     return st;
   if (img->pitch_bytes % 2 != 0)
     return RSX_ERR_INVALID_ARG;
-  IiqCallPlan call;
-  if (corr->n_ops != 0)
-    if (int st = call.create(ctx, corr, img))
+  CallPlan call;
+  SingleImageHooks hooks;
+  if (corr->n_ops != 0) { // (an empty list: no plan, the plain decode)
+    if (int st = iiq_call_create(ctx, corr, img, call))
       return st;
-  return phase_one_host(ctx, in, n_strips, strips, img, strip_status,
-                        [&](void* dev, hipStream_t s) { return call.plan ? call.run(dev, s) : int(RSX_OK); });
+    hooks.before_download = [&](uint8_t* dev, hipStream_t s) { return call.run(nullptr, dev, s); };
+  }
+  return phase_one_host(ctx, in, n_strips, strips, img, strip_status, hooks);
 }
 
 // ---------------------------------------------------------------------------
@@ -2956,59 +3017,45 @@ extern "C" int rsx_bad_pixels_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_ba
 }
 
 extern "C" int rsx_bad_pixels_plan_result(rsx_plan* plan, int job, rsx_bad_pixels_result* out) {
-  if (!plan || plan->kind != PLAN_DECODER)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
-  return plan->dec->bad_pixels_result(job, out);
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->bad_pixels_result(job, out); });
 }
 
 namespace {
-// the one-job plan of a host call: made for the call (it owns the call's two maps)
-struct BadPixelsCall {
-  rsx_plan* plan = nullptr;
-  ~BadPixelsCall() { rsx_plan_destroy(plan); }
-  int create(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc, const rsx_image* img) {
-    rsx_bad_pixels_job job{};
-    job.n_positions = desc->n_positions;
-    job.map_in = desc->map_in;
-    job.map_pitch = desc->map_in ? desc->map_pitch : 0u;
-    job.is_f32 = desc->is_f32;
-    job.img = *img;
-    job.img.data = nullptr;
-    return rsx_bad_pixels_plan_create(ctx, 1, &job, &plan);
-  }
-  // the map from the zero pixels of a uint16 image
-  int create_zero(rsx_ctx* ctx, const rsx_image* img) {
-    rsx_bad_pixels_job job{};
-    return decoder_plan_create(
-        ctx, 1, &job, &plan,
-        [&](rsx_ctx* c, int, const rsx_bad_pixels_job*, std::unique_ptr<DecoderPlan>* out) {
-          return bad_pixels_zero_plan_create(c, img, out);
-        });
-  }
-  // in place on `dev`, the positions at `pos_dev`; returns when the pass is done
-  int run(const void* pos_dev, void* dev, hipStream_t s) {
-    if (int st = rsx_plan_run(plan, pos_dev ? pos_dev : dev, dev, s))
-      return st;
-    return rsx_plan_results(plan, nullptr, nullptr);
-  }
-  // the counts and the map behind run()
-  int finish(rsx_bad_pixels_result* result, uint8_t* map_out) {
-    rsx_bad_pixels_result r;
-    if (int st = plan->dec->bad_pixels_result(0, &r))
-      return st;
-    if (result)
-      *result = r;
-    if (map_out && r.map_made)
-      return plan->dec->bad_pixels_map(0, map_out, plan->last_stream);
-    return RSX_OK;
-  }
-};
+// the fix's plan of a host call (a CallPlan: it owns the call's two maps)
+int bad_pixels_call_create(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc, const rsx_image* img,
+                           CallPlan& call) {
+  rsx_bad_pixels_job job{};
+  job.n_positions = desc->n_positions;
+  job.map_in = desc->map_in;
+  job.map_pitch = desc->map_in ? desc->map_pitch : 0u;
+  job.is_f32 = desc->is_f32;
+  job.img = *img;
+  job.img.data = nullptr;
+  return rsx_bad_pixels_plan_create(ctx, 1, &job, &call.plan);
+}
+// ... with the map from the zero pixels of a uint16 image
+int bad_pixels_zero_call_create(rsx_ctx* ctx, const rsx_image* img, CallPlan& call) {
+  rsx_bad_pixels_job job{};
+  return decoder_plan_create(
+      ctx, 1, &job, &call.plan,
+      [&](rsx_ctx* c, int, const rsx_bad_pixels_job*, std::unique_ptr<DecoderPlan>* out) {
+        return bad_pixels_zero_plan_create(c, img, out);
+      });
+}
+// the counts and the map behind the fix's run
+int bad_pixels_finish(const CallPlan& call, rsx_bad_pixels_result* result, uint8_t* map_out) {
+  rsx_bad_pixels_result r;
+  if (int st = call.plan->dec->bad_pixels_result(0, &r))
+    return st;
+  if (result)
+    *result = r;
+  if (map_out && r.map_made)
+    return call.plan->dec->bad_pixels_map(0, map_out, call.plan->last_stream);
+  return RSX_OK;
+}
 } // namespace
 
-// In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
-// work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
-// and come back through download_rects.  The positions go up in front of the pass in both cases.
+// In place (in_place_call), the positions its side input.
 extern "C" int rsx_bad_pixels_fix(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc,
                                   const rsx_image* img, rsx_bad_pixels_result* result) {
   if (result)
@@ -3021,58 +3068,14 @@ extern "C" int rsx_bad_pixels_fix(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc,
   if (desc->n_positions == 0 && !desc->map_in)
     return RSX_OK; // (the reference makes no map and touches nothing)
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  BadPixelsCall call;
-  if (int st = call.create(ctx, desc, img))
+  CallPlan call;
+  if (int st = bad_pixels_call_create(ctx, desc, img, call))
     return st;
-  hipPointerAttribute_t attr;
-  std::memset(&attr, 0, sizeof attr);
-  bool on_device = false;
-  if (hipPointerGetAttributes(&attr, img->data) == hipSuccess)
-    on_device = attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-  else
-    (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
-  const size_t pos_bytes = size_t(desc->n_positions) * 4;
-  if (on_device) {
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    DeviceBuffer d_pos;
-    if (pos_bytes) {
-      if (int e = d_pos.ensure(pos_bytes + 16))
-        return e;
-      RSX_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.ptr, desc->positions, pos_bytes, hipMemcpyHostToDevice,
-                                        ctx->stream));
-    }
-    if (int st = call.run(d_pos.ptr, img->data, nullptr))
-      return st;
-    return call.finish(result, desc->map_out);
-  }
-  LaneGuard lane(ctx);
-  if (!lane.lane)
-    return RSX_ERR_DEVICE;
-  const size_t row_bytes = size_t(img->dim_x) * (desc->is_f32 ? 4 : 2);
-  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
-  if (int e = lane.lane->d_in.ensure(pos_bytes + 64))
-    return e;
-  if (int e = lane.lane->d_out.ensure(bytes + 64))
-    return e;
-  hipStream_t s = lane.lane->stream;
-  {
-    std::lock_guard<std::mutex> up(ctx->upload_mu);
-    if (pos_bytes)
-      RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr, desc->positions, pos_bytes,
-                                        hipMemcpyHostToDevice, s));
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice, s));
-  }
-  if (int st = call.run(lane.lane->d_in.ptr, lane.lane->d_out.ptr, s))
-    return st;
-  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
-              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
-              size_t(img->dim_y)};
-  {
-    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
-    if (int e = download_rects(ctx, lane.lane, s, &dr, 1))
-      return e;
-  }
-  return call.finish(result, desc->map_out);
+  return in_place_call(
+      ctx, img, size_t(img->dim_x) * (desc->is_f32 ? 4 : 2), desc->positions,
+      size_t(desc->n_positions) * 4,
+      [&](const void* pos_dev, void* dev, hipStream_t s) { return call.run(pos_dev, dev, s); },
+      [&]() { return bad_pixels_finish(call, result, desc->map_out); });
 }
 
 // rsx_panasonic_v4_decompress, the map marked from the zero pixels of the decoded image and the
@@ -3094,42 +3097,36 @@ extern "C" int rsx_panasonic_v4_decompress_fixed(rsx_ctx* ctx, const rsx_panason
     return st;
   if ((map_out || map_pitch != 0) && map_pitch != bad_pixels_map_pitch(uint32_t(img->dim_x)))
     return RSX_ERR_INVALID_ARG;
-  BadPixelsCall call;
-  if (desc->zero_is_bad)
-    if (int st = call.create_zero(ctx, img))
+  CallPlan call;
+  SingleImageHooks hooks;
+  bool ran = false;
+  if (desc->zero_is_bad) {
+    if (int st = bad_pixels_zero_call_create(ctx, img, call))
       return st;
+    hooks.before_download = [&](uint8_t* dev, hipStream_t s) {
+      const int e = call.run(nullptr, dev, s);
+      ran = e == RSX_OK;
+      return e;
+    };
+  }
   rsx_panasonic_v4_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.desc.section_split_offset = desc->section_split_offset;
   job.desc.zero_is_bad = 0;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_panasonic_v4_plan_create);
-  key_append(key, &job);
-  bool ran = false;
-  const int rc = single_image_host(
-      ctx, key, rsx_panasonic_v4_plan_create, job, in, size_t(span), img, nullptr,
-      [](rsx_plan*, hipStream_t) { return RSX_OK; }, [](rsx_plan*, int st) { return st; },
-      [&](void* dev, hipStream_t s) {
-        if (!call.plan)
-          return int(RSX_OK);
-        const int e = call.run(nullptr, dev, s);
-        ran = e == RSX_OK;
-        return e;
-      });
+  std::vector<uint8_t> key = one_job_key(rsx_panasonic_v4_plan_create, job);
+  const int rc = single_image_host(ctx, key, rsx_panasonic_v4_plan_create, job, in, size_t(span),
+                                   img, nullptr, hooks);
   if (rc != RSX_OK || !ran)
     return rc;
   // (an image without a zero pixel leaves mBadPixelPositions empty: the reference makes no map)
   rsx_bad_pixels_result r;
-  if (int st = call.finish(&r, nullptr))
+  if (int st = bad_pixels_finish(call, &r, nullptr))
     return st;
   if (r.n_bad == 0)
     return RSX_OK;
   if (result)
     *result = r;
-  return map_out ? call.finish(nullptr, map_out) : int(RSX_OK);
+  return map_out ? bad_pixels_finish(call, nullptr, map_out) : int(RSX_OK);
 }
 
 // ---------------------------------------------------------------------------
@@ -3147,54 +3144,46 @@ extern "C" int rsx_dng_post_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_
 }
 
 extern "C" int rsx_dng_post_plan_result(rsx_plan* plan, int job, rsx_dng_post_result* out) {
-  if (!plan || plan->kind != PLAN_DECODER)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
-  return plan->dec->dng_post_result(job, out);
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->dng_post_result(job, out); });
 }
 
 extern "C" int rsx_dng_post_plan_bad_pixels(rsx_plan* plan, int job, uint32_t* out, uint32_t cap,
                                             uint64_t* n_bad) {
   if (n_bad)
     *n_bad = 0;
-  if (!plan || plan->kind != PLAN_DECODER)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
-  return plan->dec->bad_pixels(job, out, cap, n_bad);
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->bad_pixels(job, out, cap, n_bad); });
 }
 
 namespace {
-// the one-job plan of a host call: made for the call, not kept in a lane (its key would be the
-// list, up to 16 tables and the look-up table)
-struct DngPostCall {
-  rsx_plan* plan = nullptr;
-  ~DngPostCall() { rsx_plan_destroy(plan); }
-  int create(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img, uint32_t bad_cap) {
-    rsx_dng_post_job job{};
-    job.desc = *desc;
-    job.img = *img;
-    job.img.data = nullptr;
-    job.bad_cap = bad_cap;
-    return rsx_dng_post_plan_create(ctx, 1, &job, &plan);
-  }
-  // in place on `dev`; returns when the pass is done.  A hit list past its capacity is no
-  // failure of the pass: finish() reports it.
-  int run(void* dev, hipStream_t s) {
-    if (int st = rsx_plan_run(plan, dev, dev, s))
-      return st;
-    const int st = rsx_plan_results(plan, nullptr, nullptr);
-    return st == RSX_ERR_UNSUPPORTED ? int(RSX_OK) : st;
-  }
-  // the result and the positions behind run(); without a run (a failing tile) the parse's result
-  int finish(rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap, bool ran) {
-    if (result)
-      plan->dec->dng_post_result(0, result);
-    if (!ran)
-      return RSX_OK;
-    uint64_t n = 0;
-    return plan->dec->bad_pixels(0, bad, bad_cap, &n);
-  }
-};
+// the pass's plan of a host call (a CallPlan: its key would be the list, up to 16 tables and the
+// look-up table)
+int dng_post_call_create(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
+                         uint32_t bad_cap, CallPlan& call) {
+  rsx_dng_post_job job{};
+  job.desc = *desc;
+  job.img = *img;
+  job.img.data = nullptr;
+  job.bad_cap = bad_cap;
+  return rsx_dng_post_plan_create(ctx, 1, &job, &call.plan);
+}
+// in place on `dev`; returns when the pass is done.  A hit list past its capacity is no failure
+// of the pass: dng_post_finish reports it.
+int dng_post_run(CallPlan& call, void* dev, hipStream_t s) {
+  if (int st = rsx_plan_run(call.plan, dev, dev, s))
+    return st;
+  const int st = rsx_plan_results(call.plan, nullptr, nullptr);
+  return st == RSX_ERR_UNSUPPORTED ? int(RSX_OK) : st;
+}
+// the result and the positions behind the run; without a run (a failing tile) the parse's result
+int dng_post_finish(const CallPlan& call, rsx_dng_post_result* result, uint32_t* bad,
+                    uint32_t bad_cap, bool ran) {
+  if (result)
+    call.plan->dec->dng_post_result(0, result);
+  if (!ran)
+    return RSX_OK;
+  uint64_t n = 0;
+  return call.plan->dec->bad_pixels(0, bad, bad_cap, &n);
+}
 
 // The bad-pixel stage behind a pass (the _finish calls): the positions the pass composed go back
 // up and the fix runs on the same image and stream, in front of the download.  A list past
@@ -3203,7 +3192,7 @@ struct DngPostCall {
 struct DngFixStage {
   bool on = false;
   uint8_t* map_out = nullptr;
-  BadPixelsCall fix;
+  CallPlan fix;
   DeviceBuffer d_pos;
   bool ran = false;
   // cpp > 1 with positions: refused before anything is decoded (section 5)
@@ -3216,7 +3205,7 @@ struct DngFixStage {
       return RSX_OK; // (the call itself reports it)
     return r.n_bad != 0 ? int(RSX_ERR_UNSUPPORTED) : int(RSX_OK);
   }
-  int run(rsx_ctx* ctx, DngPostCall& call, const rsx_dng_post_desc* desc, const rsx_image* img,
+  int run(rsx_ctx* ctx, CallPlan& call, const rsx_dng_post_desc* desc, const rsx_image* img,
           uint32_t* bad, uint32_t bad_cap, void* dev, hipStream_t s) {
     if (!on)
       return RSX_OK;
@@ -3232,7 +3221,7 @@ struct DngFixStage {
     d.positions = bad;
     d.n_positions = uint32_t(n);
     d.is_f32 = desc->is_f32;
-    if (int e = fix.create(ctx, &d, img))
+    if (int e = bad_pixels_call_create(ctx, &d, img, fix))
       return e;
     if (int e = d_pos.ensure(size_t(n) * 4 + 16))
       return e;
@@ -3244,14 +3233,10 @@ struct DngFixStage {
     return RSX_OK;
   }
   // the map, behind the download
-  int finish() { return ran && map_out ? fix.finish(nullptr, map_out) : int(RSX_OK); }
+  int finish() { return ran && map_out ? bad_pixels_finish(fix, nullptr, map_out) : int(RSX_OK); }
 };
-} // namespace
 
-// In place.  A device pointer: the pass runs on the context's stream, behind the null stream's
-// work so far, and the call returns when it is done.  A host pointer: the rows go up as one copy,
-// and come back through download_rects.
-namespace {
+// In place (in_place_call): the pass, then the stage `fix`.
 int dng_post_call(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* img,
                   rsx_dng_post_result* result, uint32_t* bad, uint32_t bad_cap, DngFixStage& fix) {
   if (!ctx || !desc || !img || !img->data || (!bad && bad_cap != 0))
@@ -3261,52 +3246,21 @@ int dng_post_call(rsx_ctx* ctx, const rsx_dng_post_desc* desc, const rsx_image* 
   if (fix.on)
     if (int st = DngFixStage::refuse(desc, img))
       return st;
-  DngPostCall call;
-  if (int st = call.create(ctx, desc, img, bad_cap))
+  CallPlan call;
+  if (int st = dng_post_call_create(ctx, desc, img, bad_cap, call))
     return st;
-  hipPointerAttribute_t attr;
-  std::memset(&attr, 0, sizeof attr);
-  bool on_device = false;
-  if (hipPointerGetAttributes(&attr, img->data) == hipSuccess)
-    on_device = attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-  else
-    (void)hipGetLastError(); // (plain host memory is unknown to the runtime)
-  if (on_device) {
-    if (int st = call.run(img->data, nullptr))
-      return st;
-    if (int st = fix.run(ctx, call, desc, img, bad, bad_cap, img->data, nullptr))
-      return st;
-    if (int st = fix.finish())
-      return st;
-    return call.finish(result, bad, bad_cap, true);
-  }
-  LaneGuard lane(ctx);
-  if (!lane.lane)
-    return RSX_ERR_DEVICE;
-  const size_t row_bytes = size_t(img->dim_x) * size_t(img->cpp) * (desc->is_f32 ? 4 : 2);
-  const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
-  if (int e = lane.lane->d_out.ensure(bytes + 64))
-    return e;
-  hipStream_t s = lane.lane->stream;
-  {
-    std::lock_guard<std::mutex> up(ctx->upload_mu);
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, img->data, bytes, hipMemcpyHostToDevice, s));
-  }
-  if (int st = call.run(lane.lane->d_out.ptr, s))
-    return st;
-  if (int st = fix.run(ctx, call, desc, img, bad, bad_cap, lane.lane->d_out.ptr, s))
-    return st;
-  DownRect dr{static_cast<uint8_t*>(img->data), img->pitch_bytes,
-              static_cast<const uint8_t*>(lane.lane->d_out.ptr), img->pitch_bytes, row_bytes,
-              size_t(img->dim_y)};
-  {
-    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
-    if (int e = download_rects(ctx, lane.lane, s, &dr, 1))
-      return e;
-  }
-  if (int st = fix.finish())
-    return st;
-  return call.finish(result, bad, bad_cap, true);
+  return in_place_call(
+      ctx, img, size_t(img->dim_x) * size_t(img->cpp) * (desc->is_f32 ? 4 : 2), nullptr, 0,
+      [&](const void*, void* dev, hipStream_t s) {
+        if (int st = dng_post_run(call, dev, s))
+          return st;
+        return fix.run(ctx, call, desc, img, bad, bad_cap, dev, s);
+      },
+      [&]() {
+        if (int st = fix.finish())
+          return st;
+        return dng_post_finish(call, result, bad, bad_cap, true);
+      });
 }
 } // namespace
 
@@ -3341,8 +3295,8 @@ int dng_ljpeg_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_ljpeg_tile* til
   if (fix.on)
     if (int st = DngFixStage::refuse(desc, img))
       return st;
-  DngPostCall call;
-  if (int st = call.create(ctx, desc, img, bad_cap))
+  CallPlan call;
+  if (int st = dng_post_call_create(ctx, desc, img, bad_cap, call))
     return st;
   std::vector<rsx_ljpeg_job> jobs(n_tiles);
   std::vector<const uint8_t*> ins(n_tiles);
@@ -3356,7 +3310,7 @@ int dng_ljpeg_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_ljpeg_tile* til
   std::vector<uint32_t> cons(n_tiles, 0);
   bool ran = false;
   const DevicePostFn post = [&](uint8_t* dev, hipStream_t s) {
-    int e = call.run(dev, s);
+    int e = dng_post_run(call, dev, s);
     if (e == RSX_OK)
       e = fix.run(ctx, call, desc, img, bad, bad_cap, dev, s);
     ran = e == RSX_OK;
@@ -3381,12 +3335,12 @@ int dng_ljpeg_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_ljpeg_tile* til
   if (tile_consumed)
     std::copy(cons.begin(), cons.end(), tile_consumed);
   if (tile_failed) {
-    call.finish(result, nullptr, 0, false);
+    dng_post_finish(call, result, nullptr, 0, false);
     return RSX_ERR_TILE_ERRORS; // (the plain call's verdict; nothing of the list was applied)
   }
   if (int e = fix.finish())
     return e;
-  return call.finish(result, bad, bad_cap, true);
+  return dng_post_finish(call, result, bad, bad_cap, true);
 }
 } // namespace
 
@@ -3433,8 +3387,8 @@ int dng_uncompressed_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_unpack_t
   if (fix.on)
     if (int st = DngFixStage::refuse(desc, img))
       return st;
-  DngPostCall call;
-  if (int st = call.create(ctx, desc, img, bad_cap))
+  CallPlan call;
+  if (int st = dng_post_call_create(ctx, desc, img, bad_cap, call))
     return st;
   std::vector<rsx_unpack_job> jobs(n_tiles);
   size_t in_total = 0;
@@ -3464,7 +3418,7 @@ int dng_uncompressed_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_unpack_t
                                 size_t(d.crop_w) * size_t(img->cpp) * 2};
   }
   if (plain) {
-    call.finish(result, nullptr, 0, false);
+    dng_post_finish(call, result, nullptr, 0, false);
     return rsx_dng_decompress_uncompressed(ctx, n_tiles, tiles, img, tile_status);
   }
   // (inside the image, disjoint, all of it: the pass needs the whole image, and a byte no tile
@@ -3489,17 +3443,18 @@ int dng_uncompressed_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_unpack_t
       RSX_HIP_CHECK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(lane.lane->d_in.ptr) + jobs[i].in_offset,
                                         tiles[i].in, jobs[i].in_bytes, hipMemcpyHostToDevice, s));
   }
-  rsx_plan* unpack = nullptr;
-  if (int e = rsx_unpack_plan_create(ctx, n_tiles, jobs.data(), &unpack))
-    return e;
   std::vector<int32_t> st(n_tiles, RSX_OK);
-  int rc = rsx_plan_run(unpack, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
-  if (rc == RSX_OK)
-    rc = rsx_plan_results(unpack, st.data(), nullptr);
-  rsx_plan_destroy(unpack);
-  if (rc != RSX_OK)
-    return rc; // (every tile validated: a device failure; tile_status untouched)
-  if (int e = call.run(lane.lane->d_out.ptr, s))
+  {
+    CallPlan unpack;
+    if (int e = rsx_unpack_plan_create(ctx, n_tiles, jobs.data(), &unpack.plan))
+      return e;
+    int rc = rsx_plan_run(unpack.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s);
+    if (rc == RSX_OK)
+      rc = rsx_plan_results(unpack.plan, st.data(), nullptr);
+    if (rc != RSX_OK)
+      return rc; // (every tile validated: a device failure; tile_status untouched)
+  }
+  if (int e = dng_post_run(call, lane.lane->d_out.ptr, s))
     return e;
   if (int e = fix.run(ctx, call, desc, img, bad, bad_cap, lane.lane->d_out.ptr, s))
     return e;
@@ -3516,7 +3471,7 @@ int dng_uncompressed_post_call(rsx_ctx* ctx, int n_tiles, const rsx_dng_unpack_t
     std::copy(st.begin(), st.end(), tile_status);
   if (int e = fix.finish())
     return e;
-  return call.finish(result, bad, bad_cap, true);
+  return dng_post_finish(call, result, bad, bad_cap, true);
 }
 } // namespace
 
@@ -3574,20 +3529,18 @@ extern "C" int rsx_sony_arw2_decompress(rsx_ctx* ctx, const rsx_sony_arw2_desc* 
     return st;
   const size_t span = size_t(img->dim_x) * size_t(img->dim_y);
   rsx_sony_arw2_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.desc.table_mode = desc->table_mode;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_sony_arw2_plan_create);
-  key_append(key, &job); // (desc.table is NULL here: not in the key)
+  // (desc.table is NULL here: not in the key)
+  std::vector<uint8_t> key = one_job_key(rsx_sony_arw2_plan_create, job);
   job.desc.table = desc->table;
   // this call's table onto a plan the lane held, ordered before the run on the lane's stream
+  SingleImageHooks hooks;
+  hooks.on_reuse = [desc](rsx_plan* plan, hipStream_t s) {
+    return sony_arw2_plan_set_table(plan->dec.get(), 0, desc, s);
+  };
   return single_image_host(ctx, key, rsx_sony_arw2_plan_create, job, in, span, img, row_status,
-                           [desc](rsx_plan* plan, hipStream_t s) {
-                             return sony_arw2_plan_set_table(plan->dec.get(), 0, desc, s);
-                           });
+                           hooks);
 }
 
 // ---------------------------------------------------------------------------
@@ -3617,21 +3570,19 @@ extern "C" int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc
     return st;
   const size_t span = size_t(img->dim_x) * size_t(img->dim_y) * 3u;
   rsx_nikon_snef_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.desc.inv_wb_r = desc->inv_wb_r;
   job.desc.inv_wb_b = desc->inv_wb_b;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_nikon_snef_plan_create);
-  key_append(key, &job); // (desc.table is NULL here: not in the key)
+  // (desc.table is NULL here: not in the key)
+  std::vector<uint8_t> key = one_job_key(rsx_nikon_snef_plan_create, job);
   job.desc.table = desc->table;
   // this call's table onto a plan the lane held, ordered before the run on the lane's stream
+  SingleImageHooks hooks;
+  hooks.on_reuse = [desc](rsx_plan* plan, hipStream_t s) {
+    return nikon_snef_plan_set_table(plan->dec.get(), 0, desc, s);
+  };
   return single_image_host(ctx, key, rsx_nikon_snef_plan_create, job, in, span, img, nullptr,
-                           [desc](rsx_plan* plan, hipStream_t s) {
-                             return nikon_snef_plan_set_table(plan->dec.get(), 0, desc, s);
-                           });
+                           hooks);
 }
 
 // ---------------------------------------------------------------------------
@@ -3650,10 +3601,8 @@ extern "C" int rsx_vc5_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_vc5_job* 
 
 extern "C" int rsx_vc5_plan_bands(rsx_plan* plan, int job, int32_t* band_status, uint32_t* windows,
                                   uint32_t* rounds) {
-  if (!plan || plan->kind != PLAN_DECODER)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
-  return vc5_plan_bands(plan->dec.get(), job, band_status, windows, rounds);
+  return decoder_plan_get(
+      plan, [&](DecoderPlan* d) { return vc5_plan_bands(d, job, band_status, windows, rounds); });
 }
 
 // The host-pointer call (single_image_host): the tile's bytes go up as one copy.  The plan is
@@ -3667,22 +3616,16 @@ extern "C" int rsx_vc5_decompress(rsx_ctx* ctx, const rsx_vc5_desc* desc, const 
   if (int st = vc5_validate(desc, *img, in_bytes))
     return st;
   rsx_vc5_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, in_bytes, img);
   job.desc = *desc;
   job.desc.log_table = nullptr;
   job.desc.codes = nullptr;
-  job.in_bytes = in_bytes;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_vc5_plan_create);
-  key_append(key, &job);
+  std::vector<uint8_t> key = one_job_key(rsx_vc5_plan_create, job);
   key_append(key, desc->codes, size_t(desc->n_codes));
   key_append(key, desc->log_table, size_t(4096));
   job.desc.log_table = desc->log_table;
   job.desc.codes = desc->codes;
-  return single_image_host(ctx, key, rsx_vc5_plan_create, job, in, in_bytes, img, nullptr,
-                           [](rsx_plan*, hipStream_t) { return int(RSX_OK); });
+  return single_image_host(ctx, key, rsx_vc5_plan_create, job, in, in_bytes, img, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -3711,16 +3654,10 @@ extern "C" int rsx_panasonic_decompress(rsx_ctx* ctx, const rsx_panasonic_desc* 
   if (int st = panasonic_validate(desc, *img, in_bytes, &span))
     return st;
   rsx_panasonic_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.desc = *desc;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_panasonic_plan_create);
-  key_append(key, &job);
-  return single_image_host(ctx, key, rsx_panasonic_plan_create, job, in, size_t(span), img, nullptr,
-                           [](rsx_plan*, hipStream_t) { return RSX_OK; });
+  std::vector<uint8_t> key = one_job_key(rsx_panasonic_plan_create, job);
+  return single_image_host(ctx, key, rsx_panasonic_plan_create, job, in, size_t(span), img, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -3742,10 +3679,7 @@ extern "C" int rsx_panasonic_v4_plan_bad_pixels(rsx_plan* plan, int job, uint32_
                                                 uint64_t* n_bad) {
   if (n_bad)
     *n_bad = 0;
-  if (!plan || plan->kind != PLAN_DECODER)
-    return RSX_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lock(plan->ctx->mu);
-  return plan->dec->bad_pixels(job, out, cap, n_bad);
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->bad_pixels(job, out, cap, n_bad); });
 }
 
 // The host-pointer call (single_image_host): the bytes the constructor's peekStream takes go up
@@ -3764,26 +3698,21 @@ extern "C" int rsx_panasonic_v4_decompress(rsx_ctx* ctx, const rsx_panasonic_v4_
   if (int st = panasonic_v4_validate(desc, *img, in_bytes, &span))
     return st;
   rsx_panasonic_v4_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.desc.section_split_offset = desc->section_split_offset;
   job.desc.zero_is_bad = desc->zero_is_bad != 0;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
   job.bad_cap = uint32_t(std::min<uint64_t>(bad_cap, uint64_t(img->dim_x) * uint64_t(img->dim_y)));
-  std::vector<uint8_t> key;
-  key_create(key, rsx_panasonic_v4_plan_create);
-  key_append(key, &job);
+  std::vector<uint8_t> key = one_job_key(rsx_panasonic_v4_plan_create, job);
   int list_rc = RSX_OK;
-  const int rc = single_image_host(
-      ctx, key, rsx_panasonic_v4_plan_create, job, in, size_t(span), img, nullptr,
-      [](rsx_plan*, hipStream_t) { return RSX_OK; },
-      [&](rsx_plan* plan, int st) {
-        if (st != RSX_OK && st != RSX_ERR_UNSUPPORTED)
-          return st;
-        list_rc = plan->dec->bad_pixels(0, bad, job.bad_cap, n_bad);
-        return list_rc == RSX_OK || list_rc == RSX_ERR_UNSUPPORTED ? int(RSX_OK) : list_rc;
-      });
+  SingleImageHooks hooks;
+  hooks.on_done = [&](rsx_plan* plan, int st) {
+    if (st != RSX_OK && st != RSX_ERR_UNSUPPORTED)
+      return st;
+    list_rc = plan->dec->bad_pixels(0, bad, job.bad_cap, n_bad);
+    return list_rc == RSX_OK || list_rc == RSX_ERR_UNSUPPORTED ? int(RSX_OK) : list_rc;
+  };
+  const int rc = single_image_host(ctx, key, rsx_panasonic_v4_plan_create, job, in, size_t(span),
+                                   img, nullptr, hooks);
   return rc != RSX_OK ? rc : list_rc;
 }
 
@@ -3818,18 +3747,13 @@ extern "C" int rsx_samsung_v0_decompress(rsx_ctx* ctx, const uint8_t* in, size_t
     o -= lo;
   const size_t span = in_bytes - lo;
   rsx_samsung_v0_job job;
-  std::memset(&job, 0, sizeof job);
+  one_job_init(job, span, img);
   job.n_offsets = img->dim_y;
-  job.in_bytes = span;
-  job.img = *img;
-  job.img.data = nullptr;
-  std::vector<uint8_t> key;
-  key_create(key, rsx_samsung_v0_plan_create);
-  key_append(key, &job);
+  std::vector<uint8_t> key = one_job_key(rsx_samsung_v0_plan_create, job);
   key_append(key, local.data(), local.size());
   job.row_offsets = local.data();
   return single_image_host(ctx, key, rsx_samsung_v0_plan_create, job, in + lo, span, img,
-                           row_status, [](rsx_plan*, hipStream_t) { return RSX_OK; });
+                           row_status);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,
