@@ -1332,6 +1332,110 @@ int rsx_dng_decompress_uncompressed_finish(rsx_ctx* ctx, int n_tiles,
                                            uint32_t* bad, uint32_t bad_cap, uint8_t* map_out);
 
 /* ------------------------------------------------------------------------ */
+/* 6. RawImageData::scaleBlackWhite: the third call of the documented flow   */
+/*    (common/RawImageDataU16.cpp:60-392, common/RawImageDataFloat.cpp:      */
+/*    51-170, common/RawImage.cpp:270-295, :339-371).                        */
+/*                                                                           */
+/*    img describes the UNCROPPED image; the descriptor carries what         */
+/*    RawImageData holds when the call is made, the result what the          */
+/*    reference leaves in its members.  Everything is as the code is         */
+/*    written, quirks included, and bit-exact against the reference          */
+/*    (tests/golden/scale_ref.json).  The row split of startWorker does not  */
+/*    enter the result: every row seeds its own generator.                   */
+/*                                                                           */
+/*    uint16, in this order:                                                 */
+/*    (1) the estimate, when (no areas, no separate levels and black_level   */
+/*    < 0) or has_white == 0: min and max over cropped rows 250 .. crop_y -  */
+/*    250 and cropped samples 250 + col, col in 250 .. (crop_x - 250) cpp    */
+/*    (the reference's double offset); an empty window gives 65536 and 0.    */
+/*    (2) the skip rule: (no areas, black_level 0, white 65535, no separate  */
+/*    levels) or an empty crop -> skipped = 1, the image untouched.          */
+/*    (3) calculateBlackAreas when no separate levels are given: sizes       */
+/*    rounded down to even; a horizontal area counts the single sample       */
+/*    img(y, off_x) once per cropped column into the histogram of the row    */
+/*    and column parity; a vertical area counts img(y, area.offset) once per */
+/*    column of the area; the cells are 16 bits and wrap; totalpixels / 8    */
+/*    and the median walk; not CFA: the rounded average; no counted pixel:   */
+/*    all four become black_level.                                           */
+/*    (4) the pass.  host_sse2 (WITH_SSE2 && Cpuid::SSE2() of the caller's   */
+/*    build) and app_scale = 65535.0F / (white - black_separate[0]) < 63:    */
+/*    the SSE2 variant (variant 1), over cropped rows and UNCROPPED samples  */
+/*    0 .. roundDown(dim_x, 8) of a row (for cpp > 1 only these first dim_x  */
+/*    samples): saturating subtraction, 10-bit multipliers packed two to a   */
+/*    word as written, black level bls(off_x & 1) for uncropped-even         */
+/*    columns, eight 16-bit generators a row stepped once per block of       */
+/*    eight.  Otherwise the plain variant (variant 0), over cropped samples  */
+/*    0 .. crop_x cpp, with the generator v = 18000 (v & 65535) + (v >> 16)  */
+/*    seeded crop_x + y 36969 per row.  Where its int arithmetic leaves      */
+/*    int32 (undefined in the reference) it wraps, and n_wrapped counts      */
+/*    those samples.  dither == 0: no generator in either.                   */
+/*                                                                           */
+/*    F32 (is_f32, variant 2): the estimate (no areas, no separate levels,   */
+/*    black_level < 0) is the minimum over cropped rows 150 cpp .. crop_y -  */
+/*    150, cropped samples 150 .. (crop_x - 150) cpp, converted with         */
+/*    static_cast<int>; no skip rule; the pass is (p - sub) * mul over the   */
+/*    cropped samples, two roundings.                                        */
+/*                                                                           */
+/*    rsx_scale_validate, in this order: desc or img NULL (or areas NULL     */
+/*    with n_areas != 0); cpp < 1, dim_x or dim_y <= 0, pitch_bytes below    */
+/*    dim_x cpp samples or no multiple of the sample size; a crop outside    */
+/*    the image -> RSX_ERR_INVALID_ARG; dim_x or dim_y > 65536 (or cpp > 4)  */
+/*    -> RSX_ERR_UNSUPPORTED; F32 with has_white == 0 (the reference            */
+/*    dereferences it) or with areas (its answer is a sequential binary32    */
+/*    sum) -> RSX_ERR_UNSUPPORTED; uint16, when the areas would be used: an  */
+/*    area past the image (the reference's ThrowRDE) -> RSX_ERR_INVALID_ARG. */
+/*    Then, from the image, after the estimate and the areas and before      */
+/*    anything is written: F32 with a NaN inside the estimate window         */
+/*    (std::min's result would depend on the scan order) or a minimum below  */
+/*    int -> RSX_ERR_UNSUPPORTED; white - black_separate[i] <= 0 for any i   */
+/*    (the reference's division by zero or negative scale) ->                */
+/*    RSX_ERR_UNSUPPORTED; plain variant with a row seed crop_x + y 36969    */
+/*    past INT32_MAX -> RSX_ERR_UNSUPPORTED.  On any status but RSX_OK the   */
+/*    image is untouched, the result zero, and the caller keeps the host     */
+/*    path.                                                                  */
+/*    rsx_scale_black_white works in place; img->data may be a host pointer  */
+/*    (the rows go up and come back) or a device pointer (the call returns   */
+/*    when the pass is done).  Every step runs on the device without a host  */
+/*    round trip in between; areas is host memory.                           */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_scale_area {
+  uint32_t offset;
+  uint32_t size;
+  int32_t is_vertical;
+  int32_t reserved;
+} rsx_scale_area;
+
+typedef struct rsx_scale_desc {
+  int32_t off_x, off_y;   /* mOffset */
+  int32_t crop_x, crop_y; /* dim */
+  int32_t is_f32;
+  int32_t black_level; /* -1: unset */
+  int32_t has_white;
+  int32_t white_point;
+  int32_t has_separate;
+  int32_t black_separate[4];
+  uint32_t n_areas;
+  const rsx_scale_area* areas; /* may be NULL with n_areas 0 */
+  int32_t dither;              /* mDitherScale */
+  int32_t host_sse2;
+} rsx_scale_desc;
+
+typedef struct rsx_scale_result {
+  int32_t black_level;
+  int32_t white_point;
+  int32_t black_separate[4];
+  int32_t estimated; /* the estimate ran */
+  int32_t skipped;   /* "skip, if not needed": the image is untouched */
+  int32_t variant;   /* 0 plain, 1 SSE2, 2 F32 */
+  int32_t reserved;
+  uint64_t n_wrapped;
+} rsx_scale_result;
+
+int rsx_scale_validate(const rsx_scale_desc* desc, const rsx_image* img);
+int rsx_scale_black_white(rsx_ctx* ctx, const rsx_scale_desc* desc, const rsx_image* img,
+                          rsx_scale_result* result);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */
@@ -1552,6 +1656,18 @@ typedef struct rsx_bad_pixels_job {
   rsx_image img; /* .data ignored */
 } rsx_bad_pixels_job;
 
+/* one image's black/white scaling (section 6), in place on the plan's OUTPUT buffer at img_offset
+ * (a multiple of the sample size); the input buffer is not read.  The areas are copied at plan
+ * creation.  Jobs of different geometry and variant may share a plan.  A job rsx_scale_validate
+ * refuses fails the creation with that status; what only the image can decide (section 6) makes
+ * the job RSX_ERR_UNSUPPORTED in rsx_plan_results and leaves its image untouched.  The plan owns
+ * the histograms and the generator checkpoints of its jobs. */
+typedef struct rsx_scale_job {
+  rsx_scale_desc desc;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_scale_job;
+
 /* one VC-5 tile (section 4c): band offsets count from in_offset; the code book and the log table
  * are copied at plan creation.  Jobs of different geometry, book and table may share a plan; any
  * in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset.  The band decode loads a
@@ -1641,6 +1757,11 @@ int rsx_bad_pixels_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_bad_pixels_jo
 /* Bad-pixel plans, after rsx_plan_results: the counts of job `job` of the last run.
  * RSX_ERR_INVALID_ARG for another plan, a job out of range or before results. */
 int rsx_bad_pixels_plan_result(rsx_plan* plan, int job, rsx_bad_pixels_result* out);
+int rsx_scale_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_scale_job* jobs, rsx_plan** out_plan);
+/* Scaling plans, after rsx_plan_results: the levels and the verdict of job `job` of the last run
+ * (zero for a refused job).  RSX_ERR_INVALID_ARG for another plan, a job out of range or before
+ * results. */
+int rsx_scale_plan_result(rsx_plan* plan, int job, rsx_scale_result* out);
 /* After rsx_plan_results of a VC-5 plan: per band of job `job` ([channel][subband], 40 entries
  * each; any may be NULL) its status, and for the high-pass bands the 128-Kbit windows the band
  * decode walked and the parse rounds it took over all of them (a round is one parse of every

@@ -469,6 +469,55 @@ def bad_pixels_desc(positions, dim, map_in=None, is_f32=False, want_map=True, ma
     return d, keep, out
 
 
+class ScaleArea(C.Structure):
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32), ("is_vertical", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ScaleDesc(C.Structure):
+    _fields_ = [("off_x", C.c_int32), ("off_y", C.c_int32), ("crop_x", C.c_int32),
+                ("crop_y", C.c_int32), ("is_f32", C.c_int32), ("black_level", C.c_int32),
+                ("has_white", C.c_int32), ("white_point", C.c_int32), ("has_separate", C.c_int32),
+                ("black_separate", C.c_int32 * 4), ("n_areas", C.c_uint32), ("areas", C.c_void_p),
+                ("dither", C.c_int32), ("host_sse2", C.c_int32)]
+
+
+class ScaleResult(C.Structure):
+    _fields_ = [("black_level", C.c_int32), ("white_point", C.c_int32),
+                ("black_separate", C.c_int32 * 4), ("estimated", C.c_int32), ("skipped", C.c_int32),
+                ("variant", C.c_int32), ("reserved", C.c_int32), ("n_wrapped", C.c_uint64)]
+
+    def levels(self):
+        return (self.black_level, self.white_point, tuple(self.black_separate))
+
+
+class ScaleJob(C.Structure):
+    _fields_ = [("desc", ScaleDesc), ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def scale_desc(crop, black_level=-1, white_point=None, black_separate=None, areas=(), dither=True,
+               host_sse2=True, is_f32=False):
+    """(rsx_scale_desc, keep-alive objects).  crop: (off_x, off_y, crop_x, crop_y); white_point and
+    black_separate: None when unset; areas: (offset, size, is_vertical) triples."""
+    d = ScaleDesc()
+    d.off_x, d.off_y, d.crop_x, d.crop_y = crop
+    d.is_f32 = int(is_f32)
+    d.black_level = black_level
+    d.has_white = int(white_point is not None)
+    d.white_point = 0 if white_point is None else white_point
+    d.has_separate = int(black_separate is not None)
+    if black_separate is not None:
+        d.black_separate[:] = list(black_separate)
+    keep = []
+    if len(areas):
+        arr = (ScaleArea * len(areas))(*[ScaleArea(o, s, int(v), 0) for o, s, v in areas])
+        d.areas, d.n_areas = C.addressof(arr), len(areas)
+        keep.append(arr)
+    d.dither = int(dither)
+    d.host_sse2 = int(host_sse2)
+    return d, keep
+
+
 class PanasonicV4Desc(C.Structure):
     _fields_ = [("section_split_offset", C.c_uint32), ("zero_is_bad", C.c_int32)]
 

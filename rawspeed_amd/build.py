@@ -12,6 +12,8 @@
                                 the DNG opcode / look-up core (rsx_dng_post_core.h) as host C++ (g++)
   rawspeed_amd/librsx_bad_pixels_host.so, rawspeed_amd/rsx_bad_pixels_host_check
                                 the bad-pixel core (rsx_bad_pixels_core.h) as host C++ (g++)
+  rawspeed_amd/librsx_scale_host.so, rawspeed_amd/rsx_scale_host_check
+                                the black/white scaling core (rsx_scale_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -37,12 +39,15 @@ LIB_DNG_POST_HOST = os.path.join(PKG, "librsx_dng_post_host.so")
 BIN_DNG_POST_CHECK = os.path.join(PKG, "rsx_dng_post_host_check")
 LIB_BAD_PIXELS_HOST = os.path.join(PKG, "librsx_bad_pixels_host.so")
 BIN_BAD_PIXELS_CHECK = os.path.join(PKG, "rsx_bad_pixels_host_check")
+LIB_SCALE_HOST = os.path.join(PKG, "librsx_scale_host.so")
+BIN_SCALE_CHECK = os.path.join(PKG, "rsx_scale_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
                 "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_vc5.hip",
-                "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_host.cpp"]
+                "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_scale.hip",
+                "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
@@ -50,7 +55,7 @@ CORE_HEADERS = ["rsx_internal.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", 
                 "rsx_inflate_core.h", "rsx_fp_widen.h", "rsx_dither_dev.h", "rsx_nikon_snef.h",
                 "rsx_vc5.h", "rsx_vc5_core.h", "rsx_iiq_corr.h", "rsx_iiq_corr_core.h",
                 "rsx_dng_post.h", "rsx_dng_post_core.h", "rsx_bad_pixels.h",
-                "rsx_bad_pixels_core.h"]
+                "rsx_bad_pixels_core.h", "rsx_scale.h", "rsx_scale_core.h"]
 
 
 def _hipcc():
@@ -155,6 +160,13 @@ def build_bad_pixels_host(force=False):
                             ["-pthread"] + _NO_CONTRACT, force)
 
 
+def build_scale_host(force=False):
+    """rsx_scale_core.h, without contraction"""
+    return _build_host_core(LIB_SCALE_HOST, BIN_SCALE_CHECK, "rsx_scale_host.cpp",
+                            ["rsx_scale_core.h", "rsx_dither_dev.h", _RSX_H], "RSX_SCALE_HOST_MAIN",
+                            _NO_CONTRACT, force)
+
+
 def _compile_objects(objdir, extra_flags, force=False):
     """One object per source under `objdir`, rebuilt when the source or any header is newer;
     the stale ones in parallel (the sources are independent translation units: one hipcc run
@@ -210,7 +222,7 @@ def build_variant(name, extra_flags):
 def build_all(force=False):
     return (build_core(force), build_synth(force), build_inflate_host(force),
             build_vc5_host(force), build_iiq_corr_host(force), build_dng_post_host(force),
-            build_bad_pixels_host(force))
+            build_bad_pixels_host(force), build_scale_host(force))
 
 
 if __name__ == "__main__":

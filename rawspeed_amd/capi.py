@@ -45,6 +45,7 @@ EXPORTS = [
     "rsx_dng_post_plan_result", "rsx_dng_post_plan_bad_pixels",
     "rsx_bad_pixels_validate", "rsx_bad_pixels_fix", "rsx_panasonic_v4_decompress_fixed",
     "rsx_bad_pixels_plan_create", "rsx_bad_pixels_plan_result",
+    "rsx_scale_validate", "rsx_scale_black_white", "rsx_scale_plan_create", "rsx_scale_plan_result",
     "rsx_dng_finish", "rsx_dng_decompress_ljpeg_finish", "rsx_dng_decompress_uncompressed_finish",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
@@ -151,6 +152,9 @@ def lib():
                                                         C.c_size_t, C.c_void_p, C.c_void_p,
                                                         C.c_uint32, C.c_void_p]
         L.rsx_bad_pixels_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_scale_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_scale_black_white.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_scale_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_dng_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_uint32, C.c_void_p]
         L.rsx_dng_decompress_ljpeg_finish.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -192,7 +196,8 @@ def lib():
                      "rsx_samsung_v0_plan_create", "rsx_panasonic_v4_plan_create",
                      "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
                      "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
-                     "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create"):
+                     "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
+                     "rsx_scale_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -280,6 +285,12 @@ def dng_post_validate(desc, img_view, bad_cap=1 << 16):
                                      None if img_view is None else C.byref(img_view),
                                      C.byref(r), buf, bad_cap)
     return st, r, _bad_out(r, buf, st)
+
+
+def scale_validate(desc, img_view):
+    """rsx_scale_validate; desc: abi.ScaleDesc (abi.scale_desc), None passes NULL"""
+    return lib().rsx_scale_validate(None if desc is None else C.byref(desc),
+                                    None if img_view is None else C.byref(img_view))
 
 
 def bad_pixels_validate(desc, img_view):
@@ -696,6 +707,18 @@ class Context:
         creation); runs in place on the output buffer"""
         return BadPixelsPlan(self, "rsx_bad_pixels_plan_create", abi.BadPixelsJob, jobs)
 
+    def scale_black_white(self, desc, img_view):
+        """desc: abi.ScaleDesc; img_view describes the uncropped image, .data a host or a device
+        pointer; in place.  Returns (status, abi.ScaleResult)."""
+        r = abi.ScaleResult()
+        st = lib().rsx_scale_black_white(self._h, C.byref(desc), C.byref(img_view), C.byref(r))
+        return st, r
+
+    def scale_plan(self, jobs):
+        """jobs: abi.ScaleJob (their areas are copied at plan creation); runs in place on the
+        output buffer"""
+        return ScalePlan(self, "rsx_scale_plan_create", abi.ScaleJob, jobs)
+
     def sony_arw2_plan(self, jobs):
         """jobs: abi.SonyArw2Job (their tables are copied at plan creation)"""
         return Plan(self, "rsx_sony_arw2_plan_create", abi.SonyArw2Job, jobs)
@@ -812,6 +835,14 @@ class BadPixelsPlan(Plan):
         """after results(): (status, abi.BadPixelsResult) of job `job`"""
         r = abi.BadPixelsResult()
         st = lib().rsx_bad_pixels_plan_result(self._h, job, C.byref(r))
+        return st, r
+
+
+class ScalePlan(Plan):
+    def result(self, job):
+        """after results(): (status, abi.ScaleResult) of job `job`"""
+        r = abi.ScaleResult()
+        st = lib().rsx_scale_plan_result(self._h, job, C.byref(r))
         return st, r
 
 

@@ -19,6 +19,7 @@
 #include "rsx_iiq_corr.h"
 #include "rsx_dng_post.h"
 #include "rsx_bad_pixels.h"
+#include "rsx_scale.h"
 
 #include <algorithm>
 #include <map>
@@ -3076,6 +3077,48 @@ extern "C" int rsx_bad_pixels_fix(rsx_ctx* ctx, const rsx_bad_pixels_desc* desc,
       size_t(desc->n_positions) * 4,
       [&](const void* pos_dev, void* dev, hipStream_t s) { return call.run(pos_dev, dev, s); },
       [&]() { return bad_pixels_finish(call, result, desc->map_out); });
+}
+
+// ---------------------------------------------------------------------------
+// RawImageData::scaleBlackWhite
+// ---------------------------------------------------------------------------
+extern "C" int rsx_scale_validate(const rsx_scale_desc* desc, const rsx_image* img) {
+  return scale_validate(desc, img);
+}
+
+extern "C" int rsx_scale_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_scale_job* jobs,
+                                     rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, scale_plan_create);
+}
+
+extern "C" int rsx_scale_plan_result(rsx_plan* plan, int job, rsx_scale_result* out) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->scale_result(job, out); });
+}
+
+// In place (in_place_call): the estimate and the areas read the whole image, so the rows go up as
+// one copy in front of the six launches.
+extern "C" int rsx_scale_black_white(rsx_ctx* ctx, const rsx_scale_desc* desc, const rsx_image* img,
+                                     rsx_scale_result* result) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !desc || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = scale_validate(desc, img))
+    return st;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  auto job = std::make_unique<rsx_scale_job>();
+  std::memset(job.get(), 0, sizeof(rsx_scale_job));
+  job->desc = *desc;
+  job->img = *img;
+  job->img.data = nullptr;
+  CallPlan call;
+  if (int st = rsx_scale_plan_create(ctx, 1, job.get(), &call.plan))
+    return st;
+  return in_place_call(
+      ctx, img, size_t(img->dim_x) * size_t(img->cpp) * (desc->is_f32 ? 4 : 2), nullptr, 0,
+      [&](const void*, void* dev, hipStream_t s) { return call.run(nullptr, dev, s); },
+      [&]() { return result ? call.plan->dec->scale_result(0, result) : int(RSX_OK); });
 }
 
 // rsx_panasonic_v4_decompress, the map marked from the zero pixels of the decoded image and the

@@ -200,6 +200,8 @@ struct DecoderPlan {
   virtual int bad_pixels_map(int /*job*/, uint8_t* /*out*/, hipStream_t) {
     return RSX_ERR_INVALID_ARG;
   }
+  // the levels and the verdict of job `job` of the last run, after results (scaling plans)
+  virtual int scale_result(int /*job*/, rsx_scale_result* /*out*/) { return RSX_ERR_INVALID_ARG; }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };
