@@ -1043,6 +1043,89 @@ int rsx_vc5_decompress(rsx_ctx* ctx, const rsx_vc5_desc* desc, const uint8_t* in
                        const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 4e. AbstractDngDecompressor, compression 0x884c: lossy (baseline) JPEG    */
+/*    (placed here, next to the other tile codecs; 4d was taken)             */
+/*    replaces JpegDecompressor::decode(offX, offY) (decompressThread        */
+/*    <0x884c> -> decompressors/JpegDecompressor.cpp:128-170): libjpeg's     */
+/*    jpeg_read_header and jpeg_start_decompress with every default left     */
+/*    alone (JDCT_ISLOW, fancy upsampling, RGB out for three components,     */
+/*    grey for one), all scanlines, then the first min(dim_x - off_x, width) */
+/*    pixels of the first min(dim_y - off_y, height) rows widened to 16 bits */
+/*    at (off_y, cpp * off_x).  Nothing else of the image is written, its    */
+/*    pitch padding included.  "libjpeg" is libjpeg-turbo's default decoder, */
+/*    bit for bit; IJG libjpeg 9 upsamples differently.                      */
+/*    rsx_dng_jpeg_validate, in this order: no tile, no bytes, an image that */
+/*    cannot hold 16-bit samples (no pixels, cpp < 1, an odd pitch_bytes,    */
+/*    pitch_bytes < 2 cpp dim_x), off_x >= dim_x or off_y >= dim_y           */
+/*    -> RSX_ERR_INVALID_ARG; a tile of 4 GiB or more -> RSX_ERR_UNSUPPORTED;*/
+/*    then the markers up to SOS in stream order:                            */
+/*      RSX_ERR_IO           no SOI; a marker that is not there; a segment   */
+/*                           past the end; a DQT or DHT index above 3, a Pq  */
+/*                           above 1, a short table; a second SOF; a         */
+/*                           precision other than 8 or 12; zero dimensions   */
+/*                           or components; a sampling factor outside 1..4;  */
+/*                           an SOS without SOF, with an unknown component,  */
+/*                           or naming a table that is not there; EOI or     */
+/*                           RSTn in the header                              */
+/*      RSX_ERR_UNSUPPORTED  SOF2 and above (progressive, lossless,          */
+/*                           arithmetic); 12 bits; two or four components; a */
+/*                           scan that does not hold all components in frame */
+/*                           order (several scans); Ss, Se, Ah, Al other     */
+/*                           than 0, 63, 0, 0; sampling other than luma      */
+/*                           h, v in {1, 2} (not 1 x 2) with both chroma     */
+/*                           1 x 1, or all 1 x 1 for RGB                     */
+/*    then components != cpp -> RSX_ERR_INVALID_ARG (the reference's         */
+/*    ThrowRDE), and Huffman counts that are no prefix code or a DC symbol   */
+/*    above 15 -> RSX_ERR_IO.                                                */
+/*    The colour space is default_decompress_parms': one component is grey;  */
+/*    of three, JFIF seen -> YCbCr; else Adobe seen -> transform 0 RGB,      */
+/*    otherwise YCbCr; else ids 'R','G','B' -> RGB, anything else YCbCr.     */
+/*    Per-tile status of a run, the largest over the tile's segments (a      */
+/*    segment is the scan, or one restart interval).  Where libjpeg warns    */
+/*    and goes on, the tile is refused:                                      */
+/*      RSX_ERR_BAD_HUFFMAN_CODE  a code that is not in the table; a         */
+/*                                coefficient index past 63                  */
+/*      RSX_ERR_RESTART_MARKER    a marker in the data that is not the RSTn  */
+/*                                expected (modulo 8) at a restart interval  */
+/*      RSX_ERR_INPUT_OVERFLOW    data that ends before the last MCU, or     */
+/*                                inside a segment; no EOI                   */
+/*      RSX_ERR_UNSUPPORTED       a DC value outside 16 bits, a dequantised  */
+/*                                coefficient or a value behind the column   */
+/*                                pass outside +-16383 (what no encoder      */
+/*                                makes from 8-bit pixels, and where         */
+/*                                libjpeg-turbo's SIMD and C code differ)    */
+/*    Bytes behind EOI, and bytes of a segment behind its last MCU, are      */
+/*    ignored.  A tile that is not RSX_OK writes NOTHING into the image; the */
+/*    others are written.  The call returns RSX_ERR_TILE_ERRORS if any tile  */
+/*    failed.  One upload of the packed tile bytes, one launch sequence, one */
+/*    download; one host call in rsx_ctx_host_calls.                         */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_dng_jpeg_tile {
+  const uint8_t* in; /* the tile's JPEG stream, SOI first */
+  size_t in_bytes;
+  uint32_t off_x, off_y; /* e.offX, e.offY: pixels */
+} rsx_dng_jpeg_tile;
+
+#define RSX_JPEG_GREY 0
+#define RSX_JPEG_YCBCR 1
+#define RSX_JPEG_RGB 2
+
+typedef struct rsx_dng_jpeg_info {
+  uint32_t width, height;    /* the frame's */
+  int32_t components;        /* 1 or 3 = output_components */
+  int32_t h_samp, v_samp;    /* of the first component against the others */
+  int32_t colour_space;      /* RSX_JPEG_*: what the stream holds */
+  uint32_t restart_interval; /* MCUs, 0: none */
+  uint32_t n_segments;       /* entropy segments = wavefronts of the block kernel */
+} rsx_dng_jpeg_info;
+
+/* `info` may be NULL; it is filled when the status is RSX_OK */
+int rsx_dng_jpeg_validate(const rsx_dng_jpeg_tile* tile, const rsx_image* img,
+                          rsx_dng_jpeg_info* info);
+int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles,
+                            const rsx_image* img, int32_t* tile_status);
+
+/* ------------------------------------------------------------------------ */
 /* 4d. DngDecoder behind the tiles: OpcodeList1 and the LinearizationTable   */
 /*    replaces, in DngDecoder::handleMetadata (decoders/DngDecoder.cpp       */
 /*    :591-615), DngOpcodes::applyOpCodes (common/DngOpcodes.cpp) and        */
@@ -1698,6 +1781,24 @@ typedef struct rsx_dng_deflate_job {
   rsx_image img; /* .data ignored */
 } rsx_dng_deflate_job;
 
+/* the tiles of one lossy-JPEG DNG image (section 4e).  The headers, the tables and the restart
+ * markers are read from the HOST bytes of `tiles` while the plan is made; a run expects the same
+ * bytes of tile t at in_offsets[t] of its input.  The plan owns the component planes of all its
+ * tiles (whole MCUs); more than 1 GiB of them: RSX_ERR_UNSUPPORTED at creation.  The job's status
+ * is RSX_ERR_TILE_ERRORS if a tile failed; rsx_dng_jpeg_plan_tile_status has the tiles'. */
+typedef struct rsx_dng_jpeg_job {
+  int32_t n_tiles;
+  const rsx_dng_jpeg_tile* tiles;
+  const uint64_t* in_offsets;
+  uint64_t img_offset; /* a multiple of 2 */
+  rsx_image img;       /* .data ignored */
+} rsx_dng_jpeg_job;
+
+int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
+                             rsx_plan** out_plan);
+/* After rsx_plan_results: the n_tiles statuses of job `job` of the last run.
+ * RSX_ERR_INVALID_ARG for another plan or a job out of range. */
+int rsx_dng_jpeg_plan_tile_status(rsx_plan* plan, int job, int32_t* tile_status);
 int rsx_unpack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_unpack_job* jobs,
                            rsx_plan** out_plan);
 /* F32 images: same job structure, img describes 4-byte samples */

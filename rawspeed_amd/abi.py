@@ -568,6 +568,54 @@ class DngDeflateJob(C.Structure):
                 ("img_offset", C.c_uint64), ("img", Image)]
 
 
+class DngJpegTile(C.Structure):
+    """one lossy-JPEG tile: its stream and (offX, offY) in pixels (include/rsx.h section 4e)"""
+    _fields_ = [("in_", C.c_void_p), ("in_bytes", C.c_size_t),
+                ("off_x", C.c_uint32), ("off_y", C.c_uint32)]
+
+
+JPEG_GREY, JPEG_YCBCR, JPEG_RGB = 0, 1, 2
+
+
+class DngJpegInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_int32),
+                ("h_samp", C.c_int32), ("v_samp", C.c_int32), ("colour_space", C.c_int32),
+                ("restart_interval", C.c_uint32), ("n_segments", C.c_uint32)]
+
+
+class DngJpegJob(C.Structure):
+    """the tiles of one image; the host bytes of `tiles` are read while the plan is made"""
+    _fields_ = [("n_tiles", C.c_int32), ("tiles", C.POINTER(DngJpegTile)),
+                ("in_offsets", C.POINTER(C.c_uint64)), ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def dng_jpeg_tiles(streams, offsets):
+    """streams: bytes-like per tile; offsets: (off_x, off_y) per tile -> (ctypes array, keep-alive)"""
+    keep = [np.ascontiguousarray(np.frombuffer(bytes(s), np.uint8)) for s in streams]
+    arr = (DngJpegTile * max(1, len(keep)))()
+    for i, (a, (ox, oy)) in enumerate(zip(keep, offsets)):
+        arr[i].in_, arr[i].in_bytes, arr[i].off_x, arr[i].off_y = a.ctypes.data, a.size, ox, oy
+    return arr, keep
+
+
+def dng_jpeg_job(streams, offsets, img_view, img_offset=0, in_base=0, align=16):
+    """One plan job: the streams packed back to back from `in_base` (units of `align` bytes).
+    Returns (job, keep-alive, the packed input bytes of this job as a uint8 array)."""
+    tiles, keep = dng_jpeg_tiles(streams, offsets)
+    offs = (C.c_uint64 * max(1, len(keep)))()
+    at = in_base
+    for i, a in enumerate(keep):
+        offs[i] = at
+        at += (a.size + align - 1) // align * align
+    packed = np.zeros(at - in_base, np.uint8)
+    for i, a in enumerate(keep):
+        packed[offs[i] - in_base:offs[i] - in_base + a.size] = a
+    j = DngJpegJob()
+    j.n_tiles, j.tiles, j.in_offsets, j.img_offset = len(keep), tiles, offs, img_offset
+    j.img = img_view
+    return j, (tiles, keep, offs), packed
+
+
 def phase_one_strips(table):
     """[(row, offset, bytes)] -> a ctypes array of rsx_phase_one_strip"""
     arr = (PhaseOneStrip * max(1, len(table)))()

@@ -49,6 +49,8 @@ EXPORTS = [
     "rsx_dng_finish", "rsx_dng_decompress_ljpeg_finish", "rsx_dng_decompress_uncompressed_finish",
     "rsx_dng_decompress_ljpeg", "rsx_dng_decompress_uncompressed",
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
+    "rsx_dng_jpeg_validate", "rsx_dng_decompress_jpeg", "rsx_dng_jpeg_plan_create",
+    "rsx_dng_jpeg_plan_tile_status",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -172,6 +174,10 @@ def lib():
         L.rsx_dng_deflate_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_dng_decompress_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]
+        L.rsx_dng_jpeg_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_dng_decompress_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+        L.rsx_dng_jpeg_plan_tile_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -197,7 +203,7 @@ def lib():
                      "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
                      "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
                      "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
-                     "rsx_scale_plan_create"):
+                     "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -320,6 +326,14 @@ def dng_deflate_validate(bps, predictor, geom, in_bytes, img_view):
     d = abi.DngDeflateDesc(bps, predictor)
     t = dng_deflate_tile(geom, in_bytes)
     return lib().rsx_dng_deflate_validate(C.byref(d), C.byref(t), C.byref(img_view))
+
+
+def dng_jpeg_validate(stream, off, img_view):
+    """rsx_dng_jpeg_validate of one tile; off = (off_x, off_y).  Returns (status, abi.DngJpegInfo)."""
+    tiles, keep = abi.dng_jpeg_tiles([stream], [off])
+    info = abi.DngJpegInfo()
+    st = lib().rsx_dng_jpeg_validate(tiles, C.byref(img_view), C.byref(info))
+    return st, info
 
 
 def _u8(a):
@@ -633,6 +647,15 @@ class Context:
         rc = lib().rsx_dng_decompress_deflate(self._h, C.byref(d), n, tiles, C.byref(img_view), st)
         return rc, list(st)
 
+    def dng_decompress_jpeg(self, streams, offsets, img_view):
+        """streams: the tiles' JPEG streams; offsets: (off_x, off_y) per tile, pixels.  Returns
+        (status, per-tile statuses)."""
+        n = len(streams)
+        tiles, keep = abi.dng_jpeg_tiles(streams, offsets)
+        st = (C.c_int32 * n)()
+        rc = lib().rsx_dng_decompress_jpeg(self._h, n, tiles, C.byref(img_view), st)
+        return rc, list(st)
+
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)
         arrs = [_u8(d) for d in datas]
@@ -747,6 +770,10 @@ class Context:
         """jobs: abi.DngDeflateJob, one per tile (depths, predictors and images may mix)"""
         return Plan(self, "rsx_dng_deflate_plan_create", abi.DngDeflateJob, jobs)
 
+    def dng_jpeg_plan(self, jobs):
+        """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""
+        return DngJpegPlan(self, "rsx_dng_jpeg_plan_create", abi.DngJpegJob, jobs)
+
     def pentax_plan(self, jobs):
         return Plan(self, "rsx_pentax_plan_create", abi.PentaxJob, jobs)
 
@@ -844,6 +871,14 @@ class ScalePlan(Plan):
         r = abi.ScaleResult()
         st = lib().rsx_scale_plan_result(self._h, job, C.byref(r))
         return st, r
+
+
+class DngJpegPlan(Plan):
+    def tile_status(self, job, n_tiles):
+        """after results(): (status, the statuses of the job's tiles)"""
+        st = (C.c_int32 * max(1, n_tiles))()
+        rc = lib().rsx_dng_jpeg_plan_tile_status(self._h, job, st)
+        return rc, list(st)[:n_tiles]
 
 
 class PanasonicV4Plan(Plan):

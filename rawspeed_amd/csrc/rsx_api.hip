@@ -20,6 +20,8 @@
 #include "rsx_dng_post.h"
 #include "rsx_bad_pixels.h"
 #include "rsx_scale.h"
+#include "rsx_dng_jpeg.h"
+#include "rsx_jpeg_core.h"
 
 #include <algorithm>
 #include <map>
@@ -2814,6 +2816,135 @@ extern "C" int rsx_dng_decompress_deflate(rsx_ctx* ctx, const rsx_dng_deflate_de
     std::copy(st.begin(), st.end(), tile_status);
   if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM)
     return rc;
+  for (int i = 0; i < n_tiles; ++i)
+    if (st[i] != RSX_OK)
+      return RSX_ERR_TILE_ERRORS; // AbstractDngDecompressor.cpp:247-251
+  return RSX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// AbstractDngDecompressor, compression 0x884c (lossy JPEG)
+// ---------------------------------------------------------------------------
+extern "C" int rsx_dng_jpeg_validate(const rsx_dng_jpeg_tile* tile, const rsx_image* img,
+                                     rsx_dng_jpeg_info* info) {
+  return rsx_jpeg::validate_call(tile, img, info);
+}
+
+extern "C" int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
+                                        rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, dng_jpeg_plan_create);
+}
+
+extern "C" int rsx_dng_jpeg_plan_tile_status(rsx_plan* plan, int job, int32_t* tile_status) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) {
+    return d->row_status(plan->last_stream, job, tile_status);
+  });
+}
+
+// The host-pointer call: the tiles' bytes packed into one upload, one run of a plan made for the
+// call (its key would be the streams themselves), the windows of the tiles that decoded back
+// through download_rects -- as one rectangle where they fill their bounding box.
+extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles,
+                                       const rsx_image* img, int32_t* tile_status) {
+  if (!ctx || !tiles || n_tiles < 1 || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  if (img->dim_x <= 0 || img->dim_y <= 0 || img->pitch_bytes == 0)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  std::vector<uint64_t> offs(n_tiles);
+  size_t in_total = 0;
+  for (int i = 0; i < n_tiles; ++i) {
+    if (!tiles[i].in || tiles[i].in_bytes >= (uint64_t(1) << 32))
+      return tiles[i].in ? RSX_ERR_UNSUPPORTED : RSX_ERR_INVALID_ARG;
+    offs[i] = in_total;
+    in_total += align_up(tiles[i].in_bytes + 64, 16);
+  }
+  rsx_dng_jpeg_job job;
+  std::memset(&job, 0, sizeof job);
+  job.n_tiles = n_tiles;
+  job.tiles = tiles;
+  job.in_offsets = offs.data();
+  job.img = *img;
+  job.img.data = nullptr;
+  CallPlan cp;
+  if (int st = rsx_dng_jpeg_plan_create(ctx, 1, &job, &cp.plan))
+    return st;
+  const std::vector<JpegWindow>& win = dng_jpeg_plan_windows(cp.plan->dec.get(), 0);
+  // the output staging holds the image rows the windows cover
+  size_t row_lo = size_t(img->dim_y), row_hi = 0;
+  for (const JpegWindow& w : win)
+    if (w.host_status == RSX_OK) {
+      row_lo = std::min(row_lo, size_t(w.off_y));
+      row_hi = std::max(row_hi, size_t(w.off_y) + w.copy_h);
+    }
+  std::vector<int32_t> st(n_tiles, RSX_OK);
+  int rc = RSX_OK;
+  if (row_hi > row_lo) {
+    RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    LaneGuard lane(ctx);
+    if (!lane.lane)
+      return RSX_ERR_DEVICE;
+    const size_t out_skip = size_t(img->pitch_bytes) * row_lo;
+    if (int e = lane.lane->d_in.ensure(in_total + 64))
+      return e;
+    if (int e = lane.lane->d_out.ensure(size_t(img->pitch_bytes) * (row_hi - row_lo) + 64))
+      return e;
+    hipStream_t s = lane.lane->stream;
+    {
+      std::lock_guard<std::mutex> up(ctx->upload_mu);
+      RSX_HIP_CHECK(ctx, hipMemsetAsync(lane.lane->d_in.ptr, 0, in_total + 64, s));
+      for (int i = 0; i < n_tiles; ++i)
+        if (tiles[i].in_bytes)
+          RSX_HIP_CHECK(ctx, hipMemcpyAsync(static_cast<uint8_t*>(lane.lane->d_in.ptr) + offs[i],
+                                            tiles[i].in, tiles[i].in_bytes, hipMemcpyHostToDevice, s));
+    }
+    uint8_t* const out_row0 = static_cast<uint8_t*>(lane.lane->d_out.ptr) - out_skip;
+    rc = rsx_plan_run(cp.plan, lane.lane->d_in.ptr, out_row0, s);
+    if (rc == RSX_OK)
+      rc = rsx_plan_results(cp.plan, nullptr, nullptr);
+    if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM)
+      return rc;
+    if (int e = cp.plan->dec->row_status(s, 0, st.data()))
+      return e;
+    std::vector<HostRect> rects;
+    for (int i = 0; i < n_tiles; ++i)
+      if (st[i] == RSX_OK)
+        rects.push_back(HostRect{size_t(win[i].off_y), size_t(win[i].copy_h),
+                                 size_t(win[i].off_x) * win[i].cpp * 2,
+                                 size_t(win[i].copy_w) * win[i].cpp * 2});
+    if (rects.size() > 1) {
+      size_t r0 = ~size_t(0), r1 = 0, b0 = ~size_t(0), b1 = 0;
+      for (const HostRect& r : rects) {
+        r0 = std::min(r0, r.row0);
+        r1 = std::max(r1, r.row0 + r.rows);
+        b0 = std::min(b0, r.byte0);
+        b1 = std::max(b1, r.byte0 + r.bytes);
+      }
+      // (rects_tile_image: inside, disjoint, and together the whole of their bounding box)
+      std::vector<HostRect> rel(rects);
+      for (HostRect& r : rel) {
+        r.row0 -= r0;
+        r.byte0 -= b0;
+      }
+      if (rects_tile_image(std::move(rel), r1 - r0, b1 - b0))
+        rects.assign(1, HostRect{r0, r1 - r0, b0, b1 - b0});
+    }
+    std::vector<DownRect> down;
+    down.reserve(rects.size());
+    for (const HostRect& r : rects) {
+      const size_t off = r.row0 * img->pitch_bytes + r.byte0;
+      down.push_back({static_cast<uint8_t*>(img->data) + off, img->pitch_bytes, out_row0 + off,
+                      img->pitch_bytes, r.bytes, r.rows});
+    }
+    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+    if (int e = download_rects(ctx, lane.lane, s, down.data(), down.size()))
+      return e;
+  } else {
+    for (int i = 0; i < n_tiles; ++i)
+      st[i] = win[i].host_status;
+  }
+  if (tile_status)
+    std::copy(st.begin(), st.end(), tile_status);
   for (int i = 0; i < n_tiles; ++i)
     if (st[i] != RSX_OK)
       return RSX_ERR_TILE_ERRORS; // AbstractDngDecompressor.cpp:247-251
