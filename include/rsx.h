@@ -853,6 +853,78 @@ int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* in, size_t i
                                        int32_t* strip_status);
 
 /* ------------------------------------------------------------------------ */
+/* 3u. FujiDecompressor (compressed RAF)                                     */
+/*    replaces FujiDecompressor::decompress()                                */
+/*    (decompressors/FujiDecompressor.cpp:901-908 -> decompressThread        */
+/*    :805-826 -> fuji_decode_strip :734-779 per strip).  The constructor    */
+/*    keeps its host work, the CFA checks included (:864-879).               */
+/*    rsx_fuji_parse = what the constructor does with the stream (:850-899): */
+/*    the big-endian 16-byte header (u16 signature, u8 version, u8 raw_type, */
+/*    u8 raw_bits, u16 raw_height, u16 raw_rounded_width, u16 raw_width,     */
+/*    u16 block_size, u8 blocks_in_row, u16 total_lines), blocks_in_row u32  */
+/*    sizes, 0x10 - (4 blocks_in_row & 0xC) bytes of padding where           */
+/*    4 blocks_in_row & 0xC is not zero, then the strips one after another;  */
+/*    every read past the end -> RSX_ERR_IO.  A header that FujiHeader::     */
+/*    operator bool refuses leaves n_strips 0 and RSX_OK: the refusal is     */
+/*    rsx_fuji_validate's, and no size is read.                              */
+/*    rsx_fuji_validate = the constructor's checks in its order: cpp 1 (an   */
+/*    rsx_image is UINT16), FujiHeader::operator bool (:919-937), dim ==     */
+/*    (raw_width, raw_height) (and pitch_bytes >= 2 dim_x) ->                */
+/*    RSX_ERR_INVALID_ARG; raw_bits 12 -> RSX_ERR_UNSUPPORTED (:859-862,     */
+/*    the reference throws); fuji_block_checks (:191-194) and n_strips !=    */
+/*    blocks_in_row -> RSX_ERR_INVALID_ARG.  A strip that does not lie in    */
+/*    the `in_bytes` of a call (getStream) -> RSX_ERR_IO from the call.      */
+/*    A frame is blocks_in_row strips of 768 columns, each one               */
+/*    BitStreamerMSB over exactly its own bytes (bytes behind it read as     */
+/*    zero), 18 line buffers of line_width + 2 samples (512 for raw_type 16, */
+/*    X-Trans; 384 for raw_type 0, Bayer) and two sets of three tables of 41 */
+/*    {value1, value2} pairs starting at {1 << (raw_bits - 6), 1}.  Every    */
+/*    strip decodes line_width samples a line; the copy-out of the last one  */
+/*    is raw_width - 768 n columns wide.                                     */
+/*    Per-strip statuses, the first exception of the strip in stream order:  */
+/*      RSX_ERR_IO              strip shorter than 4 bytes ("Bit stream size */
+/*                              is smaller than MaxProcessBytes")            */
+/*      RSX_ERR_INPUT_OVERFLOW  a refill more than 8 bytes past the strip    */
+/*                              (BitStreamer.h:100-132).  Every request is   */
+/*                              fill(32), one per batch of the zero count    */
+/*                              and one in front of the code bits: with c    */
+/*                              bits consumed and k words loaded the cache   */
+/*                              holds 32 k - c bits, a fill loads iff that   */
+/*                              is below 32, and k = ceil(c / 32) + 1 behind */
+/*                              it.  The load of word k throws iff           */
+/*                              4 k > size + 8, so a fill at c fails iff     */
+/*                              4 ceil(c / 32) > size + 8                    */
+/*      RSX_ERR_VALUE_RANGE     code < 0 || code >= total_values (:467)      */
+/*    The reference collects the strips' errors and throws if there is one;  */
+/*    the call returns the status of the lowest-numbered failing strip, and  */
+/*    through host pointers leaves the caller's image untouched then.  The   */
+/*    other strips are decoded.  `in` and `img->data` are both host or both  */
+/*    device pointers.  `strip_status` (may be NULL) gets n_strips statuses. */
+/* ------------------------------------------------------------------------ */
+#define RSX_FUJI_MAX_STRIPS 16
+typedef struct rsx_fuji_desc {
+  int32_t signature; /* 0x4953 */
+  int32_t version;   /* 1 */
+  int32_t raw_type;  /* 16 X-Trans, 0 Bayer */
+  int32_t raw_bits;
+  int32_t raw_height;
+  int32_t raw_rounded_width;
+  int32_t raw_width;
+  int32_t block_size;
+  int32_t blocks_in_row;
+  int32_t total_lines;
+  int32_t n_strips;
+  int32_t reserved;
+  uint64_t strip_offset[RSX_FUJI_MAX_STRIPS]; /* into `in` */
+  uint32_t strip_bytes[RSX_FUJI_MAX_STRIPS];
+} rsx_fuji_desc;
+
+int rsx_fuji_parse(const uint8_t* in, size_t in_bytes, rsx_fuji_desc* desc);
+int rsx_fuji_validate(const rsx_fuji_desc* desc, const rsx_image* img);
+int rsx_fuji_decompress(rsx_ctx* ctx, const rsx_fuji_desc* desc, const uint8_t* in,
+                        size_t in_bytes, const rsx_image* img, int32_t* strip_status);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -1793,6 +1865,22 @@ typedef struct rsx_dng_jpeg_job {
   uint64_t img_offset; /* a multiple of 2 */
   rsx_image img;       /* .data ignored */
 } rsx_dng_jpeg_job;
+
+/* one compressed RAF frame (section 3u); the strip offsets of `desc` are relative to in_offset.
+ * Jobs of both types, both depths and different geometries may share a plan: all their strips go
+ * into one launch.  Any in_offset, any even pitch_bytes >= 2 dim_x and any even img_offset. */
+typedef struct rsx_fuji_job {
+  rsx_fuji_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_fuji_job;
+
+int rsx_fuji_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fuji_job* jobs, rsx_plan** out_plan);
+/* Fuji plans, after rsx_plan_results: the statuses of the strips of job `job` of the last run
+ * (blocks_in_row entries).  RSX_ERR_INVALID_ARG for another plan, a refused job or before a run. */
+int rsx_fuji_plan_strip_status(rsx_plan* plan, int job, int32_t* strip_status);
 
 int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
                              rsx_plan** out_plan);

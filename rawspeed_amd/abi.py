@@ -709,3 +709,33 @@ def fill_recipe(desc, tables, table_index, init_pred):
         desc.table_index[c] = ti
     for c, p in enumerate(init_pred):
         desc.init_pred[c] = p
+
+
+FUJI_MAX_STRIPS = 16
+
+
+class FujiDesc(C.Structure):
+    """rsx_fuji_desc (include/rsx.h section 3u)"""
+    _fields_ = [("signature", C.c_int32), ("version", C.c_int32), ("raw_type", C.c_int32),
+                ("raw_bits", C.c_int32), ("raw_height", C.c_int32),
+                ("raw_rounded_width", C.c_int32), ("raw_width", C.c_int32),
+                ("block_size", C.c_int32), ("blocks_in_row", C.c_int32),
+                ("total_lines", C.c_int32), ("n_strips", C.c_int32), ("reserved", C.c_int32),
+                ("strip_offset", C.c_uint64 * FUJI_MAX_STRIPS),
+                ("strip_bytes", C.c_uint32 * FUJI_MAX_STRIPS)]
+
+
+class FujiJob(C.Structure):
+    _fields_ = [("desc", FujiDesc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def fuji_desc(header, strips):
+    """header: the dict of the ten header fields; strips: [(offset, bytes)]"""
+    d = FujiDesc()
+    for k, v in header.items():
+        setattr(d, k, v)
+    d.n_strips = len(strips)
+    for i, (off, n) in enumerate(strips):
+        d.strip_offset[i], d.strip_bytes[i] = off, n
+    return d

@@ -51,6 +51,8 @@ EXPORTS = [
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_dng_jpeg_validate", "rsx_dng_decompress_jpeg", "rsx_dng_jpeg_plan_create",
     "rsx_dng_jpeg_plan_tile_status",
+    "rsx_fuji_parse", "rsx_fuji_validate", "rsx_fuji_decompress", "rsx_fuji_plan_create",
+    "rsx_fuji_plan_strip_status",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -178,6 +180,11 @@ def lib():
         L.rsx_dng_decompress_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
         L.rsx_dng_jpeg_plan_tile_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_fuji_parse.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_fuji_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_fuji_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p]
+        L.rsx_fuji_plan_strip_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -203,7 +210,8 @@ def lib():
                      "rsx_dng_deflate_plan_create", "rsx_nikon_snef_plan_create",
                      "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
                      "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
-                     "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create"):
+                     "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create",
+                     "rsx_fuji_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -312,6 +320,19 @@ def samsung_v0_validate(offsets, in_bytes, img_view, n_offsets=None):
     arr = abi.samsung_v0_offsets(offsets)
     n = len(offsets) if n_offsets is None else n_offsets
     return lib().rsx_samsung_v0_validate(arr, n, in_bytes, C.byref(img_view))
+
+
+def fuji_parse(data):
+    """rsx_fuji_parse -> (status, abi.FujiDesc)"""
+    a = _u8(np.frombuffer(bytes(data) + b"\0", np.uint8))  # (a pointer for no bytes)
+    d = abi.FujiDesc()
+    return lib().rsx_fuji_parse(a.ctypes.data, len(data), C.byref(d)), d
+
+
+def fuji_validate(desc, img_view):
+    """rsx_fuji_validate; None passes NULL"""
+    return lib().rsx_fuji_validate(None if desc is None else C.byref(desc),
+                                   None if img_view is None else C.byref(img_view))
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -632,6 +653,19 @@ class Context:
                                              C.byref(img_view), rs)
         return st, (list(rs)[:img_view.dim_y] if rows else None)
 
+    def fuji_decompress(self, desc, data, img_view, in_ptr=None, in_bytes=None):
+        """desc: abi.FujiDesc with strip offsets inside `data` (host bytes) or inside the device
+        buffer at in_ptr (then img_view.data is a device pointer too).  Returns (status, per-strip
+        statuses; -1 where the call wrote none)."""
+        n = max(0, min(abi.FUJI_MAX_STRIPS, desc.n_strips))
+        ss = (C.c_int32 * abi.FUJI_MAX_STRIPS)(*([-1] * abi.FUJI_MAX_STRIPS))
+        if in_ptr is None:
+            a = _u8(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data)
+            in_ptr, in_bytes = a.ctypes.data, a.size
+        st = lib().rsx_fuji_decompress(self._h, C.byref(desc), C.c_void_p(in_ptr), in_bytes,
+                                       C.byref(img_view), ss)
+        return st, list(ss)[:n]
+
     def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
         """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
         tiles' zlib streams.  Returns (status, per-tile statuses)."""
@@ -770,6 +804,10 @@ class Context:
         """jobs: abi.DngDeflateJob, one per tile (depths, predictors and images may mix)"""
         return Plan(self, "rsx_dng_deflate_plan_create", abi.DngDeflateJob, jobs)
 
+    def fuji_plan(self, jobs):
+        """jobs: abi.FujiJob, one per frame (types, depths and geometries may mix)"""
+        return FujiPlan(self, "rsx_fuji_plan_create", abi.FujiJob, jobs)
+
     def dng_jpeg_plan(self, jobs):
         """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""
         return DngJpegPlan(self, "rsx_dng_jpeg_plan_create", abi.DngJpegJob, jobs)
@@ -879,6 +917,14 @@ class DngJpegPlan(Plan):
         st = (C.c_int32 * max(1, n_tiles))()
         rc = lib().rsx_dng_jpeg_plan_tile_status(self._h, job, st)
         return rc, list(st)[:n_tiles]
+
+
+class FujiPlan(Plan):
+    def strip_status(self, job, n_strips):
+        """after results(): (status, the statuses of the job's strips)"""
+        st = (C.c_int32 * max(1, n_strips))()
+        rc = lib().rsx_fuji_plan_strip_status(self._h, job, st)
+        return rc, list(st)[:n_strips]
 
 
 class PanasonicV4Plan(Plan):

@@ -12,6 +12,8 @@
 #include "rsx_panasonic_v4.h"
 #include "rsx_phase_one.h"
 #include "rsx_samsung_v0.h"
+#include "rsx_fuji.h"
+#include "rsx_fuji_core.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
@@ -3928,6 +3930,73 @@ extern "C" int rsx_samsung_v0_decompress(rsx_ctx* ctx, const uint8_t* in, size_t
   job.row_offsets = local.data();
   return single_image_host(ctx, key, rsx_samsung_v0_plan_create, job, in + lo, span, img,
                            row_status);
+}
+
+// ---------------------------------------------------------------------------
+// FujiDecompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_fuji_parse(const uint8_t* in, size_t in_bytes, rsx_fuji_desc* desc) {
+  return rsx_fuji::parse(in, in_bytes, desc);
+}
+
+extern "C" int rsx_fuji_validate(const rsx_fuji_desc* desc, const rsx_image* img) {
+  return rsx_fuji::validate(desc, img);
+}
+
+extern "C" int rsx_fuji_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fuji_job* jobs,
+                                    rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, fuji_plan_create);
+}
+
+extern "C" int rsx_fuji_plan_strip_status(rsx_plan* plan, int job, int32_t* strip_status) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) {
+    return d->row_status(plan->last_stream, job, strip_status);
+  });
+}
+
+// Device pointers: a plan of the call's own runs on them, on the context's stream behind the null
+// stream's work so far, and the call returns when it is done.  Host pointers (single_image_host):
+// the bytes from the first strip's up go up as one copy; the plan's key holds the descriptor.
+extern "C" int rsx_fuji_decompress(rsx_ctx* ctx, const rsx_fuji_desc* desc, const uint8_t* in,
+                                   size_t in_bytes, const rsx_image* img, int32_t* strip_status) {
+  if (!ctx || !desc || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_fuji::validate(desc, img))
+    return st;
+  if (int st = rsx_fuji::check_strips(*desc, in_bytes))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool in_dev = is_device_pointer(in), out_dev = is_device_pointer(img->data);
+  if (in_dev != out_dev)
+    return RSX_ERR_INVALID_ARG;
+  rsx_fuji_job job;
+  if (in_dev) {
+    one_job_init(job, in_bytes, img);
+    job.desc = *desc;
+    CallPlan call;
+    if (int st = rsx_fuji_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    const int rc = call.run(in, img->data, nullptr);
+    if (rc == RSX_ERR_DEVICE || rc == RSX_ERR_NOMEM)
+      return rc;
+    if (strip_status)
+      if (int e = call.plan->dec->row_status(call.plan->last_stream, 0, strip_status))
+        return e;
+    return rc;
+  }
+  uint64_t lo = desc->strip_offset[0];
+  for (int32_t s = 1; s < desc->n_strips; ++s)
+    lo = std::min(lo, desc->strip_offset[s]);
+  const size_t span = in_bytes - size_t(lo);
+  one_job_init(job, span, img);
+  job.desc = *desc;
+  for (int32_t s = 0; s < desc->n_strips; ++s)
+    job.desc.strip_offset[s] -= lo;
+  std::vector<uint8_t> key = one_job_key(rsx_fuji_plan_create, job);
+  return single_image_host(ctx, key, rsx_fuji_plan_create, job, in + lo, span, img, strip_status);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

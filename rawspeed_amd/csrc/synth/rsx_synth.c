@@ -681,3 +681,276 @@ size_t rsx_synth_phase_one_encode(const uint16_t* samples, size_t row_stride, in
   row_off[h] = n;
   return n;
 }
+
+/* ------------------------------------------------------------------------ */
+/* FujiDecompressor (compressed RAF) strip writer.  The reference has no     */
+/* encoder: this runs the decoder's state (decompressors/FujiDecompressor.   */
+/* cpp:444-779: 18 line buffers, the two sets of gradient tables, the pass   */
+/* order, the helper columns, the rotation) forward over `target`, 6         */
+/* total_lines rows of 768 pixels, and emits per coded sample the smallest   */
+/* code -- direct or over either wrap by total_values -- that makes the      */
+/* decoder reach the target: zeros, a 1 and bitDiff bits, or the escape      */
+/* (max_bits - raw_bits - 1 zeros, a 1, raw_bits bits of code - 1) where the */
+/* zero count of the regular form would reach the escape's.  X-Trans         */
+/* positions that take no bits get their interpolation whatever the target   */
+/* says: `reached` (same shape) gets the pixels a decoder will return.       */
+/* plant_kind 1 (regular form) / 2 (escape form): the first coded sample at  */
+/* or behind index plant_at that can carry an out-of-range code in that form */
+/* gets one, and the writer stops there (*planted = 1; the rows of the lines */
+/* before it are in `reached`).  The bits are padded with zeros to a byte.   */
+/* Returns the bytes written, 0 on overflow of `cap`.                        */
+/* ------------------------------------------------------------------------ */
+enum { FJ_STRIDE = 514, FJ_LINES = 18, FJ_R2 = 2, FJ_G2 = 7, FJ_B2 = 15 };
+
+typedef struct fj_enc {
+  int raw_bits, total, q4, escape_at, lw, xtrans;
+  uint16_t lines[FJ_LINES][FJ_STRIDE];
+  int want[FJ_LINES][FJ_STRIDE];
+  int ge[3][41][2], go[3][41][2];
+  uint8_t* out;
+  size_t n, cap;
+  uint64_t acc;
+  int nacc, overflow;
+  int plant_kind, planted;
+  uint32_t plant_at, n_coded;
+} fj_enc;
+
+static void fj_put(fj_enc* e, uint32_t v, int nbits) {
+  /* nbits <= 48: the zeros and the 1 of a sample, or its code bits */
+  e->acc = (e->acc << nbits) | v;
+  e->nacc += nbits;
+  while (e->nacc >= 8) {
+    e->nacc -= 8;
+    if (e->n >= e->cap) {
+      e->overflow = 1;
+      return;
+    }
+    e->out[e->n++] = (uint8_t)(e->acc >> e->nacc);
+  }
+  e->acc &= ((uint64_t)1 << e->nacc) - 1;
+}
+
+static int fj_quant(int v) {
+  const int a = v < 0 ? -v : v;
+  const int g = a >= 0x114 ? 4 : a >= 0x43 ? 3 : a >= 0x12 ? 2 : a > 0 ? 1 : 0;
+  return v < 0 ? -g : g;
+}
+
+static int fj_width(unsigned v) {
+  int n = 0;
+  while (v) {
+    ++n;
+    v >>= 1;
+  }
+  return n;
+}
+
+static int fj_bit_diff(int v1, int v2) {
+  int dec = fj_width((unsigned)v1) - fj_width((unsigned)v2);
+  if (dec < 0)
+    dec = 0;
+  if ((v2 << dec) < v1)
+    ++dec;
+  return dec > 15 ? 15 : dec;
+}
+
+/* one coded sample: returns the value the decoder reaches, -1 behind a planted code */
+static int fj_sample(fj_enc* e, int grad, int interp, int (*tbl)[2], int want) {
+  int* t = tbl[grad < 0 ? -grad : grad];
+  const int bits = fj_bit_diff(t[0], t[1]);
+  const int s = grad < 0 ? -1 : 1;
+  long best = -1;
+  for (int k = 0; k < 3; ++k) {
+    const long d = (long)s * (want - interp + (k == 1 ? e->total : k == 2 ? -e->total : 0));
+    const long code = d >= 0 ? 2 * d : -2 * d - 1;
+    if (code < e->total && (best < 0 || code < best))
+      best = code;
+  }
+  long code = best;
+  int bad = 0;
+  if (e->plant_kind && !e->planted && e->n_coded >= e->plant_at) {
+    if (e->plant_kind == 2) {
+      bad = 2;
+      code = e->total;
+    } else if (((long)(e->escape_at - 1) << bits) >= e->total) {
+      bad = 1;
+      code = (long)(e->escape_at - 1) << bits;
+    }
+  }
+  if (bad)
+    e->planted = 1;
+  if ((code >> bits) < e->escape_at && bad != 2) {
+    const int zeros = (int)(code >> bits);
+    fj_put(e, 1, zeros + 1);
+    if (bits)
+      fj_put(e, (uint32_t)(code & ((1L << bits) - 1)), bits);
+  } else {
+    fj_put(e, 1, e->escape_at + 1);
+    fj_put(e, (uint32_t)(code - 1), e->raw_bits);
+  }
+  if (bad)
+    return -1;
+  ++e->n_coded;
+  code = (code & 1) ? -1 - code / 2 : code / 2;
+  t[0] += (int)(code < 0 ? -code : code);
+  if (t[1] == 0x40) {
+    t[0] >>= 1;
+    t[1] >>= 1;
+  }
+  t[1]++;
+  int v = grad < 0 ? interp - (int)code : interp + (int)code;
+  if (v < 0)
+    v += e->total;
+  else if (v > e->q4)
+    v -= e->total;
+  if (v < 0)
+    return 0;
+  return v > e->q4 ? e->q4 : v;
+}
+
+static void fj_even(const fj_enc* e, int c, int col, int* grad, int* interp) {
+  const uint16_t* a = e->lines[c - 1];
+  const int Rb = a[1 + 2 * col], Rc = a[2 * col], Rd = a[2 + 2 * col];
+  const int Rf = e->lines[c - 2][1 + 2 * col];
+  const int dcb = abs(Rc - Rb), dfb = abs(Rf - Rb), ddb = abs(Rd - Rb);
+  int t1, t2;
+  if (dcb > (dfb > ddb ? dfb : ddb)) {
+    t1 = Rf;
+    t2 = Rd;
+  } else {
+    t1 = ddb > (dcb > dfb ? dcb : dfb) ? Rf : Rd;
+    t2 = Rc;
+  }
+  *interp = (2 * Rb + t1 + t2) >> 2;
+  *grad = 9 * fj_quant(Rb - Rf) + fj_quant(Rc - Rb);
+}
+
+static void fj_odd(const fj_enc* e, int c, int col, int* grad, int* interp) {
+  const uint16_t* a = e->lines[c - 1];
+  const int Ra = e->lines[c][1 + 2 * col], Rg = e->lines[c][3 + 2 * col];
+  const int Rb = a[2 + 2 * col], Rc = a[1 + 2 * col], Rd = a[3 + 2 * col];
+  const int mn = Rc < Rd ? Rc : Rd, mx = Rc < Rd ? Rd : Rc;
+  int v = Ra + Rg;
+  if (Rb < mn || Rb > mx)
+    v = (v + 2 * Rb) >> 1;
+  *interp = v >> 1;
+  *grad = 9 * fj_quant(Rb - Rc) + fj_quant(Rc - Ra);
+}
+
+static int fj_no_bits(int row, int i, int comp) {
+  const int even = (i & 1) == 0;
+  if (comp == 0)
+    return row == 0 || (row == 2 && even) || (row == 4 && !even) || row == 5;
+  return row == 1 || row == 2 || (row == 3 && !even) || (row == 5 && even);
+}
+
+/* (line, position) of image row r of a strip line and strip column x */
+static void fj_out_index(int xtrans, int r, int x, int* line, int* pos) {
+  static const char xt[6][7] = {"GGRGGB", "GGBGGR", "BRGRBG", "GGBGGR", "GGRGGB", "RBGBRG"};
+  char colour;
+  int idx;
+  if (xtrans) {
+    colour = xt[r][x % 6];
+    idx = (((x * 2 / 3) & 0x7FFFFFFE) | ((x % 3) & 1)) + ((x % 3) >> 1);
+  } else {
+    colour = (r & 1) == (x & 1) ? ((r & 1) ? 'B' : 'R') : 'G';
+    idx = x >> 1;
+  }
+  *line = colour == 'R' ? FJ_R2 + (r >> 1) : colour == 'G' ? FJ_G2 + r : FJ_B2 + (r >> 1);
+  *pos = 1 + idx;
+}
+
+/* the six passes of a line of the strip; 0, or -1 behind a planted code */
+static int fj_block(fj_enc* e) {
+  const int half = e->lw / 2;
+  int counter[3] = {0, 0, 0}; /* red, green, blue lines used */
+  static const int first[3] = {FJ_R2, FJ_G2, FJ_B2}, last[3] = {4, 12, 17};
+  for (int row = 0; row < 6; ++row) {
+    const int k[2] = {(row & 1) ? 1 : 0, (row & 1) ? 2 : 1};
+    int c[2];
+    for (int comp = 0; comp < 2; ++comp)
+      c[comp] = first[k[comp]] + counter[k[comp]]++;
+    for (int i = 0; i < half + 4; ++i) {
+      if (i < half)
+        for (int comp = 0; comp < 2; ++comp) {
+          int grad, interp, v;
+          fj_even(e, c[comp], i, &grad, &interp);
+          if (e->xtrans && fj_no_bits(row, i, comp))
+            v = interp;
+          else if ((v = fj_sample(e, grad, interp, e->ge[row % 3],
+                                  e->want[c[comp]][1 + 2 * i])) < 0)
+            return -1;
+          e->lines[c[comp]][1 + 2 * i] = (uint16_t)v;
+        }
+      if (i >= 4)
+        for (int comp = 0; comp < 2; ++comp) {
+          int grad, interp, v;
+          const int col = i - 4;
+          fj_odd(e, c[comp], col, &grad, &interp);
+          if ((v = fj_sample(e, grad, interp, e->go[row % 3], e->want[c[comp]][2 + 2 * col])) < 0)
+            return -1;
+          e->lines[c[comp]][2 + 2 * col] = (uint16_t)v;
+        }
+    }
+    for (int comp = 0; comp < 2; ++comp)
+      for (int i = first[k[comp]]; i <= last[k[comp]]; ++i) {
+        e->lines[i][0] = e->lines[i - 1][1];
+        e->lines[i][e->lw + 1] = e->lines[i - 1][e->lw];
+      }
+  }
+  return 0;
+}
+
+size_t rsx_synth_fuji_encode_strip(int raw_type, int raw_bits, int total_lines,
+                                   const uint16_t* target, int plant_kind, uint32_t plant_at,
+                                   uint8_t* out, size_t cap, uint16_t* reached, int* planted) {
+  fj_enc* e = (fj_enc*)calloc(1, sizeof(fj_enc));
+  if (!e)
+    return 0;
+  e->raw_bits = raw_bits;
+  e->total = 1 << raw_bits;
+  e->q4 = e->total - 1;
+  e->escape_at = raw_bits * (64 / raw_bits) - raw_bits - 1;
+  e->xtrans = raw_type == 16;
+  e->lw = e->xtrans ? 512 : 384;
+  e->out = out;
+  e->cap = cap;
+  e->plant_kind = plant_kind;
+  e->plant_at = plant_at;
+  for (int j = 0; j < 3; ++j)
+    for (int i = 0; i < 41; ++i) {
+      e->ge[j][i][0] = e->go[j][i][0] = 1 << (raw_bits - 6);
+      e->ge[j][i][1] = e->go[j][i][1] = 1;
+    }
+  memset(reached, 0, (size_t)total_lines * 6 * 768 * sizeof(uint16_t));
+  for (int cur = 0; cur < total_lines; ++cur) {
+    for (int r = 0; r < 6; ++r)
+      for (int x = 0; x < 768; ++x) {
+        int line, pos;
+        fj_out_index(e->xtrans, r, x, &line, &pos);
+        e->want[line][pos] = target[((size_t)cur * 6 + r) * 768 + x];
+      }
+    if (fj_block(e) < 0)
+      break;
+    for (int r = 0; r < 6; ++r)
+      for (int x = 0; x < 768; ++x) {
+        int line, pos;
+        fj_out_index(e->xtrans, r, x, &line, &pos);
+        reached[((size_t)cur * 6 + r) * 768 + x] = e->lines[line][pos];
+      }
+    if (cur + 1 == total_lines)
+      break;
+    static const int a[3] = {0, 5, 13}, b[3] = {5, 8, 5};
+    for (int k = 0; k < 3; ++k) {
+      memcpy(e->lines[a[k]], e->lines[a[k] + b[k] - 2], 2 * sizeof e->lines[0]);
+      e->lines[a[k] + 2][e->lw + 1] = e->lines[a[k] + 1][e->lw];
+    }
+  }
+  if (e->nacc)
+    fj_put(e, 0, 8 - e->nacc);
+  if (planted)
+    *planted = e->planted;
+  const size_t n = e->overflow ? 0 : e->n;
+  free(e);
+  return n;
+}

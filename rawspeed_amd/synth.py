@@ -63,6 +63,10 @@ def lib():
         _lib.rsx_synth_ljpeg_header.argtypes = [
             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.rsx_synth_fuji_encode_strip.restype = C.c_size_t
+        _lib.rsx_synth_fuji_encode_strip.argtypes = [
+            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t,
+            C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -314,6 +318,27 @@ def phase_one_encode(img, choices=(0.0, 0.0, 0.0), seed=0):
     if n == 0:
         raise ValueError("Phase One encode failed")
     return [out[int(off[r]):int(off[r + 1])].tobytes() for r in range(h)]
+
+
+def fuji_encode_strip(raw_type, raw_bits, total_lines, target, plant=None):
+    """One strip of a compressed RAF (FujiDecompressor.cpp:734-779) from `target`, (6 total_lines,
+    768) pixels.  plant: None, or (kind, index) with kind 'regular' or 'escape': the first coded
+    sample at or behind `index` that can carry an out-of-range code in that form gets one, and
+    the strip ends there.  Returns (the bytes, the pixels a decoder returns -- X-Trans positions
+    that take no bits hold their interpolation --, whether a code was planted)."""
+    target = np.ascontiguousarray(target, dtype=np.uint16)
+    assert target.shape == (6 * total_lines, 768), target.shape
+    cap = target.size * 9 + 64
+    out = np.empty(cap, dtype=np.uint8)
+    reached = np.zeros_like(target)
+    planted = C.c_int(0)
+    kind = {None: 0, "regular": 1, "escape": 2}[plant[0] if plant else None]
+    n = lib().rsx_synth_fuji_encode_strip(raw_type, raw_bits, total_lines, target.ctypes.data, kind,
+                                          plant[1] if plant else 0, out.ctypes.data, cap,
+                                          reached.ctypes.data, C.byref(planted))
+    if n == 0:
+        raise ValueError("Fuji encode failed")
+    return out[:n].tobytes(), reached, bool(planted.value)
 
 
 def huff_tables(*pairs, fix16=False):
