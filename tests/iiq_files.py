@@ -9,6 +9,8 @@
   iiq_strips()     (raw_data, strips) exactly as IiqDecoder::computeSripes cuts them
                    (IiqDecoder.cpp:75-118): a strip runs from its offset to the next larger
                    one, the last to the end of raw_data -- what the drop-in hunk hands over
+  planned_rows()   rows whose raw groups are planned per column parity, with free runs as long
+                   as the row between them; header_walk() finds the raw groups of a row
   model_row()      the kernel's decomposition in numpy terms: the header walk with a
                    checkpoint every 8 groups, 64-pixel chunks decoded from their checkpoint,
                    a segmented scan mod 2^16 per column parity, the over-read closed form,
@@ -42,6 +44,77 @@ def sample_image(rng, w, h):
 
 def encode(img, seed, choices=(0.25, 0.1, 0.4)):
     return synth.phase_one_encode(img, choices, seed)
+
+
+# ---------------------------------------------------------------------------------------
+# rows with a planned run structure
+# ---------------------------------------------------------------------------------------
+PATTERNS = ("small", "plus4096", "minus4095")
+
+
+def planned_rows(width, plans, pattern, seed=0, keep=False):
+    """(img, rows): one row per reset plan.  A plan is (even groups, odd groups): the 8-pixel
+    groups that must be raw in that column parity; every other group of the parity must not be.
+    The plain encoder (choices (0, 0, 0)) goes raw only where a difference of the group leaves
+    -4095 .. 4096, so a planned reset is a jump of more than 4096 at the group's first pixel of
+    that parity and nowhere else, and a row whose group 0 is not planned starts within that
+    range of 0.  Between the jumps the differences of a parity follow `pattern`:
+      small       random, of a scale that changes with every group (every length but 14)
+      plus4096    all +4096, the largest a 13-bit length holds: the sum wraps 2^16 every 16 pixels
+      minus4095   all -4095, the smallest
+    keep: choices (1, 0, 0) -- behind group 0 every header is the single keep bit, the lengths
+    a checkpoint holds are those of the start of the row (plans without resets only: a raw
+    length, once there, is kept as well)."""
+    if pattern not in PATTERNS:
+        raise ValueError(pattern)
+    ng = width >> 3
+    img = np.empty((len(plans), width), dtype=np.uint16)
+    for r, plan in enumerate(plans):
+        rng = np.random.default_rng([0x9A7, seed, width, r])
+        for p in (0, 1):
+            n = width // 2  # pixels of the parity; pixel i is column 2 i + p, group i >> 2
+            if pattern == "small":
+                scale = 2 ** rng.integers(0, 13, size=n // 4 + 1)
+                d = rng.integers(-1, 2, size=n) * (rng.random(n) * np.repeat(scale, 4)[:n]).astype(np.int64)
+            else:
+                d = np.full(n, 4096 if pattern == "plus4096" else -4095, dtype=np.int64)
+            for g in plan[p]:
+                if not 0 <= g < ng:
+                    raise ValueError("no group %d in a row of %d pixels" % (g, width))
+                d[4 * g] = int(rng.integers(4097, 28000)) * (1 if rng.random() < 0.5 else -1)
+            img[r, p::2] = np.cumsum(d) & 0xFFFF
+    if keep and any(plan[0] or plan[1] for plan in plans):
+        raise ValueError("the all-keep encoder keeps a raw length too")
+    rows = synth.phase_one_encode(img, (1.0, 0.0, 0.0) if keep else (0.0, 0.0, 0.0), seed)
+    return img, rows
+
+
+def header_walk(strip, width):
+    """The group headers of an encoded row: (raw groups of the even columns, of the odd columns,
+    headers that are the single keep bit).  The raw tail of a row (width % 8 pixels) is no group."""
+    W = _words(strip, width)
+    pos, l0, l1 = 0, 8, 8
+    raw, keeps = ([], []), 0
+    for g in range(width >> 3):
+        w = _peek(W, pos)
+        h0, l0, _ = _len(w, l0)
+        h1, l1, _ = _len((w << h0) & 0xFFFFFFFF, l1)
+        keeps += (h0 == 1) + (h1 == 1)
+        if l0 == 14:
+            raw[0].append(g)
+        if l1 == 14:
+            raw[1].append(g)
+        pos += h0 + h1 + 4 * (_bits(l0) + _bits(l1))
+    return raw[0], raw[1], keeps
+
+
+def longest_free_run(resets, n):
+    """the most consecutive positions of 0 .. n - 1 that hold none of `resets`"""
+    best, prev = 0, -1
+    for g in sorted(resets) + [n]:
+        best = max(best, g - prev - 1)
+        prev = g
+    return best
 
 
 # ---------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ decompressors/SamsungV0Decompressor.cpp:44-204, reached from decoders/SrwDecoder
   BitWriter        BitStreamerMSB32 rows: little-endian 32-bit words filled MSB first
   encode_row       a random valid row: lengths stay in 0..16, dir = 1 only where it is allowed
   random_rows      the rows of a frame (+ statistics of what the encoder drew)
+  planned_dirs     the upward blocks of every row from row 2 on, planned instead of drawn
   srw_v0_file      the container: one strip, tag 40976 -> a table of `height` row offsets
   parse_row        one row's headers and adjustments, or the status of its first exception
   model_decode     the whole decode: statuses per row, and the image when every row is fine
@@ -40,16 +41,25 @@ def new_stats():
     return {"headers": 0, "ops": [0, 0, 0, 0], "eligible": 0, "up": 0, "lens": set()}
 
 
-def encode_row(rng, width, row, p_up=0.3, stats=None, plant=False, op_weights=(1, 1, 1, 1)):
+def encode_row(rng, width, row, p_up=0.3, stats=None, plant=False, op_weights=(1, 1, 1, 1), dirs=None):
     """One random valid row.  Every op that keeps its length in 0..16 is drawn with the given
-    weights; `plant` forces a length through 15 -> 16 and one to 0 in the first two blocks."""
+    weights; `plant` forces a length through 15 -> 16 and one to 0 in the first two blocks.
+    dirs: a bool per block that says which blocks are upward, instead of the draw with p_up
+    (an upward block in row 0 or 1 or in the last block is an error: no valid row has one)."""
     st = stats if stats is not None else new_stats()
     w = BitWriter()
     lens = [7] * 4 if row < 2 else [4] * 4
     nblk = (width + 15) // 16
+    if dirs is not None and len(dirs) != nblk:
+        raise ValueError("dirs: %d entries for %d blocks" % (len(dirs), nblk))
     for b in range(nblk):
         can_up = row >= 2 and 16 * b + 16 < width
-        up = bool(can_up and rng.random() < p_up)
+        if dirs is not None:
+            up = bool(dirs[b])
+            if up and not can_up:
+                raise ValueError("block %d of row %d cannot be upward" % (b, row))
+        else:
+            up = bool(can_up and rng.random() < p_up)
         st["eligible"] += can_up
         st["up"] += up
         ops, vals = [], []
@@ -84,9 +94,19 @@ def encode_row(rng, width, row, p_up=0.3, stats=None, plant=False, op_weights=(1
     return w.bytes()
 
 
-def random_rows(rng, width, height, p_up=0.3, stats=None, plant=False, op_weights=(1, 1, 1, 1)):
-    return [encode_row(rng, width, y, p_up, stats, plant and y == 0, op_weights)
+def random_rows(rng, width, height, p_up=0.3, stats=None, plant=False, op_weights=(1, 1, 1, 1),
+                dirs=None):
+    """dirs: {row: a bool per block} for the rows whose upward blocks are planned, not drawn"""
+    return [encode_row(rng, width, y, p_up, stats, plant and y == 0, op_weights,
+                       None if dirs is None else dirs.get(y))
             for y in range(height)]
+
+
+def planned_dirs(width, height, plan):
+    """plan {row: upward blocks} -> the `dirs` of random_rows for a frame in which every row from
+    row 2 on is planned: the rows the plan does not name have no upward block"""
+    nblk = (width + 15) // 16
+    return {y: [b in plan.get(y, ()) for b in range(nblk)] for y in range(2, height)}
 
 
 def tiled_rows(rng, width, height, p_up=0.3, pool=24, op_weights=(1, 1, 1, 1)):

@@ -48,6 +48,47 @@ def test_model_matches_reference_on_random_files(ref, chunk):
     assert {0, 2, 4, 6} <= residues
 
 
+def _long_run_files():
+    """the planned rows of tests/long_runs.py at the widths that reach wave 1, wave 2, the tail
+    with a lane of its own and the widest row: every plan class, every value pattern, all-keep"""
+    import long_runs as L
+    return [c for c in L.p1_files() if c[1] in (4160, 8256, 11974, 11976)]
+
+
+@pytest.mark.parametrize("case", _long_run_files(), ids=lambda c: c[0])
+@pytest.mark.ref
+@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built")
+def test_model_matches_reference_on_long_reset_free_runs(ref, case):
+    """Rows whose raw groups are planned (none; one in one parity at a lane or wave edge; one
+    in the middle of a lane; one early): the longest run without one is the row, 1497 groups at
+    w = 11976, where test_model_matches_reference_on_random_files never has more than a few
+    dozen.  The reference's decode, the model's and the source agree, and the hash recorded in
+    tests/golden/long_runs_ref.json is the reference's."""
+    import long_runs as L
+    img, rows, blob = L.p1_build(case)
+    h, w = img.shape
+    st, dec = ref.decode_file(blob)
+    assert st == 0, (case[0], ref.last_error())
+    got = dec.u16()[:h, :w]
+    assert np.array_equal(got, img)
+    mst, mimg, mrows = I.model_file(blob)
+    assert mst == 0 and mrows == [0] * h and np.array_equal(mimg, got)
+    rec = L.golden()["phase_one"][case[0]]
+    assert (L.sha_rows(rows)[:16], L.sha(got)) == (rec["input"], rec["image"])
+
+
+def test_model_matches_recorded_hashes_of_long_reset_free_runs():
+    """the same without the reference: the model against what was recorded from it (never skips)"""
+    import long_runs as L
+    rec = L.golden()["phase_one"]
+    assert sorted(rec) == sorted(c[0] for c in L.p1_files())
+    for case in _long_run_files():
+        img, rows, blob = L.p1_build(case)
+        assert L.sha_rows(rows)[:16] == rec[case[0]]["input"], case[0]
+        mst, mimg, _ = I.model_file(blob)
+        assert mst == 0 and L.sha(mimg) == rec[case[0]]["image"] == L.sha(img), case[0]
+
+
 def _headers(rows, width):
     """(length codes used, 'keep' headers, raw groups) over the rows' group headers"""
     used, keeps, raws = set(), 0, 0

@@ -259,6 +259,48 @@ def test_widest_rows(ref, w):
     _check(ref, w, 4, S.random_rows(rng, w, 4, p_up=0.3))
 
 
+def _long_run_frames():
+    """the planned frames of tests/long_runs.py one block into pass 1 and at the widest row"""
+    import long_runs as L
+    return [c for c in L.v0_frames() if c[1] in (3088, 5546)]
+
+
+@pytest.mark.ref
+@needs_ref
+@pytest.mark.parametrize("w", [3088, 5546])
+def test_model_matches_reference_on_long_runs_without_upward_blocks(ref, w):
+    """Frames whose upward blocks are planned (none; one in row 2 or 3 at a wave or pass edge;
+    every eligible one; two 200 blocks apart): the root of a run lies up to 347 blocks to the
+    left, where the random files above never have it more than 27.  The hash recorded in
+    tests/golden/long_runs_ref.json is the reference's."""
+    import long_runs as L
+    rec = L.golden()["samsung_v0"]
+    for case in _long_run_frames():
+        name, cw, h, _ = case
+        if cw != w:
+            continue
+        rows = L.v0_build(case)
+        _check(ref, w, h, rows)
+        st, dec = ref.decode_file(S.rows_file(w, h, rows))
+        assert (L.sha_rows(rows)[:16], L.sha(dec.u16()[:h, :w])) == (rec[name]["input"], rec[name]["image"])
+
+
+@pytest.mark.parametrize("width", [3088, 5546])
+def test_model_matches_recorded_hashes_of_long_runs_without_upward_blocks(width):
+    """the same without the reference: the model against what was recorded from it (never skips)"""
+    import long_runs as L
+    rec = L.golden()["samsung_v0"]
+    assert sorted(rec) == sorted(c[0] for c in L.v0_frames())
+    for case in _long_run_frames():
+        name, w, h, _ = case
+        if w != width:
+            continue
+        rows = L.v0_build(case)
+        assert L.sha_rows(rows)[:16] == rec[name]["input"], name
+        st, _, img = S.model_decode(w, h, rows)
+        assert st == S.OK and L.sha(img) == rec[name]["image"], name
+
+
 @pytest.mark.ref
 @needs_ref
 def test_truncated_rows_at_every_size(ref):
