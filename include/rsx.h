@@ -925,6 +925,46 @@ int rsx_fuji_decompress(rsx_ctx* ctx, const rsx_fuji_desc* desc, const uint8_t* 
                         size_t in_bytes, const rsx_image* img, int32_t* strip_status);
 
 /* ------------------------------------------------------------------------ */
+/* 3v. OlympusDecompressor (compressed ORF)                                  */
+/*    replaces OlympusDecompressor::decompress()                             */
+/*    (decompressors/OlympusDecompressor.cpp:229-231 -> :204-214, per row    */
+/*    decompressRow :183-202, per pixel getDiff :61-97 and getPred           */
+/*    :130-164); OrfDecoder::decodeUncompressed is rsx_unpack_* already.     */
+/*    rsx_olympus_validate = the constructor's checks in its order           */
+/*    (:218-227): cpp 1 (an rsx_image is UINT16); dim_x and dim_y positive   */
+/*    and even, dim_x <= 10400, dim_y <= 7792; and pitch_bytes >= 2 dim_x    */
+/*    -> RSX_ERR_INVALID_ARG.  Then what the reader refuses before the first */
+/*    bit: in_bytes < 7 (skipBytes(7), :209) and in_bytes - 7 < 4 ("Bit      */
+/*    stream size is smaller than MaxProcessBytes", BitStreamer.h:58-59)     */
+/*    -> RSX_ERR_IO.                                                         */
+/*    `in` is the stream as OrfDecoder hands it over, the 7 bytes in front   */
+/*    included.  Behind them one BitStreamerMSB runs over all rows with no   */
+/*    alignment or marker between them; each row starts two difference       */
+/*    decoders (one a column parity) at carry {0, 0, 0}.  Every byte string  */
+/*    is a stream: the only failures are the reader's.                       */
+/*    Statuses of a decode:                                                  */
+/*      RSX_ERR_INVALID_ARG     the constructor's refusals, the pitch, an    */
+/*                              odd pitch or image offset, host and device   */
+/*                              pointers mixed                               */
+/*      RSX_ERR_IO              fewer than 11 bytes                          */
+/*      RSX_ERR_INPUT_OVERFLOW  a refill more than 8 bytes past the end      */
+/*                              (BitStreamer.h:100-132).  Every request is   */
+/*                              fill(32), one in front of every symbol, and  */
+/*                              a symbol takes at most 31 bits: as in 3u, a  */
+/*                              fill with c bits consumed fails iff          */
+/*                              4 ceil(c / 32) > size + 8, size =            */
+/*                              in_bytes - 7.  Bytes past the end read as    */
+/*                              zero until then.                             */
+/*    `in` and `img->data` are both host or both device pointers.  Through   */
+/*    host pointers a failing call leaves the caller's image untouched;      */
+/*    through device pointers the image behind a failure is unspecified      */
+/*    (the walk writes differences into it).                                 */
+/* ------------------------------------------------------------------------ */
+int rsx_olympus_validate(size_t in_bytes, const rsx_image* img);
+int rsx_olympus_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                           const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -1881,6 +1921,23 @@ int rsx_fuji_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fuji_job* jobs, rsx
 /* Fuji plans, after rsx_plan_results: the statuses of the strips of job `job` of the last run
  * (blocks_in_row entries).  RSX_ERR_INVALID_ARG for another plan, a refused job or before a run. */
 int rsx_fuji_plan_strip_status(rsx_plan* plan, int job, int32_t* strip_status);
+
+/* one compressed ORF frame (section 3v).  Jobs of different geometry may share a plan: one
+ * wavefront walks each job's bits, four reconstruct its planes.  Any in_offset, any even
+ * pitch_bytes >= 2 dim_x and any even img_offset. */
+typedef struct rsx_olympus_job {
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_olympus_job;
+
+int rsx_olympus_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_olympus_job* jobs,
+                            rsx_plan** out_plan);
+/* Olympus plans, after rsx_plan_results (which returns the status of the lowest-numbered failing
+ * job): the status of job `job` of the last run.  RSX_ERR_INVALID_ARG for another plan or before
+ * a run's results. */
+int rsx_olympus_plan_job_status(rsx_plan* plan, int job, int32_t* status);
 
 int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
                              rsx_plan** out_plan);

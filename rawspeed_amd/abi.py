@@ -739,3 +739,9 @@ def fuji_desc(header, strips):
     for i, (off, n) in enumerate(strips):
         d.strip_offset[i], d.strip_bytes[i] = off, n
     return d
+
+
+class OlympusJob(C.Structure):
+    """rsx_olympus_job (include/rsx.h section 3v)"""
+    _fields_ = [("in_offset", C.c_uint64), ("in_bytes", C.c_uint64), ("img_offset", C.c_uint64),
+                ("img", Image)]

@@ -53,6 +53,8 @@ EXPORTS = [
     "rsx_dng_jpeg_plan_tile_status",
     "rsx_fuji_parse", "rsx_fuji_validate", "rsx_fuji_decompress", "rsx_fuji_plan_create",
     "rsx_fuji_plan_strip_status",
+    "rsx_olympus_validate", "rsx_olympus_decompress", "rsx_olympus_plan_create",
+    "rsx_olympus_plan_job_status",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -185,6 +187,9 @@ def lib():
         L.rsx_fuji_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p]
         L.rsx_fuji_plan_strip_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_olympus_validate.argtypes = [C.c_size_t, C.c_void_p]
+        L.rsx_olympus_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_olympus_plan_job_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -211,7 +216,7 @@ def lib():
                      "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
                      "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
                      "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create",
-                     "rsx_fuji_plan_create"):
+                     "rsx_fuji_plan_create", "rsx_olympus_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -333,6 +338,11 @@ def fuji_validate(desc, img_view):
     """rsx_fuji_validate; None passes NULL"""
     return lib().rsx_fuji_validate(None if desc is None else C.byref(desc),
                                    None if img_view is None else C.byref(img_view))
+
+
+def olympus_validate(in_bytes, img_view):
+    """rsx_olympus_validate; None passes NULL"""
+    return lib().rsx_olympus_validate(in_bytes, None if img_view is None else C.byref(img_view))
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -666,6 +676,15 @@ class Context:
                                        C.byref(img_view), ss)
         return st, list(ss)[:n]
 
+    def olympus_decompress(self, data, img_view, in_ptr=None, in_bytes=None):
+        """data: the stream with its 7 leading bytes (host bytes), or the device buffer at in_ptr
+        (then img_view.data is a device pointer too).  Returns the status."""
+        if in_ptr is None:
+            a = _u8(np.frombuffer(bytes(data) + b"\0", np.uint8))  # (a pointer for no bytes)
+            in_ptr, in_bytes = a.ctypes.data, len(data)
+        return lib().rsx_olympus_decompress(self._h, C.c_void_p(in_ptr), in_bytes,
+                                            C.byref(img_view))
+
     def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
         """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
         tiles' zlib streams.  Returns (status, per-tile statuses)."""
@@ -808,6 +827,10 @@ class Context:
         """jobs: abi.FujiJob, one per frame (types, depths and geometries may mix)"""
         return FujiPlan(self, "rsx_fuji_plan_create", abi.FujiJob, jobs)
 
+    def olympus_plan(self, jobs):
+        """jobs: abi.OlympusJob, one per frame (geometries may mix)"""
+        return OlympusPlan(self, "rsx_olympus_plan_create", abi.OlympusJob, jobs)
+
     def dng_jpeg_plan(self, jobs):
         """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""
         return DngJpegPlan(self, "rsx_dng_jpeg_plan_create", abi.DngJpegJob, jobs)
@@ -925,6 +948,14 @@ class FujiPlan(Plan):
         st = (C.c_int32 * max(1, n_strips))()
         rc = lib().rsx_fuji_plan_strip_status(self._h, job, st)
         return rc, list(st)[:n_strips]
+
+
+class OlympusPlan(Plan):
+    def job_status(self, job):
+        """after results(): (status of the getter, the job's status)"""
+        st = C.c_int32(-1)
+        rc = lib().rsx_olympus_plan_job_status(self._h, job, C.byref(st))
+        return rc, st.value
 
 
 class PanasonicV4Plan(Plan):

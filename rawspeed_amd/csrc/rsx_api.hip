@@ -14,6 +14,8 @@
 #include "rsx_samsung_v0.h"
 #include "rsx_fuji.h"
 #include "rsx_fuji_core.h"
+#include "rsx_olympus.h"
+#include "rsx_olympus_core.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
@@ -3997,6 +3999,52 @@ extern "C" int rsx_fuji_decompress(rsx_ctx* ctx, const rsx_fuji_desc* desc, cons
     job.desc.strip_offset[s] -= lo;
   std::vector<uint8_t> key = one_job_key(rsx_fuji_plan_create, job);
   return single_image_host(ctx, key, rsx_fuji_plan_create, job, in + lo, span, img, strip_status);
+}
+
+// ---------------------------------------------------------------------------
+// OlympusDecompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_olympus_validate(size_t in_bytes, const rsx_image* img) {
+  return rsx_olympus::validate(in_bytes, img);
+}
+
+extern "C" int rsx_olympus_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_olympus_job* jobs,
+                                       rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, olympus_plan_create);
+}
+
+extern "C" int rsx_olympus_plan_job_status(rsx_plan* plan, int job, int32_t* status) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) {
+    return d->row_status(plan->last_stream, job, status);
+  });
+}
+
+// Device pointers: a plan of the call's own runs on them, on the context's stream behind the null
+// stream's work so far, and the call returns when it is done.  Host pointers (single_image_host):
+// the whole stream goes up as one copy; the plan is keyed by the geometry and the stream's size.
+extern "C" int rsx_olympus_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                      const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_olympus::validate(in_bytes, img))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool in_dev = is_device_pointer(in), out_dev = is_device_pointer(img->data);
+  if (in_dev != out_dev)
+    return RSX_ERR_INVALID_ARG;
+  rsx_olympus_job job;
+  one_job_init(job, in_bytes, img);
+  if (in_dev) {
+    CallPlan call;
+    if (int st = rsx_olympus_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    return call.run(in, img->data, nullptr);
+  }
+  std::vector<uint8_t> key = one_job_key(rsx_olympus_plan_create, job);
+  return single_image_host(ctx, key, rsx_olympus_plan_create, job, in, in_bytes, img, nullptr);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

@@ -954,3 +954,160 @@ size_t rsx_synth_fuji_encode_strip(int raw_type, int raw_bits, int total_lines,
   free(e);
   return n;
 }
+
+/* ------------------------------------------------------------------------ */
+/* Compressed ORF (OlympusDecompressor.cpp): the 7 bytes the decoder skips,  */
+/* then one MSB-first bit string over all rows.  A symbol is a sign bit, the */
+/* two low bits of the difference, then either `high` zeros and a one        */
+/* (high <= 11) or twelve zeros, 15 - n bits of high and one bit the decoder */
+/* skips, and then n = numLowBits bits; n follows from the carries of the    */
+/* symbol's column parity, which start at zero in every row.                 */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  uint8_t* out;
+  size_t cap, n;
+  uint32_t acc;
+  int fill; /* bits in acc */
+  int overflow;
+} OlyBits;
+
+static void oly_put(OlyBits* w, uint32_t v, int bits) {
+  for (int i = bits - 1; i >= 0; --i) {
+    w->acc = w->acc << 1 | ((v >> i) & 1u);
+    if (++w->fill == 8) {
+      if (w->n < w->cap)
+        w->out[w->n++] = (uint8_t)w->acc;
+      else
+        w->overflow = 1;
+      w->acc = 0;
+      w->fill = 0;
+    }
+  }
+}
+
+static size_t oly_finish(OlyBits* w) {
+  if (w->fill)
+    oly_put(w, 0, 8 - w->fill);
+  return w->overflow ? 0 : w->n;
+}
+
+typedef struct {
+  int32_t c0, c1, c2;
+} OlyCarry;
+
+static int oly_low_bits(const OlyCarry* c) {
+  const int bias = c->c2 < 3 ? 2 : 0;
+  uint32_t v = (uint32_t)c->c0 & 0xFFFFu;
+  int active = 0;
+  while (v) {
+    ++active;
+    v >>= 1;
+  }
+  const int n = active - bias;
+  return n > 2 + bias ? n : 2 + bias;
+}
+
+/* one symbol as given; returns the carry[0] it makes */
+static int32_t oly_emit(OlyBits* w, int n, int sign, int low, int escape, uint32_t high,
+                        uint32_t field, int skipped_bit) {
+  oly_put(w, (uint32_t)sign & 1u, 1);
+  oly_put(w, (uint32_t)low & 3u, 2);
+  if (!escape) {
+    oly_put(w, 0, (int)high);
+    oly_put(w, 1, 1);
+  } else {
+    oly_put(w, 0, 12);
+    oly_put(w, high, 15 - n);
+    oly_put(w, (uint32_t)skipped_bit & 1u, 1);
+  }
+  oly_put(w, field, n);
+  return (int32_t)(high << n | field);
+}
+
+static void oly_after(OlyCarry* c, int32_t c0, int sign) {
+  c->c0 = c0;
+  const int32_t d = (c0 ^ -sign) + c->c1;
+  c->c1 = (3 * d + c->c1) >> 5;
+  c->c2 = c0 > 16 ? 0 : c->c2 + 1;
+}
+
+static int32_t oly_pred(const uint16_t* img, int w, int row, int col) {
+  if (row < 2 && col < 2)
+    return 0;
+  const int32_t left = col >= 2 ? img[(size_t)row * w + col - 2] : 0;
+  if (row < 2)
+    return left;
+  const int32_t up = img[(size_t)(row - 2) * w + col];
+  if (col < 2)
+    return up;
+  const int32_t nw = img[(size_t)(row - 2) * w + col - 2];
+  const int32_t a = left - nw, b = up - nw;
+  const int32_t aa = a < 0 ? -a : a, ab = b < 0 ? -b : b;
+  if ((a < 0) != (b < 0) && a != 0 && b != 0)
+    return (aa > 32 || ab > 32) ? left + b : (left + up) >> 1;
+  return aa > ab ? left : up;
+}
+
+/* The stream that decodes to `target` (h rows of w pixels, no padding).  Returns its size, 7
+ * leading bytes included, or 0: the image cannot be reached, or `cap` is too small. */
+size_t rsx_synth_olympus_encode(int w, int h, const uint16_t* target, uint8_t* out, size_t cap) {
+  if (w <= 0 || h <= 0 || (w & 1) || cap < 7)
+    return 0;
+  memset(out, 0, 7);
+  OlyBits bw = {out + 7, cap - 7, 0, 0, 0, 0};
+  for (int row = 0; row < h; ++row) {
+    OlyCarry c[2] = {{0, 0, 0}, {0, 0, 0}};
+    for (int col = 0; col < w; ++col) {
+      OlyCarry* s = &c[col & 1];
+      const int32_t p = oly_pred(target, w, row, col);
+      /* the difference mod 2^16, as the representative next to zero */
+      const int32_t diff = (int32_t)(((uint32_t)(target[(size_t)row * w + col] - p) + 32768u) & 0xFFFFu) - 32768;
+      const int low = diff & 3;
+      const int32_t x = (diff >> 2) - s->c1;
+      const int sign = x < 0;
+      const int32_t c0 = sign ? ~x : x;
+      const int n = oly_low_bits(s);
+      const uint32_t high = (uint32_t)c0 >> n, field = (uint32_t)c0 & ((1u << n) - 1u);
+      if (high <= 11)
+        oly_emit(&bw, n, sign, low, 0, high, field, 0);
+      else if (c0 < (1 << 15))
+        oly_emit(&bw, n, sign, low, 1, high, field, 1);
+      else
+        return 0;
+      oly_after(s, c0, sign);
+    }
+  }
+  const size_t n = oly_finish(&bw);
+  return bw.overflow ? 0 : n + 7;
+}
+
+/* The stream of planted symbols: `syms` holds n_syms symbols in stream order, six ints each
+ * (sign, low, escape form, high, low field, the bit the escape form skips); the low field is
+ * masked to the symbol's numLowBits, high to 15 - numLowBits in the escape form.  The symbols
+ * behind them, up to w h, are (0, 0, regular, 0, 0).  Returns the size, or 0. */
+size_t rsx_synth_olympus_plant(int w, int h, const int32_t* syms, int n_syms, uint8_t* out,
+                               size_t cap) {
+  if (w <= 0 || h <= 0 || (w & 1) || cap < 7)
+    return 0;
+  memset(out, 0, 7);
+  OlyBits bw = {out + 7, cap - 7, 0, 0, 0, 0};
+  int k = 0;
+  for (int row = 0; row < h; ++row) {
+    OlyCarry c[2] = {{0, 0, 0}, {0, 0, 0}};
+    for (int col = 0; col < w; ++col, ++k) {
+      OlyCarry* s = &c[col & 1];
+      static const int32_t none[6] = {0, 0, 0, 0, 0, 0};
+      const int32_t* y = k < n_syms ? syms + 6 * (size_t)k : none;
+      const int n = oly_low_bits(s);
+      const int escape = y[2] != 0;
+      if (!escape && (y[3] < 0 || y[3] > 11))
+        return 0;
+      const uint32_t high = escape ? (uint32_t)y[3] & ((1u << (15 - n)) - 1u) : (uint32_t)y[3];
+      const uint32_t field = (uint32_t)y[4] & ((1u << n) - 1u);
+      const int32_t c0 = oly_emit(&bw, n, y[0] & 1, y[1], escape, high, field, y[5]);
+      oly_after(s, c0, y[0] & 1);
+    }
+  }
+  const size_t n = oly_finish(&bw);
+  return bw.overflow ? 0 : n + 7;
+}

@@ -271,6 +271,17 @@ inline int samsung_v0(const std::vector<ByteStream>& stripes, const RawImage& im
                                    implicit_cast<int>(offsets.size()), &v, nullptr);
 }
 
+// OlympusDecompressor::decompress(): `input` is the stream OrfDecoder hands
+// over, the 7 bytes the decompressor skips included
+inline int olympus(const ByteStream& input, const RawImage& img) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  const rsx_image v = view(img);
+  const Buffer in = input.peekRemainingBuffer();
+  return rsx_olympus_decompress(rsx, in.begin(), in.getSize(), &v);
+}
+
 // DngDecoder::decodeRawInternal() / handleMetadata(): what follows the tiles --
 // OpcodeList1 and the LinearizationTable look-up -- handed to the tile fan-out so that it runs on
 // the device in front of the ONE download.  The hunk fills this BEFORE decodeData (the entries,

@@ -67,6 +67,12 @@ def lib():
         _lib.rsx_synth_fuji_encode_strip.argtypes = [
             C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t,
             C.c_void_p, C.c_void_p]
+        _lib.rsx_synth_olympus_encode.restype = C.c_size_t
+        _lib.rsx_synth_olympus_encode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t]
+        _lib.rsx_synth_olympus_plant.restype = C.c_size_t
+        _lib.rsx_synth_olympus_plant.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_size_t]
     return _lib
 
 
@@ -339,6 +345,32 @@ def fuji_encode_strip(raw_type, raw_bits, total_lines, target, plant=None):
     if n == 0:
         raise ValueError("Fuji encode failed")
     return out[:n].tobytes(), reached, bool(planted.value)
+
+
+def olympus_encode(target):
+    """The compressed ORF stream (OlympusDecompressor.cpp:204-214, the 7 leading bytes included)
+    that decodes to `target`, (h, w) uint16 with w even.  Every image can be reached; the writer
+    raises instead of writing another one."""
+    target = np.ascontiguousarray(target, dtype=np.uint16)
+    h, w = target.shape
+    cap = target.size * 4 + 16  # (a symbol is at most 31 bits)
+    out = np.empty(cap, dtype=np.uint8)
+    n = lib().rsx_synth_olympus_encode(w, h, target.ctypes.data, out.ctypes.data, cap)
+    if n == 0:
+        raise ValueError("Olympus encode failed")
+    return out[:n].tobytes()
+
+
+def olympus_plant(w, h, syms):
+    """The stream of the planted symbols `syms`, (sign, low, escape form, high, low field, skipped
+    bit) each, in stream order; the symbols behind them are (0, 0, regular, 0, 0)."""
+    a = np.ascontiguousarray(np.array(syms, dtype=np.int32).reshape(-1, 6))
+    cap = w * h * 4 + 16
+    out = np.empty(cap, dtype=np.uint8)
+    n = lib().rsx_synth_olympus_plant(w, h, a.ctypes.data, a.shape[0], out.ctypes.data, cap)
+    if n == 0:
+        raise ValueError("Olympus plant failed")
+    return out[:n].tobytes()
 
 
 def huff_tables(*pairs, fix16=False):
