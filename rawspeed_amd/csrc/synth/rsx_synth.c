@@ -697,7 +697,12 @@ size_t rsx_synth_phase_one_encode(const uint16_t* samples, size_t row_stride, in
 /* plant_kind 1 (regular form) / 2 (escape form): the first coded sample at  */
 /* or behind index plant_at that can carry an out-of-range code in that form */
 /* gets one, and the writer stops there (*planted = 1; the rows of the lines */
-/* before it are in `reached`).  The bits are padded with zeros to a byte.   */
+/* before it are in `reached`).  plant_kind 3 (a long escape): the first      */
+/* coded sample at or behind plant_at whose code is at least 1 is written as */
+/* plant_zeros zeros, a 1 and raw_bits bits of code - 1 -- a decoder takes   */
+/* any zero count of at least the escape's for the escape --, *planted = 1,  */
+/* and the writer goes on: the pixels are those of the strip without it.     */
+/* The bits are padded with zeros to a byte.                                 */
 /* Returns the bytes written, 0 on overflow of `cap`.                        */
 /* ------------------------------------------------------------------------ */
 enum { FJ_STRIDE = 514, FJ_LINES = 18, FJ_R2 = 2, FJ_G2 = 7, FJ_B2 = 15 };
@@ -712,7 +717,7 @@ typedef struct fj_enc {
   uint64_t acc;
   int nacc, overflow;
   int plant_kind, planted;
-  uint32_t plant_at, n_coded;
+  uint32_t plant_at, plant_zeros, n_coded;
 } fj_enc;
 
 static void fj_put(fj_enc* e, uint32_t v, int nbits) {
@@ -767,9 +772,11 @@ static int fj_sample(fj_enc* e, int grad, int interp, int (*tbl)[2], int want) {
       best = code;
   }
   long code = best;
-  int bad = 0;
+  int bad = 0, long_run = 0;
   if (e->plant_kind && !e->planted && e->n_coded >= e->plant_at) {
-    if (e->plant_kind == 2) {
+    if (e->plant_kind == 3) {
+      long_run = code >= 1;
+    } else if (e->plant_kind == 2) {
       bad = 2;
       code = e->total;
     } else if (((long)(e->escape_at - 1) << bits) >= e->total) {
@@ -777,9 +784,17 @@ static int fj_sample(fj_enc* e, int grad, int interp, int (*tbl)[2], int want) {
       code = (long)(e->escape_at - 1) << bits;
     }
   }
-  if (bad)
+  if (bad || long_run)
     e->planted = 1;
-  if ((code >> bits) < e->escape_at && bad != 2) {
+  if (long_run) {
+    for (uint32_t left = e->plant_zeros; left;) {
+      const int m = left > 32 ? 32 : (int)left;
+      fj_put(e, 0, m);
+      left -= (uint32_t)m;
+    }
+    fj_put(e, 1, 1);
+    fj_put(e, (uint32_t)(code - 1), e->raw_bits);
+  } else if ((code >> bits) < e->escape_at && bad != 2) {
     const int zeros = (int)(code >> bits);
     fj_put(e, 1, zeros + 1);
     if (bits)
@@ -903,7 +918,7 @@ static int fj_block(fj_enc* e) {
 
 size_t rsx_synth_fuji_encode_strip(int raw_type, int raw_bits, int total_lines,
                                    const uint16_t* target, int plant_kind, uint32_t plant_at,
-                                   uint8_t* out, size_t cap, uint16_t* reached, int* planted) {
+                                   uint32_t plant_zeros, uint8_t* out, size_t cap, uint16_t* reached, int* planted) {
   fj_enc* e = (fj_enc*)calloc(1, sizeof(fj_enc));
   if (!e)
     return 0;
@@ -917,6 +932,7 @@ size_t rsx_synth_fuji_encode_strip(int raw_type, int raw_bits, int total_lines,
   e->cap = cap;
   e->plant_kind = plant_kind;
   e->plant_at = plant_at;
+  e->plant_zeros = plant_zeros;
   for (int j = 0; j < 3; ++j)
     for (int i = 0; i < 41; ++i) {
       e->ge[j][i][0] = e->go[j][i][0] = 1 << (raw_bits - 6);

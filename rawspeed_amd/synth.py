@@ -65,8 +65,8 @@ def lib():
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.rsx_synth_fuji_encode_strip.restype = C.c_size_t
         _lib.rsx_synth_fuji_encode_strip.argtypes = [
-            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t,
-            C.c_void_p, C.c_void_p]
+            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+            C.c_size_t, C.c_void_p, C.c_void_p]
         _lib.rsx_synth_olympus_encode.restype = C.c_size_t
         _lib.rsx_synth_olympus_encode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_size_t]
@@ -330,17 +330,21 @@ def fuji_encode_strip(raw_type, raw_bits, total_lines, target, plant=None):
     """One strip of a compressed RAF (FujiDecompressor.cpp:734-779) from `target`, (6 total_lines,
     768) pixels.  plant: None, or (kind, index) with kind 'regular' or 'escape': the first coded
     sample at or behind `index` that can carry an out-of-range code in that form gets one, and
-    the strip ends there.  Returns (the bytes, the pixels a decoder returns -- X-Trans positions
-    that take no bits hold their interpolation --, whether a code was planted)."""
+    the strip ends there; or ('long_escape', index, zeros): the first coded sample at or behind
+    `index` whose code is at least 1 is written in the escape form behind `zeros` zeros, which a
+    decoder takes like the escape's own count, and the strip goes on.  Returns (the bytes, the
+    pixels a decoder returns -- X-Trans positions that take no bits hold their interpolation --,
+    whether a code was planted)."""
     target = np.ascontiguousarray(target, dtype=np.uint16)
     assert target.shape == (6 * total_lines, 768), target.shape
-    cap = target.size * 9 + 64
+    zeros = plant[2] if plant and plant[0] == "long_escape" else 0
+    cap = target.size * 9 + 64 + zeros // 8
     out = np.empty(cap, dtype=np.uint8)
     reached = np.zeros_like(target)
     planted = C.c_int(0)
-    kind = {None: 0, "regular": 1, "escape": 2}[plant[0] if plant else None]
+    kind = {None: 0, "regular": 1, "escape": 2, "long_escape": 3}[plant[0] if plant else None]
     n = lib().rsx_synth_fuji_encode_strip(raw_type, raw_bits, total_lines, target.ctypes.data, kind,
-                                          plant[1] if plant else 0, out.ctypes.data, cap,
+                                          plant[1] if plant else 0, zeros, out.ctypes.data, cap,
                                           reached.ctypes.data, C.byref(planted))
     if n == 0:
         raise ValueError("Fuji encode failed")

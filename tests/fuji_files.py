@@ -97,14 +97,92 @@ def out_map(xtrans):
     return m[:, :, 0], m[:, :, 1]
 
 
+CSRC = os.path.join(os.path.dirname(HERE), "rawspeed_amd", "csrc")
+
+
+@functools.lru_cache(maxsize=None)
+def device_constants():
+    """FJ_WIN, FJ_CHUNK, FJ_CHUNK_WORDS of rsx_fuji.hip and ZEROS_CAP of rsx_fuji_core.h, read out
+    of the sources: the schedule below describes the kernel that is there"""
+    import re
+    out = {}
+    for fname, names in (("rsx_fuji.hip", ("FJ_WIN", "FJ_CHUNK", "FJ_CHUNK_WORDS")),
+                         ("rsx_fuji_core.h", ("ZEROS_CAP",))):
+        with open(os.path.join(CSRC, fname)) as f:
+            text = f.read()
+        for name in names:
+            m = re.findall(r"^\s*constexpr\s+\w+\s+%s\s*=\s*([\w\s*+<()-]+);" % name, text, re.M)
+            assert len(m) == 1, (fname, name, m)
+            out[name] = int(eval(m[0], {"__builtins__": {}}, dict(out)))
+    return out
+
+
+class Schedule:
+    """What fuji_strip_kernel does around the walk of one strip of `size` bytes: the chunks of a
+    pass, the window refills in front of them, and for every word the reader loads whether the
+    512-word window served it or the fallback read of memory did (FjSrc::word).  k: the words
+    loaded (Bits::k); after a fill at c bits k = ceil(c / 32) + 1."""
+
+    def __init__(self, size):
+        K = device_constants()
+        self.win, self.chunk_words, self.cap = K["FJ_WIN"], K["FJ_CHUNK_WORDS"], K["ZEROS_CAP"]
+        self.chunk_iters = K["FJ_CHUNK"]
+        self.size = size
+        self.k, self.k0, self.have_window = 0, 0, False
+        self.refills = []    # (in front of a pass's first chunk, k - k0 of the window left or None,
+        #                       the new window spans the strip's end)
+        self.window_reads = 0
+        self.fallback = []   # (k, inside the zero-count loop, 4 k + 4 > size)
+        self.failed = None   # (k, outside the window) of the fill that failed
+        self.runs_ok = 0     # samples that decoded behind fallback reads inside their zero run
+        self.max_zeros = 0
+        self._run_reads = 0
+
+    def chunk(self, first):
+        """in front of iterations [i0, i0 + FJ_CHUNK) of a pass"""
+        if not self.have_window or self.k - self.k0 + self.chunk_words > self.win:
+            left = self.k - self.k0 if self.have_window else None
+            spans = 4 * self.k < self.size < 4 * (self.k + self.win)
+            self.refills.append((first, left, spans))
+            self.k0, self.have_window = self.k, True
+
+    def fill(self, c, in_zeros):
+        """Bits::fill at c bits consumed -> False: it fails"""
+        if 32 * self.k - c >= 32:
+            return True
+        assert self.k == (c + 31) // 32 and self.have_window
+        outside = self.k - self.k0 >= self.win
+        if 4 * self.k > self.size + 8:
+            self.failed = (self.k, outside)
+            return False
+        if outside:
+            self.fallback.append((self.k, in_zeros, 4 * self.k + 4 > self.size))
+            self._run_reads += in_zeros
+        else:
+            self.window_reads += 1
+        self.k += 1
+        return True
+
+    def sample(self, zeros=None):
+        """in front of a sample (None), and behind one that decoded, with its zero count"""
+        if zeros is not None:
+            self.max_zeros = max(self.max_zeros, zeros)
+            self.runs_ok += self._run_reads > 0
+        self._run_reads = 0
+
+
 class Strip:
     """One strip.  data: the bytes to decode; target: (6 total_lines, 768) pixels to encode
     (plant: (kind, sample index), kind 'regular' or 'escape': from that coded sample on, the first
-    one that can carry an out-of-range code in that form gets one)."""
+    one that can carry an out-of-range code in that form gets one; ('long_escape', sample index,
+    Z): from that coded sample on, the first one whose code is at least 1 is written in the escape
+    form behind Z zeros -- any count of at least escape_at is the escape --, and the strip goes on).
+    sched: a Schedule that follows a decode."""
 
-    def __init__(self, P, total_lines, data=None, target=None, plant=None):
+    def __init__(self, P, total_lines, data=None, target=None, plant=None, sched=None):
         self.P, self.total_lines = P, total_lines
         self.data, self.target, self.plant = data, target, plant
+        self.sched = sched
         self.c = 0  # bits consumed
         self.out = bytearray()
         self.acc, self.nacc = 0, 0
@@ -121,8 +199,11 @@ class Strip:
         self.pixels = np.zeros((6 * total_lines, BLOCK), np.uint16)
 
     # ---- BitStreamerMSB, every request fill(32): the rule of include/rsx.h 3u ----
-    def fill(self):
-        if self.data is not None and 4 * ((self.c + 31) // 32) > len(self.data) + 8:
+    def fill(self, in_zeros=False):
+        fails = self.data is not None and 4 * ((self.c + 31) // 32) > len(self.data) + 8
+        if self.sched is not None:
+            assert self.sched.fill(self.c, in_zeros) == (not fails)
+        if fails:
             raise FujiError(ERR_INPUT_OVERFLOW)
 
     def peek32(self):
@@ -142,7 +223,7 @@ class Strip:
     def zerobits(self):
         count = 0
         while True:
-            self.fill()
+            self.fill(in_zeros=True)
             batch = self.peek32()
             n = 32 - batch.bit_length()
             count += n
@@ -157,6 +238,8 @@ class Strip:
         escape_at = P.max_bits - P.raw_bits - 1
         reg_bits = bit_diff(e[0], e[1])
         if self.data is not None:
+            if self.sched is not None:
+                self.sched.sample()
             zeros = self.zerobits()
             if zeros < escape_at:
                 bits, delta = reg_bits, zeros << reg_bits
@@ -170,6 +253,8 @@ class Strip:
             code += delta
             if code < 0 or code >= P.total:
                 raise FujiError(ERR_VALUE_RANGE)
+            if self.sched is not None:
+                self.sched.sample(zeros)
         else:
             # the residual that reaches `want`, directly or over either wrap: the smallest code
             s = -1 if grad < 0 else 1
@@ -180,9 +265,11 @@ class Strip:
                 if code < P.total and (best is None or code < best):
                     best = code
             code = best
-            bad = None
+            bad, long_run = None, None
             if self.plant and not self.planted and self.n_coded >= self.plant[1]:
-                if self.plant[0] == "escape":
+                if self.plant[0] == "long_escape":
+                    long_run = self.plant[2] if code >= 1 else None
+                elif self.plant[0] == "escape":
                     bad = ("escape", P.total)
                 elif ((escape_at - 1) << reg_bits) >= P.total:
                     bad = ("regular", (escape_at - 1) << reg_bits)
@@ -190,7 +277,15 @@ class Strip:
                 self.planted = True
                 self.stats["planted"] += 1
                 code = bad[1]
-            if (code >> reg_bits) < escape_at and not (bad and bad[0] == "escape"):
+            if long_run is not None:
+                self.planted = True
+                self.stats["planted"] += 1
+                zeros, bits = long_run, P.raw_bits
+                for at in range(0, zeros, 32):
+                    self.put(0, min(32, zeros - at))
+                self.put(1, 1)
+                self.put(code - 1, bits)
+            elif (code >> reg_bits) < escape_at and not (bad and bad[0] == "escape"):
                 zeros, bits = code >> reg_bits, reg_bits
                 self.put(1, zeros + 1)
                 if bits:
@@ -284,6 +379,8 @@ class Strip:
                 counter[k] += 1
             ge, go = self.ge[row % 3], self.go[row % 3]
             for i in range(half + 4):
+                if self.sched is not None and i % self.sched.chunk_iters == 0:
+                    self.sched.chunk(i == 0)
                 if i < half:
                     for comp in range(2):
                         grad, interp = self.even_inner(c[comp], i)
@@ -352,10 +449,12 @@ def encode_strip(P, total_lines, target, plant=None):
     return bytes(s.out), s.pixels, s
 
 
-def decode_strip(P, total_lines, data):
-    """-> (status, pixels: what the lines that decoded hold, zero behind a failure)"""
-    s = Strip(P, total_lines, data=bytes(data))
-    return s.run(), s.pixels
+def decode_strip(P, total_lines, data, trace=False):
+    """-> (status, pixels: what the lines that decoded hold, zero behind a failure); trace: and
+    the Schedule of the decode"""
+    s = Strip(P, total_lines, data=bytes(data), sched=Schedule(len(data)) if trace else None)
+    st = s.run()
+    return (st, s.pixels, s.sched) if trace else (st, s.pixels)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -454,19 +553,31 @@ def content(kind, raw_bits, width, height, seed):
     return np.clip(img, 0, q4).astype(np.uint16)
 
 
-SHAPES = ((768, 6), (768, 12), (768, 18), (792, 12), (1560, 12), (12288, 6))
+SHAPES = ((768, 6), (768, 12), (768, 18), (792, 12), (1560, 12), (12288, 6),
+          # last strips of 48, 384 and 744 columns (the others' are 24 wide), and a strip of ten lines
+          (816, 6), (1152, 6), (1512, 6), (768, 60))
+N_FIRST_SHAPES = 6  # (the cases of these came first: their contents and seeds stay what they were)
 CONTENTS = ("noisy", "flat", "saturated", "checker", "steps")
 TYPES = ((16, 14), (16, 16), (0, 14), (0, 16))
+
+
+# The medium long escape per type: (Z, sample index), picked with Schedule among the first samples
+# of the chunks in front of which the window stays: the run starts some 250 words into the window,
+# is shorter than the window and still leaves it, and the rest of its chunk reads outside the
+# window (tests/test_fuji_model.py asserts that it does)
+LONG_MEDIUM = {"x14": (8640, 1928), "x16": (8448, 1144), "b14": (8384, 632), "b16": (8512, 1912)}
+LONG_AT = 1500  # coded samples in front of the other long escapes
+ZERO_TAIL_HEAD = 900  # bytes of the strip in front of a zero tail: 225 words, inside window 0
 
 
 def case_list():
     """[dict(name, raw_type, raw_bits, width, height, content, seed, fault)] -- fault: None, or
     (kind, strip, argument) applied to the encoded strips"""
-    out = []
-    n = 0
+    out, later = [], []
+    n = m = 0
     for raw_type, raw_bits in TYPES:
         tag = "%s%d" % ("x" if raw_type == 16 else "b", raw_bits)
-        for si, (w, h) in enumerate(SHAPES):
+        for si, (w, h) in enumerate(SHAPES[:N_FIRST_SHAPES]):
             # every content on the one-strip shapes, one (cycling) on the wide ones
             kinds = CONTENTS if w == 768 and h == 6 else (CONTENTS[(si + n) % len(CONTENTS)],)
             for kind in kinds:
@@ -487,7 +598,34 @@ def case_list():
         # error for the whole image, so these are held against the model ("model_only")
         out.append(dict(base, name="%s_multi" % tag, width=1560, height=12, seed=8,
                         fault=("multi", None, None)))
-    return out
+
+        # the later shapes: one content each, cycling on; the tall strip noisy
+        for si, (w, h) in enumerate(SHAPES[N_FIRST_SHAPES:]):
+            kind = "noisy" if h == 60 else CONTENTS[(si + m) % len(CONTENTS)]
+            m += 1
+            later.append(dict(name="%s_%dx%d_%s" % (tag, w, h, kind), raw_type=raw_type,
+                              raw_bits=raw_bits, width=w, height=h, content=kind, seed=200 + m,
+                              fault=None))
+        # a valid sample no writer emits: the escape form behind more zeros than escape_at
+        escape_at = Params(raw_type, raw_bits).max_bits - raw_bits - 1
+        runs = [(escape_at + 1, LONG_AT), (96, LONG_AT), LONG_MEDIUM[tag], (20000, LONG_AT)]
+        if tag in ("x14", "b16"):
+            runs.append(((1 << 20) + 40, LONG_AT))  # (past ZEROS_CAP; a strip of 131 KB)
+        for z, at in runs:
+            later.append(dict(base, name="%s_long%d" % (tag, z), seed=7,
+                              fault=("long_escape", 0, (z, at))))
+        # a zero run that starts in window 0 and ends the strip outside it, at every size % 4
+        for z in (2400, 2401, 2402, 2403):
+            later.append(dict(base, name="%s_zero_tail%d" % (tag, z), seed=7,
+                              fault=("zero_tail", 0, z)))
+        # a failing strip 0 with the bytes of strip 1 directly behind it
+        three = dict(base, width=1560, height=12, seed=9)
+        for cut in (-9, -8, -4):
+            later.append(dict(three, name="%s_next_cut%d" % (tag, -cut), fault=("cut", 0, cut)))
+        for z in (2401, 2403):
+            later.append(dict(three, name="%s_next_zero_tail%d" % (tag, z),
+                              fault=("zero_tail", 0, z)))
+    return out + later
 
 
 PLANT_AT = 1500  # coded samples in front of a planted code: the tables have grown by then
@@ -506,7 +644,7 @@ def _built(name):
 def fault_bytes(c, s, data):
     """the bytes of strip s of case c behind its fault (the plant is the encoder's)"""
     f = c["fault"]
-    if f is None or f[0] == "plant":
+    if f is None or f[0] in ("plant", "long_escape"):
         return data
     kind, which, arg = f
     if kind == "multi":
@@ -522,11 +660,15 @@ def fault_bytes(c, s, data):
         return np.random.default_rng(arg).integers(0, 256, 2000, dtype=np.uint8).tobytes()
     if kind == "zero":
         return bytes(arg)
+    if kind == "zero_tail":
+        return data[:ZERO_TAIL_HEAD] + bytes(arg)
     raise ValueError(kind)
 
 
 def plant_of(c, s):
     f = c["fault"]
+    if f and f[0] == "long_escape" and f[1] == s:
+        return ("long_escape", f[2][1], f[2][0])
     return (f[2], PLANT_AT) if f and f[0] == "plant" and f[1] == s else None
 
 
@@ -559,13 +701,21 @@ def expected(name):
         if c["fault"] is None:
             st, p = OK, b["reached"][:, s * BLOCK:(s + 1) * BLOCK]  # (test_fuji_model decodes these)
         else:
-            st, p = decode_strip(P, lines, b["strips"][s])
+            st, p, _ = traced(name, s)
         sts.append(st)
         px[:, s * BLOCK:(s + 1) * BLOCK] = p
     rc = next((st for st in sts if st != OK), OK)
     return rc, sts, px[:, :c["width"]]
 
 
+@functools.lru_cache(maxsize=None)
+def traced(name, s):
+    """-> (status, pixels, Schedule) of the model's decode of strip s of a case"""
+    c, P, lines, img, n = _built(name)
+    return decode_strip(P, lines, build_case(name)["strips"][s], trace=True)
+
+
+@functools.lru_cache(maxsize=None)
 def lines_done(name, s):
     """how many lines of strip s of a case a decoder completes (its rows up to there are the
     reached pixels; the rows behind stay as the caller left them)"""

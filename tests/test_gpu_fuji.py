@@ -2,7 +2,9 @@
 every case of tests/fuji_files.py through rsx_fuji_decompress with host pointers and with device
 pointers, pixels and per-strip statuses against the model (which tests/test_fuji_model.py pins
 against the reference's recorded answers, tests/golden/fuji_ref.json) and the hashes of that file;
-padded pitches; a plan of several frames of mixed geometry, types and verdicts in one launch."""
+padded pitches; a plan of several frames of mixed geometry, types and verdicts in one launch; the
+strips that end early with 0xFF instead of nothing behind them; a plan of more strips than are
+resident at once."""
 import numpy as np
 import pytest
 import torch
@@ -38,15 +40,16 @@ def _check_padding(out):
     assert (pad == 0xA5).all(), "the pitch padding was written"
 
 
-def _device_call(gpu, data, w, h, pitch, lead=0):
-    """-> (status, strip statuses, (h, w) pixels); `lead` bytes in front of the container"""
+def _device_call(gpu, data, w, h, pitch, lead=0, behind=b""):
+    """-> (status, strip statuses, (h, w) pixels); `lead` bytes in front of the container, and
+    `behind` it bytes that are in the tensor and not in the call's in_bytes"""
     d = _desc(data)
     for s in range(d.n_strips):
         d.strip_offset[s] += lead
-    inp = torch.from_numpy(np.frombuffer(bytes(lead) + data, np.uint8).copy()).cuda()
+    inp = torch.from_numpy(np.frombuffer(bytes(lead) + data + behind, np.uint8).copy()).cuda()
     out = torch.full((pitch * h,), 0xA5, dtype=torch.uint8, device="cuda")
     view = abi.Image(out.data_ptr(), pitch, w, h, 1, 1)
-    st, ss = gpu.fuji_decompress(d, None, view, in_ptr=inp.data_ptr(), in_bytes=inp.numel())
+    st, ss = gpu.fuji_decompress(d, None, view, in_ptr=inp.data_ptr(), in_bytes=lead + len(data))
     host = out.cpu().numpy().reshape(h, pitch)
     assert (host[:, 2 * w:] == 0xA5).all(), "the pitch padding was written"
     return st, ss, np.ascontiguousarray(host[:, :2 * w]).view(np.uint16)
@@ -78,7 +81,8 @@ def test_case_host_and_device_pointers(gpu, golden, name):
 
 
 @pytest.mark.parametrize("name", [next(n for n in NAMES if n.startswith(p))
-                                  for p in ("x14_792x12_", "b16_1560x12_")])
+                                  for p in ("x14_792x12_", "b16_1560x12_", "x16_1512x6_",
+                                            "b14_1512x6_")])
 @pytest.mark.parametrize("extra", [2, 16, 22])
 def test_padded_pitch(gpu, name, extra):
     """pitches off and on the 16-byte grid: the narrow and the wide stores"""
@@ -145,6 +149,97 @@ def test_plan_of_mixed_jobs(gpu):
             for r in range(h):
                 covered[off + r * pitch:off + r * pitch + 2 * w] = True
         assert (host[~covered] == 0xA5).all(), "bytes outside the jobs' rectangles were written"
+    plan.close()
+
+
+def _lay_out(names, gap, gap_len, share=False):
+    """the cases as jobs of one plan: every job its own image rectangle at its own pitch class;
+    the inputs one behind the other with gap_len(k) bytes of `gap` between them (share: the jobs
+    of one case read one copy) -> (jobs, input bytes, [(name, image offset, pitch, w, h)], output
+    bytes)"""
+    jobs, expect, where = [], [], {}
+    parts = [np.full(5, gap, np.uint8)]
+    in_off, img_off = 5, 0
+    for k, name in enumerate(names):
+        b = F.build_case(name)
+        c = b["case"]
+        w, h = c["width"], c["height"]
+        pitch = (2 * w + 15) // 16 * 16 + 2 * (k % 11)
+        if not (share and name in where):
+            where[name] = in_off
+            parts += [np.frombuffer(b["data"], np.uint8), np.full(gap_len(k), gap, np.uint8)]
+            in_off += len(b["data"]) + gap_len(k)
+        j = abi.FujiJob()
+        j.desc = _desc(b["data"])
+        j.in_offset, j.in_bytes, j.img_offset = where[name], len(b["data"]), img_off
+        j.img = abi.Image(None, pitch, w, h, 1, 1)
+        jobs.append(j)
+        expect.append((name, img_off, pitch, w, h))
+        img_off += pitch * h + 6
+    return jobs, np.concatenate(parts), expect, img_off
+
+
+def _check_plan(plan, st, host, expect):
+    """every job's status, the strip statuses of the failing ones, every rectangle against the
+    model, 0xA5 outside the rectangles"""
+    covered = np.zeros(host.size, bool)
+    for k, (name, off, pitch, w, h) in enumerate(expect):
+        want, sts, px = F.expected(name)
+        assert st[k] == want, (k, name)
+        if want != F.OK:
+            assert plan.strip_status(k, len(sts)) == (abi.RSX_OK, sts), (k, name)
+        rows = np.lib.stride_tricks.as_strided(host[off:], (h, 2 * w), (pitch, 1))
+        F.check_pixels(name, np.ascontiguousarray(rows).view(np.uint16), 0xA5A5)
+        np.lib.stride_tricks.as_strided(covered[off:], (h, 2 * w), (pitch, 1))[:] = True
+    assert (host[~covered] == 0xA5).all(), "bytes outside the jobs' rectangles were written"
+
+
+def test_bytes_behind_a_strip_are_not_read_as_data(gpu):
+    """Bytes behind a strip read as zero, whatever lies there: every strip that ends early --
+    cut, 3 bytes, all zero, a zero tail that leaves the window, and those with the next strip's
+    bytes behind them -- decodes as the model says with 64 bytes of 0xFF directly behind the
+    container (in the tensor, outside in_bytes), and as jobs of one plan with 0xFF between the
+    jobs' inputs."""
+    names = [c["name"] for c in F.case_list()
+             if c["fault"] and c["fault"][0] in ("cut", "cut_to", "zero", "zero_tail")]
+    assert len(names) == 4 * (5 + 1 + 1 + 4 + 5)
+    for k, name in enumerate(names):
+        b = F.build_case(name)
+        w, h = b["case"]["width"], b["case"]["height"]
+        rc, sts, px = F.expected(name)
+        st, ss, got = _device_call(gpu, b["data"], w, h, (2 * w + 15) // 16 * 16, lead=k % 4,
+                                   behind=b"\xff" * 64)
+        assert (st, ss) == (rc, sts), name
+        F.check_pixels(name, got, 0xA5A5)
+    jobs, data, expect, out_bytes = _lay_out(names, 0xFF, lambda k: 64 + k % 4)
+    inp = torch.from_numpy(data).cuda()
+    out = torch.full((out_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    plan = gpu.fuji_plan(jobs)
+    plan.run(inp.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    rc, st, _ = plan.results()
+    _check_plan(plan, st, out.cpu().numpy(), expect)
+    plan.close()
+
+
+def test_plan_past_residency(gpu):
+    """1561 strips in one launch, more than the 1280 a device of 256 CUs holds at once (five a
+    CU): 97 jobs of one 16-strip frame reading one copy of its bytes, and three frames with
+    failing strips at different job indices; twice."""
+    good = next(n for n in NAMES if n.startswith("x14_12288x6_"))
+    names = [good] * 100
+    for k, tag in ((3, "b16"), (50, "x14"), (99, "b14")):
+        names[k] = tag + "_multi"
+    jobs, data, expect, out_bytes = _lay_out(names, 0x5A, lambda k: 3 + k % 5, share=True)
+    assert sum(j.desc.n_strips for j in jobs) == 1561 > 1280
+    inp = torch.from_numpy(data).cuda()
+    out = torch.full((out_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    plan = gpu.fuji_plan(jobs)
+    for _ in range(2):
+        out.fill_(0xA5)
+        plan.run(inp.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rc, st, _ = plan.results()
+        assert rc != 0 and sum(s != 0 for s in st) == 3
+        _check_plan(plan, st, out.cpu().numpy(), expect)
     plan.close()
 
 
