@@ -1,6 +1,7 @@
 """Compressed ORF (OlympusDecompressor) test material: an independent pure-Python model of the
 codec -- a decoder with the reference's reader bookkeeping and reach statistics, and, run forward,
-an encoder from target pixels and one from planted raw symbols --, the case list, the builders of
+an encoder from target pixels and one from planted raw symbols --, a mirror of the parse kernel's
+window bookkeeping with its constants read out of rsx_olympus.hip, the case list, the builders of
 the cases' streams (through the C writer of rawspeed_amd/csrc/synth or through the model), the
 host build's wrapper and the golden file's reader and writer.
 
@@ -14,6 +15,7 @@ import functools
 import hashlib
 import json
 import os
+import random
 import re
 import struct
 import sys
@@ -102,9 +104,99 @@ def predict(px, row, col, stats=None):
     return left if abs(a) > abs(b) else up
 
 
-def decode(data, w, h, stats=None):
+@functools.lru_cache(maxsize=None)
+def kernel_constants():
+    """OL_WIN_REGS, OL_BATCH and OL_BATCH_WORDS as rsx_olympus.hip states them (the expression
+    evaluated, not retyped) and OL_WIN_WORDS, 64 words a window register"""
+    path = os.path.join(os.path.dirname(HERE), "rawspeed_amd", "csrc", "rsx_olympus.hip")
+    src = open(path).read()
+    text = {n: re.search(r"constexpr int %s = ([^;]+);" % n, src).group(1)
+            for n in ("OL_WIN_REGS", "OL_BATCH", "OL_BATCH_WORDS", "OL_WIN_WORDS")}
+    assert text["OL_WIN_WORDS"].replace(" ", "") == "64*OL_WIN_REGS"
+    k = dict(OL_WIN_REGS=int(text["OL_WIN_REGS"]), OL_BATCH=int(text["OL_BATCH"]))
+    expr = re.sub(r"OL_\w+", lambda m: str(k[m.group(0)]), text["OL_BATCH_WORDS"])
+    assert re.fullmatch(r"[\s0-9()+*/-]+", expr), expr
+    k["OL_BATCH_WORDS"] = eval(expr.replace("/", "//"))
+    k["OL_WIN_WORDS"] = 64 * k["OL_WIN_REGS"]
+    return k
+
+
+def window_top():
+    """-> (the highest batch-start offset k - k0 that goes without a reload, the highest window
+    index a fill can load).  A batch reloads iff k - k0 + OL_BATCH_WORDS > OL_WIN_WORDS, so it
+    starts at offset OL_WIN_WORDS - OL_BATCH_WORDS at most.  Behind a symbol the cache holds at
+    least one bit, so every batch but a stream's first (which starts at offset 0) starts with
+    level >= 1; its last fill stands in front of its last symbol, behind OL_BATCH - 1 symbols of at
+    most 31 bits, and leaves a level of at most 63.  With n words loaded:
+    1 + 32 n - 31 (OL_BATCH - 1) <= 63, which for OL_BATCH = 64 is 32 n <= 63 * 31 + 63 - 1 and
+    n <= 62.  The stream's first batch loads one more at most, from offset 0."""
+    k = kernel_constants()
+    start = k["OL_WIN_WORDS"] - k["OL_BATCH_WORDS"]
+    words = (31 * (k["OL_BATCH"] - 1) + 63 - 1) // 32
+    return start, start + words - 1
+
+
+class Window:
+    """olympus_parse_kernel's window bookkeeping (k, k0, the reload rule in front of every batch of
+    OL_BATCH symbols of a row) beside the model's reader: which batch-start offsets k - k0 occur,
+    which window indices a fill loads, which of them with a non-zero word, and the stream's tail.
+    The model stops at a failing fill where the kernel finishes its batch on zeros."""
+    TOP = 224  # (the upper half of the window's last register)
+
+    def __init__(self):
+        k = kernel_constants()
+        self.batch_syms, self.batch_words, self.win_words = \
+            k["OL_BATCH"], k["OL_BATCH_WORDS"], k["OL_WIN_WORDS"]
+        self.k0 = None
+        self.starts, self.loaded, self.nonzero = set(), set(), set()
+        self.reloads = []             # (k - k0 in front of a reload, words its batch then loaded)
+        self._reloaded = None
+        self.nonzero_top = 0          # words loaded at index TOP or above that were not zero
+        self.past_end = False         # bits behind the stream's last byte were consumed
+        self.partial_nonzero = False  # ... and size % 4 != 0 with a non-zero byte in the last word
+        self.residue = None           # size % 4
+
+    def batch(self, k):
+        self._close(k)
+        if self.k0 is None:
+            self.k0 = k
+        elif k - self.k0 + self.batch_words > self.win_words:
+            self._reloaded = (k - self.k0, k)
+            self.k0 = k
+        self.starts.add(k - self.k0)
+
+    def _close(self, k):
+        if self._reloaded is not None:
+            self.reloads.append((self._reloaded[0], k - self._reloaded[1]))
+        self._reloaded = None
+
+    def late_reload_overruns(self, late):
+        """whether a reload rule `late` words too lenient would let a batch of this stream run
+        past the window: a batch that reloads at an offset the lenient rule lets pass, and then
+        loads more words than the window holds behind that offset"""
+        start = self.win_words - self.batch_words
+        return any(at <= start + late and at + words > self.win_words for at, words in self.reloads)
+
+    def load(self, k, word):
+        j = k - self.k0
+        assert 0 <= j < self.win_words, "the walk outran its window"
+        self.loaded.add(j)
+        if word:
+            self.nonzero.add(j)
+            self.nonzero_top += j >= self.TOP
+
+    def tail(self, bits, pos, k):
+        self._close(k)
+        size = len(bits)
+        self.residue = size % 4
+        self.past_end = pos > 8 * size
+        self.partial_nonzero = self.past_end and size % 4 != 0 and any(bits[size - size % 4:])
+
+
+def decode(data, w, h, stats=None, win=None):
     """-> (status, (h, w) uint16 pixels or None).  The reader keeps the reference's books (words
-    loaded, fill level), not the closed form; `stats` (a Counter) gets the reach statistics."""
+    loaded, fill level), not the closed form; `stats` (a Counter) gets the reach statistics, `win`
+    (a Window) the kernel's window bookkeeping."""
     st = validate(len(data), w, h)
     if st != OK:
         return st, None
@@ -113,16 +205,22 @@ def decode(data, w, h, stats=None):
     padded = bits + bytes(16)
     pos, loaded, level = 0, 0, 0
     px = [[0] * w for _ in range(h)]
+    batch = win.batch_syms if win is not None else 0
     for row in range(h):
         carry = [[0, 0, 0], [0, 0, 0]]
         if stats is not None and pos % 8:
             stats["row_start_off_byte"] += 1
         prow = px[row]
         for col in range(w):
+            if win is not None and col % batch == 0:
+                win.batch(loaded)
             # fill(32)
             if level < 32:
                 if 4 * loaded > size + 8:
                     return ERR_INPUT_OVERFLOW, None
+                if win is not None:
+                    word = padded[4 * loaded:4 * loaded + 4].ljust(4, b"\0")
+                    win.load(loaded, int.from_bytes(word, "big"))
                 loaded += 1
                 level += 32
             at = pos >> 3
@@ -176,6 +274,8 @@ def decode(data, w, h, stats=None):
                 if p + d16 < 0:
                     stats["wrap_below"] += 1
             prow[col] = v & 0xFFFF
+    if win is not None:
+        win.tail(bits, pos, loaded)
     return OK, np.array(px, dtype=np.uint16).reshape(h, w)
 
 
@@ -367,12 +467,49 @@ PLANTED = {
                                     _reg(1, 1)])),
 }
 
+
+def dense_symbols(w, h, seed, mixed=False):
+    """w h planted symbols from random.Random(seed), every one the 31-bit escape form with random
+    sign, low bits, high field, low field and skipped bit: every word of the stream is then random
+    and every pixel depends on it.  `mixed`: behind every third batch of 64 a run of 3 .. 40
+    regular symbols of every length, so that carry[0], carry[2] and numLowBits move while the
+    window's top is in use."""
+    rng = random.Random(seed)
+    out, run = [], 0
+    for k in range(w * h):
+        if mixed and k % 192 == 191:
+            run = rng.randrange(3, 41)
+        if run:
+            run -= 1
+            out.append(_reg(rng.randrange(12), rng.getrandbits(15), rng.getrandbits(1),
+                            rng.getrandbits(2)))
+        else:
+            out.append(_esc(rng.getrandbits(13), rng.getrandbits(15), rng.getrandbits(1),
+                            rng.getrandbits(2), rng.getrandbits(1)))
+    return out
+
+
 GEOMETRY = ((2, 2), (4, 2), (2, 4), (4, 4), (6, 6), (66, 4), (130, 6), (258, 4), (386, 4),
             (4, 130), (4, 258), (10400, 2), (2, 7792))
 CONTENTS = ("flat0", "flat4095", "flat65535", "checker", "steps", "noise16", "wrap")
 REFUSED = ((10402, 2), (2, 7794), (3, 2), (2, 3), (0, 2))
 CUT_SHAPE = (130, 4, 6)  # a noise image of 130 x 4, read as 130 x 6: the last two rows read zeros
 MID = (1024, 768)
+# dense rows, 31 bits a symbol: a row's short last batch shifts where the next row's batches start
+# in the window, so the first three widths sweep the batch-start offsets up to the last one; the
+# 202-wide rows come to a batch at offset 195, the first where a missed reload outruns the window
+DENSE = ((194, 8), (196, 8), (198, 8), (202, 8))
+DENSE_MIXED = (198, 12)
+# a 6 x 6 noise image cut 1 .. 12 bytes short, from two seeds whose full lengths differ mod 4
+TRUNC_SEEDS = (901, 902)
+TRUNC_CUTS = tuple(range(1, 13))
+# plane sizes 63 .. 129 on both axes: ragged last tiles under a second band, short last bands
+# over several tiles; 10400 x 130 is the smallest frame whose second band reads the last entry of
+# the reconstruction's prev_row
+RAGGED = ((126, 130), (128, 128), (130, 130), (258, 130), (130, 258), (254, 126), (256, 258))
+WIDEST_BANDED = (MAX_X, 130)
+# (not through the model's encoder)
+SLOW = ("f_%dx%d_random" % MID, "g_%dx%d_noise16" % WIDEST_BANDED)
 
 
 @functools.lru_cache(maxsize=None)
@@ -405,6 +542,19 @@ def case_list():
                       random=400))
     for w, h in REFUSED:
         cases.append(dict(name="x_%dx%d" % (w, h), kind="refused", width=w, height=h))
+    for w, h in DENSE:
+        cases.append(dict(name="d_%dx%d" % (w, h), kind="plant", width=w, height=h, dense=w))
+    cases.append(dict(name="d_mixed_%dx%d" % DENSE_MIXED, kind="plant", width=DENSE_MIXED[0],
+                      height=DENSE_MIXED[1], dense=7, mixed=True))
+    for seed in TRUNC_SEEDS:
+        for cut in TRUNC_CUTS:
+            cases.append(dict(name="t_%d_cut_%d" % (seed, cut), kind="bytes", width=6, height=6,
+                              trunc=(seed, cut)))
+    for k, (w, h) in enumerate(RAGGED + (WIDEST_BANDED,)):
+        cases.append(dict(name="g_%dx%d_noise16" % (w, h), kind="pixels", width=w, height=h,
+                          content="noise16", seed=600 + k))
+    cases.append(dict(name="g_130x130_wrap", kind="pixels", width=130, height=130, content="wrap",
+                      seed=0))
     assert len({c["name"] for c in cases}) == len(cases)
     return tuple(cases)
 
@@ -468,6 +618,8 @@ def _build(name, encoder):
     if c["kind"] == "pixels":
         return enc(content(c["content"], w, h, c["seed"]))
     if c["kind"] == "plant":
+        if "dense" in c:
+            return pl(w, h, dense_symbols(w, h, c["dense"], c.get("mixed", False)))
         return pl(w, h, list(PLANTED[c["plant"]][2]))
     if c["kind"] == "refused":
         return bytes(SKIP + 16)
@@ -477,6 +629,9 @@ def _build(name, encoder):
         return bytes([c["byte"]]) * worst_bytes(w, h)
     if "random" in c:
         return np.random.default_rng(c["random"]).bytes(worst_bytes(w, h))
+    if "trunc" in c:
+        seed, cut = c["trunc"]
+        return enc(content("noise16", w, h, seed))[:-cut]
     if "cut" in c:
         full = enc(content("noise12", CUT_SHAPE[0], CUT_SHAPE[1], 500))
         n = cut_lengths(full)[c["cut"]]
@@ -492,13 +647,18 @@ def build_case(name, encoder="c"):
 @functools.lru_cache(maxsize=None)
 def _model(name):
     c = case(name)
-    stats = collections.Counter()
-    return decode(_build(name, "c"), c["width"], c["height"], stats) + (stats,)
+    stats, win = collections.Counter(), Window()
+    return decode(_build(name, "c"), c["width"], c["height"], stats, win) + (stats, win)
 
 
 def expected(name):
     """the model's answer: (status, pixels or None)"""
     return _model(name)[:2]
+
+
+def window(name):
+    """the kernel's window bookkeeping over the case's stream (a Window)"""
+    return _model(name)[3]
 
 
 def reach(names=None):
@@ -537,7 +697,8 @@ def host_decode(data, w, h, fill=0xA5A5, pad=0):
     from rawspeed_amd import abi
     buf = np.full((max(h, 1), max(w, 0) + pad), fill, np.uint16)
     view = abi.Image(buf.ctypes.data, 2 * (max(w, 0) + pad), w, h, 1, 1)
-    a = np.frombuffer(bytes(data) + b"\0", np.uint8)  # (a pointer for no bytes)
+    # (a pointer for no bytes; what lies behind the stream must not matter, so it is not zero)
+    a = np.frombuffer(bytes(data) + b"\xff" * 16, np.uint8)
     rc = host_lib().rsx_olympus_host_decode(a.ctypes.data, len(data), C.byref(view))
     return rc, buf
 

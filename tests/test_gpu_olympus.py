@@ -3,7 +3,8 @@ C-ABI: every case of tests/olympus_files.py through rsx_olympus_decompress with 
 and with host pointers, and through a plan; pixels against the host build bit for bit, hashes
 against the reference's recorded ones (tests/golden/olympus_ref.json), statuses identical.  The
 walk writes differences into the image, so every image buffer starts as 0xA5A5 and the bytes of a
-row past 2 dim_x, in front of img_offset and behind the last row must stay as they were."""
+row past 2 dim_x, in front of img_offset and behind the last row must stay as they were.  Behind
+every stream lie 16 bytes of 0xFF: what a walk reads behind its stream is zero, not memory."""
 import numpy as np
 import pytest
 import torch
@@ -17,7 +18,10 @@ pytestmark = pytest.mark.gpu
 CASES = F.case_list()
 NAMES = [c["name"] for c in CASES]
 GEOMETRY = [c["name"] for c in CASES if c["name"].startswith("g_")]
+DENSE = [c["name"] for c in CASES if c["name"].startswith("d_")]
+TRUNCATED = [c["name"] for c in CASES if c["name"].startswith("t_")]
 LEAD, TAIL = 6, 10  # canary bytes around a device image
+BEHIND = b"\xff" * 16  # what lies behind a stream
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +56,7 @@ def _check_canaries(host, rects):
 
 def _device_call(gpu, data, w, h, pitch, lead_in=0):
     """-> (status, the output buffer on the host); the image lies LEAD bytes into the buffer"""
-    inp = torch.from_numpy(np.frombuffer(bytes(lead_in) + data + b"\0", np.uint8).copy()).cuda()
+    inp = torch.from_numpy(np.frombuffer(bytes(lead_in) + data + BEHIND, np.uint8).copy()).cuda()
     out = torch.full((LEAD + pitch * max(h, 1) + TAIL,), 0xA5, dtype=torch.uint8, device="cuda")
     view = abi.Image(out.data_ptr() + LEAD, pitch, w, h, 1, 1)
     st = gpu.olympus_decompress(None, view, in_ptr=inp.data_ptr() + lead_in, in_bytes=len(data))
@@ -96,29 +100,36 @@ def test_case_device_and_host_pointers(gpu, golden, name):
             assert (out.buf == 0xA5).all(), "a failed decode wrote into the caller's image"
 
 
-def _plan_of(gpu, names):
+def _plan_of(gpu, names, every_alignment=False):
     """-> (plan, input tensor, output size, [(name, img_offset, pitch, w, h)]); the streams lie at
-    staggered odd offsets of one input buffer, the images at even ones of one output buffer"""
+    staggered odd offsets of one input buffer (every_alignment: back to back behind gaps of 0xFF,
+    job k at an offset that is k + k // 4 mod 4, so that
+    every length mod 4 meets several alignments), the images at even ones of one output buffer"""
     jobs, parts, where = [], [], []
     in_off, img_off = 0, 4
     for k, name in enumerate(names):
         c = F.case(name)
         w, h = c["width"], c["height"]
         data = F.build_case(name)["data"]
-        gap = 1 + 2 * (k % 4)
-        gap += (in_off + gap + 1) % 2  # (an odd in_offset)
-        parts += [np.full(gap, 0x5A, np.uint8), np.frombuffer(data, np.uint8)]
+        if every_alignment:
+            gap = 1 + (k + k // 4 - in_off - 1) % 4
+        else:
+            gap = 1 + 2 * (k % 4)
+            gap += (in_off + gap + 1) % 2  # (an odd in_offset)
+        parts += [np.full(gap, 0xFF if every_alignment else 0x5A, np.uint8),
+                  np.frombuffer(data, np.uint8)]
         in_off += gap
         pitch = _pitch(name, w) + 2 * (k % 3)
         j = abi.OlympusJob()
-        assert in_off % 2 == 1 and img_off % 2 == 0
+        assert in_off % 4 == (k + k // 4) % 4 if every_alignment else in_off % 2 == 1
+        assert img_off % 2 == 0
         j.in_offset, j.in_bytes, j.img_offset = in_off, len(data), img_off
         j.img = abi.Image(None, pitch, w, h, 1, 1)
         jobs.append(j)
         where.append((name, img_off, pitch, w, h))
         in_off += len(data)
         img_off += pitch * max(h, 0) + 6 + 2 * (k % 2)
-    inp = torch.from_numpy(np.concatenate(parts + [np.zeros(1, np.uint8)])).cuda()
+    inp = torch.from_numpy(np.concatenate(parts + [np.frombuffer(BEHIND, np.uint8)])).cuda()
     return gpu.olympus_plan(jobs), inp, img_off, where
 
 
@@ -157,6 +168,45 @@ def test_plan_of_all_geometries_at_odd_offsets(gpu, golden):
         assert np.array_equal(got, F.host_expected(name)[1]), name
         assert F.sha_rows(got) == golden[name]["sha256"]
     _check_canaries(host, [x[1:] for x in where])
+    plan.close()
+
+
+def test_plan_of_the_truncated_streams_at_every_alignment(gpu, golden):
+    """the streams cut short, back to back with 0xFF between them, their first bytes at all four
+    alignments: what a walk reads behind its stream's end is zero, not the gap or the next stream"""
+    plan, inp, n, where = _plan_of(gpu, TRUNCATED, every_alignment=True)
+    want = [F.host_expected(name)[0] for name in TRUNCATED]
+    by_residue = {(len(F.build_case(name)["data"]) - F.SKIP) % 4 for name, st in zip(TRUNCATED, want)
+                  if st == F.OK}
+    assert by_residue == {0, 1, 2, 3} and set(want) == {F.OK, F.ERR_INPUT_OVERFLOW}
+    rc, st, host = _run(plan, inp, n)
+    assert st == want
+    assert rc == F.ERR_INPUT_OVERFLOW
+    for (name, off, pitch, w, h), status in zip(where, want):
+        if status == F.OK:
+            got = _rows(host, off, pitch, w, h)
+            assert np.array_equal(got, F.host_expected(name)[1]), name
+            assert F.sha_rows(got) == golden[name]["sha256"]
+    _check_canaries(host, [x[1:] for x in where])
+    plan.close()
+
+
+def test_plan_of_the_dense_rows_run_twice(gpu, golden):
+    """every window word in use and non-zero, four walks side by side, twice into one buffer"""
+    plan, inp, n, where = _plan_of(gpu, DENSE)
+    out = torch.full((n,), 0xA5, dtype=torch.uint8, device="cuda")
+    hosts = []
+    for _ in range(2):
+        plan.run(inp.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rc, st, _ = plan.results()
+        assert rc == 0 and st == [0] * len(DENSE)
+        hosts.append(out.cpu().numpy())
+    assert np.array_equal(hosts[0], hosts[1])
+    for name, off, pitch, w, h in where:
+        got = _rows(hosts[1], off, pitch, w, h)
+        assert np.array_equal(got, F.host_expected(name)[1]), name
+        assert F.sha_rows(got) == golden[name]["sha256"]
+    _check_canaries(hosts[1], [x[1:] for x in where])
     plan.close()
 
 

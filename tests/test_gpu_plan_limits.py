@@ -12,8 +12,8 @@ jobs whose input or output lies past 2^31 and 2^32 bytes of the plan's buffers.
   offsets     For every plan type, one small job placed at offset 0, straddling 2^31,
               straddling 2^32 and wholly above 2^32 -- of the input and, separately, of the
               output -- and one job whose own rows cross 4 GiB (a pitch of 1 MiB + 16, 4100
-              rows).  Every copy against the oracle (Phase One / ARW2: the source image / the
-              numpy model) in status, consumed bytes and pixels; every byte of the output buffer
+              rows).  Every copy against the oracle (Phase One / ARW2 / Olympus: the source
+              image / the numpy model / the host build) in status, consumed bytes and pixels; every byte of the output buffer
               a job does not own is still 0xA5.
 
 The two 6.6 GB buffers are allocated once for the module, and a plan is given a base 2 GiB into
@@ -30,6 +30,7 @@ import cases as C
 import golden_cases as G
 import iiq_files as I
 import nikon_cases as N
+import olympus_files as O
 import samsung_v2_cases as V2
 from oracle_lib import HostImage
 from rawspeed_amd import abi, synth
@@ -423,6 +424,17 @@ def _sony_arw2(oracle, tall):
     return c
 
 
+def _olympus(oracle, tall):
+    # (130 wide: three batches of the walk a row, two tiles of the reconstruction; the tall image
+    # has 33 bands; the expected image is the host build's)
+    w, h = 130, TALL_ROWS if tall else 6
+    data = synth.olympus_encode(O.content("noise12", w, h, 0xB10 + tall))
+    st, px = O.host_decode(data, w, h)
+    want = HostImage(w, h)
+    want.pixels()[:] = px
+    return Case("olympus_plan", abi.OlympusJob, None, np.frombuffer(data, np.uint8), want, st)
+
+
 KINDS = {
     "unpack_u16": _unpack, "unpack_f32": _unpack_f32, "unpack_variant": _unpack_variant,
     "ljpeg_1c": _ljpeg(1), "ljpeg_2c": _ljpeg(2), "ljpeg_3c": _ljpeg(3), "ljpeg_4c": _ljpeg(4),
@@ -430,6 +442,7 @@ KINDS = {
     "nikon_split": _nikon(True), "nikon_curve": _nikon(False), "pentax": _pentax,
     "samsung_v1": _samsung_v1, "samsung_v2": _samsung_v2, "hasselblad": _hasselblad,
     "sony_arw1": _sony_arw1, "phase_one": _phase_one, "sony_arw2": _sony_arw2,
+    "olympus": _olympus,
 }
 
 
