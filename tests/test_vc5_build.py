@@ -71,6 +71,38 @@ def test_merge_stores_16_bytes_and_memory_accesses_stay_global(kernels):
     assert not re.search(r"\bflat_(load|store)", asm)
 
 
+def test_the_test_material_mirrors_the_launch_geometry():
+    """tests/vc5_files.py names the sizes the device tests place their edges by -- the window and
+    the words behind it, the merge, level and low-pass decompositions, the image sides -- and the
+    tests assert from them that an input reaches its path.  Read here out of the sources, so that
+    a retuned kernel cannot move an edge away from its test unnoticed."""
+    import vc5_files as V
+    hip = open(os.path.join(CSRC, "rsx_vc5.hip")).read()
+    core = open(os.path.join(CSRC, "rsx_vc5_core.h")).read()
+
+    def const(name, text=hip):
+        return re.search(r"constexpr \w+ (?:\w+ = [^,;]+, )*%s = ([^,;]+)[,;]" % name, text).group(1).strip()
+
+    assert const("SEG_BITS", core) == "RSX_VC5_SEG_BITS"
+    assert int(re.search(r"#define RSX_VC5_SEG_BITS (\d+)", core).group(1)) == V.SEG_BITS
+    assert const("VC_THREADS") == "RSX_VC5_THREADS"
+    assert int(re.search(r"#define RSX_VC5_THREADS (\d+)", hip).group(1)) == V.LANES
+    assert const("VC_WIN_BITS") == "VC_THREADS * SEG_BITS" and V.WIN_BITS == V.LANES * V.SEG_BITS
+    assert const("VC_WIN_WORDS") == "VC_WIN_BITS / 32"
+    assert const("VC_WIN_LOAD") == "VC_WIN_WORDS + %d" % V.WIN_EXTRA_WORDS
+    assert (int(const("VC_TILE_X")), int(const("VC_TILE_Y"))) == (V.LEVEL_X, V.LEVEL_Y)
+    assert int(const("VC_MERGE_ROWS")) == V.MERGE_ROWS
+    assert (int(const("VC_MIN_DIM")), int(const("VC_MAX_DIM"))) == (V.MIN_DIM, V.MAX_DIM)
+    # the low-pass band: VC_LP_SPLIT workgroups of 256 lanes, and the loop's stride
+    split = int(const("VC_LP_SPLIT"))
+    assert "__launch_bounds__(256) vc5_lowpass_kernel" in hip and "i += 256u * VC_LP_SPLIT" in hip
+    assert "dim3(n_lp * VC_LP_SPLIT), dim3(256)" in hip and split * 256 == V.LP_STRIDE
+    # the merge: 64 lanes of 4 cells a row (the kernel and the plan's tile count write them out)
+    lanes, cells = re.search(r"c0 = (\d+)u \* \(I\.tx \* (\d+)u \+ \(threadIdx\.x & 63u\)\)", hip).group(2, 1)
+    assert int(cells) == V.MERGE_LANE_CELLS and int(lanes) * int(cells) == V.MERGE_CELLS
+    assert "tx < (M.w2 + %du) / %du" % (V.MERGE_CELLS - 1, V.MERGE_CELLS) in hip
+
+
 def test_sources_are_part_of_the_core_library():
     assert "rsx_vc5.hip" in build.CORE_SOURCES
     assert "rsx_vc5.h" in build.CORE_HEADERS and "rsx_vc5_core.h" in build.CORE_HEADERS

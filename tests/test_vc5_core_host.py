@@ -4,6 +4,7 @@ walks in the band kernel's window scheme, and one wavelet level, against the num
 AddressSanitizer and UBSan where g++ has their runtimes, every chunk in an allocation of exactly
 its size.  Nothing here is loaded into Python under a sanitizer.  No GPU needed."""
 import ctypes as C
+import functools
 import os
 import struct
 import subprocess
@@ -102,8 +103,90 @@ def test_rounds_are_what_the_model_counts(host):
     stream = V.encode_values(vals)
     for lanes in (4, 16, 256):
         st, _, win, rnd = _band(host, V.book(), stream, 1, vals.size, lanes)
-        model = V.rounds_needed(stream, 1, lanes)
+        model = V.rounds_needed(stream, 1, vals.size, lanes)
         assert st == V.OK and (win, rnd) == (len(model), sum(model)), (lanes, win, rnd, model)
+
+
+EDGE_LANES = (2, 3, 256, 1024)
+EDGE_D = (-27, -1, 0, 1, 26)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_corpus():
+    """[(name, stream, quant, n, lanes, k, d, last)]: dense bands whose end marker starts d bits
+    from the end of window k of `lanes` segments -- the marker sound, with its sign bit set, and a
+    zero run in its place -- the chunk ending with the marker's last byte or padded to four.
+    last: the bits of the last coefficient's symbol, or None; d = 26 comes with one of 27 bits,
+    which starts in window k, and with one of 3, which starts in the window behind it."""
+    out = []
+    rng = np.random.default_rng(0xED6E)
+    _, by_run, marker = V._rows_by_key()
+    dense = V.symbols_of(V.random_band(rng, 1, 2 * V.WIN_BITS // 3, 1.0, 200))
+    for lanes in EDGE_LANES:
+        for k in (1, 2):
+            for d, last in [(d, None) for d in EDGE_D[:-1]] + [(26, 27), (26, 3)]:
+                target = k * lanes * V.SEG_BITS + d
+                syms, n = V.symbols_ending_at(dense, target, last=last)
+                for kind, end in (("sound", (marker, False)), ("sign", (marker, True)), ("run", (by_run[12], False))):
+                    for pad in ((1, 4) if lanes < 256 else (1,) if k == 1 else (4,)):
+                        stream = V.encode_symbols(syms + [end], marker=False, pad_to=pad)
+                        name = "%s_%d_%d_%+d_%s_%d" % (kind, lanes, k, d, last, pad)
+                        out.append((name, stream, -3, n, lanes, k, d, last))
+    return out
+
+
+def test_the_band_end_helper_lands_on_any_bit_and_count(host):
+    rng = np.random.default_rng(7)
+    dense = V.symbols_of(V.random_band(rng, 1, 600, 1.0, 200))
+    for target, n, last in ((3, None, None), (97, None, None), (1000, None, 27), (1001, 700, None),
+                            (1002, 2000, 3), (4099, 9000, 27)):
+        syms, count = V.symbols_ending_at(dense, target, n=n, last=last)
+        assert sum(V.symbol_bits(s)[0] for s in syms) == target
+        assert count == sum(V.symbol_bits(s)[1] for s in syms) and (n is None or count == n)
+        assert last is None or V.symbol_bits(syms[-1]) == (last, 1)
+        stream = V.encode_symbols(syms, pad_to=1)
+        assert 8 * stream.size == -(-(target + 27) // 8) * 8
+        st, got, _, _ = _band(host, V.book(), stream, 2, count, 3)
+        want_st, want = V.model_band(stream, 2, count)
+        assert st == want_st == V.OK and np.array_equal(got, want)
+    with pytest.raises(ValueError):
+        V.symbols_ending_at(dense, 5)         # (no value symbol has 1, 2 or 5 bits)
+
+
+def test_band_end_at_a_window_edge(host):
+    """verdict and coefficients as the model's, windows and rounds as rounds_needed counts them:
+    the band ends in the window whose lane reaches the last coefficient, and its marker is read
+    from behind that window when it starts there"""
+    for name, stream, quant, n, lanes, k, d, last in edge_corpus():
+        want_st, want = V.model_band(stream, quant, n)
+        assert want_st == (V.OK if name.startswith("sound") else V.MARKER), name
+        st, got, win, rnd = _band(host, V.book(), stream, quant, n, lanes)
+        assert st == want_st, (name, st, want_st)
+        if st == V.OK:
+            assert np.array_equal(got, want), name
+        model = V.rounds_needed(stream, quant, n, lanes)
+        assert (win, rnd) == (len(model), sum(model)), (name, win, rnd, model)
+        assert win == (k + 1 if last == 3 else k), (name, win)
+
+
+def test_rounds_needed_without_the_coefficient_count_walks_too_far(host):
+    """what the count is for: a band that ends with a window's last segment (its marker starts at
+    the edge or a bit behind it) ends in that window, as the core does; the walk that knows the
+    stream alone goes on into the next one"""
+    differ = 0
+    for name, stream, quant, n, lanes, k, d, last in edge_corpus():
+        if not name.startswith("sound") or lanes < 256:
+            continue
+        new = V.rounds_needed(stream, quant, n, lanes)
+        old = V.rounds_needed_by_stream_alone(stream, quant, lanes)
+        st, _, win, rnd = _band(host, V.book(), stream, quant, n, lanes)
+        assert (win, rnd) == (len(new), sum(new))
+        if d in (0, 1) or last == 27:
+            assert len(old) == len(new) + 1 == k + 1 and (win, rnd) != (len(old), sum(old)), name
+            differ += 1
+        else:
+            assert old == new, name
+    assert differ == 12
 
 
 def test_code_books_the_table_builder_refuses(host):
@@ -189,6 +272,11 @@ def test_corpora_through_the_sanitizer_program(host):
                     st, got, win, rnd = _band(host, r, stream, quant, n, lanes)
                     want.append("band %d %d %d %d" % (st, win, rnd, _fnv(got) if st == 0 else 0))
             if book_rows is rows:
+                for name, stream, quant, n, lanes, _, _, _ in edge_corpus():
+                    f.write(struct.pack("<IIiII", 1, len(stream), quant, n, lanes))
+                    f.write(bytes(stream))
+                    st, got, win, rnd = _band(host, rows, stream, quant, n, lanes)
+                    want.append("band %d %d %d %d" % (st, win, rnd, _fnv(got) if st == 0 else 0))
                 for w, h, pitch0, shift, clamp, b0, b in level_corpus():
                     f.write(struct.pack("<IIIIii", 2, w, h, pitch0, shift, clamp))
                     f.write(b0[:h].tobytes() + b[0].tobytes() + b[1].tobytes() + b[2].tobytes())

@@ -23,6 +23,12 @@ GOLDEN = os.path.join(HERE, "golden", "vc5_ref.json")
 OK, MARKER, CODE, OVERREAD, RANGE, UNSUPPORTED = 0, 1, 3, 5, 10, 7
 SEG_BITS, LANES = 128, 1024          # rsx_vc5.hip: bits of a segment, segments of a window
 WIN_BITS = SEG_BITS * LANES
+WIN_EXTRA_WORDS = 4                  # words loaded behind a window, for a symbol behind its last segment
+MERGE_CELLS, MERGE_ROWS = 256, 32    # cells a row and cell rows of a merge workgroup (64 lanes x 4 cells)
+MERGE_LANE_CELLS = 4
+LEVEL_X, LEVEL_Y = 64, 4             # cells of a level workgroup
+LP_STRIDE = 16 * 256                 # low-pass fields a trip of the loop: 16 workgroups of 256 lanes
+MIN_DIM, MAX_DIM = 34, 65534         # image sides the decoder takes
 WHITELEVEL = 50717
 RUNS = (320, 180, 100, 60, 32, 20, 12, 1)   # the book's zero runs, longest first
 
@@ -379,32 +385,44 @@ def model_band(data, quant, n):
         pos += length
 
 
-def rounds_needed(data, quant, lanes=LANES):
-    """Parse rounds per window of the band kernel's scheme on this stream: every segment parsed
-    from entry 0, then from the exit of the segment in front of it as of the round before, until
-    nothing changes.  [rounds of window 0, 1, ..] up to the window with the band's end."""
+def rounds_needed(data, quant, n, lanes=LANES, carries=None):
+    """Parse rounds per window of the band kernel's scheme on this stream of a band of n
+    coefficients: every segment parsed from entry 0, then from the exit of the segment in front of
+    it as of the round before, until nothing changes.  [rounds of window 0, 1, ..] up to the window
+    in which the true chain reaches coefficient n or stops at a symbol that fails the band -- the
+    last one the kernel loads: a band that ends with a window's last segment has its end marker
+    read from the words behind that window.  carries: a list that gets the entry offset of lane 0
+    of every window walked."""
     data = np.asarray(data, np.uint8)
     bits = bit_string(data) + "0" * (SEG_BITS * lanes)
     lim = start_limit(data.size)
+    seen = {}
 
     def walk(pos, end):
+        """(exit, coefficients) of the symbols that start in [pos, end); exit None: stopped"""
+        count = 0
         while pos < end:
             if pos > lim:
-                return None
-            s = read_symbol(bits, pos)
+                return None, count
+            if pos not in seen:                           # (guessed parses soon read true symbols)
+                seen[pos] = read_symbol(bits, pos)
+            s = seen[pos]
             if s is None or s[1] == 0 or not -32768 <= s[2] * quant <= 32767:
-                return None
+                return None, count
+            count += s[1]
             pos += s[3]
-        return pos - end
+        return pos - end, count
 
-    out, carry, w = [], 0, 0
+    out, carry, w, p = [], 0, 0, 0
     while True:
         base = w * SEG_BITS * lanes
+        if carries is not None:
+            carries.append(carry)
         entry = [carry] + [0] * (lanes - 1)
         ex = [walk(base + k * SEG_BITS + entry[k], base + (k + 1) * SEG_BITS) for k in range(lanes)]
         rounds = 1
         while True:
-            new = [carry] + [0 if e is None else e for e in ex[:-1]]
+            new = [carry] + [0 if e is None else e for e, _ in ex[:-1]]
             changed = [k for k in range(lanes) if new[k] != entry[k]]
             if not changed:
                 break
@@ -413,13 +431,74 @@ def rounds_needed(data, quant, lanes=LANES):
                 entry[k] = new[k]
                 ex[k] = walk(base + k * SEG_BITS + entry[k], base + (k + 1) * SEG_BITS)
         out.append(rounds)
-        # the true chain ends in this window when a walk on it stopped
-        k = 0
-        while k < lanes and ex[k] is not None:
-            k += 1
-        if k < lanes or base > lim:
-            return out
-        carry, w = ex[-1], w + 1
+        # the true chain: the first lane that stops, or that holds coefficient n - 1, ends the band
+        for e, count in ex:
+            if e is None or p + count >= n:
+                return out
+            p += count
+        carry, w = ex[-1][0], w + 1
+
+
+def rounds_needed_by_stream_alone(data, quant, lanes=LANES):
+    """rounds_needed as it was before it took the coefficient count: it walks on until a walk of
+    the true chain stops, into windows the kernel never loads when the band ends with a window.
+    Kept for the test that shows the difference (tests/test_vc5_core_host.py)."""
+    return rounds_needed(data, quant, 1 << 62, lanes)
+
+
+def symbol_bits(symbol):
+    """(bits, coefficients) of a symbol (row, negative)"""
+    size, _, count, value = book()[symbol[0]]
+    return size + (1 if value != 0 else 0), count
+
+
+def symbols_ending_at(symbols, target, n=None, last=None):
+    """(symbols, coefficients): a stream whose encoded length -- in front of the end marker -- is
+    exactly `target` bits.  A prefix of `symbols` up to about target - 80 bits, then value symbols
+    whose lengths add up to the rest (the book has value symbols of 3, 4 and 6 .. 27 bits).  With
+    n the band has exactly n coefficients: the zero runs that make up for them go in front.
+    last: the bits of the last symbol."""
+    coins = {}
+    for row, (size, _, count, value) in enumerate(book()):
+        if count == 1 and value > 0:
+            coins.setdefault(size + 1, row)
+    if last is not None:
+        out, count = symbols_ending_at(symbols, target - last, None if n is None else n - 1)
+        return out + [(coins[last], True)], count + 1
+    symbols = symbols[:target + 1]                        # (a symbol has a bit at least)
+    by_run = _rows_by_key()[1]
+    top = 12                                              # (coins enough for 80 bits and more)
+    reach = [{0: None}]                                   # reach[c][sum] = the last coin of c coins
+    for c in range(1, top + 1):
+        reach.append({s + l: l for s in reach[-1] for l in coins})
+
+    def change(c, gap):
+        out = []
+        while c:
+            out.append(reach[c][gap])
+            c, gap = c - 1, gap - out[-1]
+        return out
+
+    sizes = [symbol_bits(s) for s in symbols]
+    at = np.concatenate(([0], np.cumsum([b for b, _ in sizes]))).astype(np.int64)
+    got = np.concatenate(([0], np.cumsum([k for _, k in sizes]))).astype(np.int64)
+    for m in range(int(np.searchsorted(at, max(target - 80, 0), "right")) - 1, -1, -1):
+        for c in range(1, top + 1):
+            zeros = 0 if n is None else n - int(got[m]) - c
+            if zeros < 0:
+                break
+            front = []                                    # (as symbols_of writes a zero run)
+            for r in RUNS:
+                front += [(by_run[r], False)] * (zeros // r)
+                zeros %= r
+            gap = target - int(at[m]) - sum(symbol_bits(s)[0] for s in front)
+            if gap in reach[c]:
+                tail = [(coins[l], k % 2 == 1) for k, l in enumerate(change(c, gap))]
+                out = front + list(symbols[:m]) + tail
+                bits, count = (sum(x) for x in zip(*(symbol_bits(s) for s in out)))
+                assert bits == target and (n is None or count == n), (bits, target, count, n)
+                return out, count
+    raise ValueError("no stream of %d bits%s" % (target, "" if n is None else " and %d coefficients" % n))
 
 
 def model_lowpass(data, precision, w, h):
