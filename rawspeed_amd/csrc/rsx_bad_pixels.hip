@@ -36,6 +36,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_bad_pixels.h"
 #include "rsx_bad_pixels_core.h"
 
@@ -218,10 +219,6 @@ struct BpPlan final : DecoderPlan {
   DeviceBuffer d_jobs, d_outs, d_maps, d_mapin;
   uint32_t word_blocks = 0, zero_blocks = 0, mark_blocks = 0, fix_blocks = 0, col_x = 0, col_y = 0;
   bool any_u16 = false, any_f32 = false, have_results = false;
-  ~BpPlan() override {
-    for (DeviceBuffer* b : {&d_jobs, &d_outs, &d_maps, &d_mapin})
-      b->release();
-  }
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override {
     have_results = false;
     BpArgs A{};
@@ -272,16 +269,10 @@ struct BpPlan final : DecoderPlan {
                                         hipMemcpyDeviceToHost, s));
       RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
     }
-    int rc = RSX_OK;
-    for (size_t i = 0; i < n_jobs; ++i) {
-      const int32_t st = h_out[i].flag ? int32_t(RSX_ERR_INVALID_ARG) : int32_t(RSX_OK);
-      if (job_status)
-        job_status[i] = st;
-      if (st)
-        rc = st;
-    }
     have_results = ran;
-    return rc;
+    return fold_jobs(n_jobs, FoldOrder::LAST_FAILING, job_status, [&](size_t i) {
+      return h_out[i].flag ? int(RSX_ERR_INVALID_ARG) : int(RSX_OK);
+    });
   }
   int bad_pixels_result(int job, rsx_bad_pixels_result* out) override {
     if (job < 0 || size_t(job) >= n_jobs || !out || !have_results)
@@ -369,13 +360,11 @@ int plan_create(rsx_ctx* ctx, int n_jobs, const rsx_bad_pixels_job* jobs, bool m
   }
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(JobDev) + 16)) ||
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) ||
       (st = p->d_outs.ensure(p->jobs.size() * sizeof(JobOut) + 16)) ||
       (st = p->d_maps.ensure(size_t(map_words) * 8 + 16)) ||
       (st = p->d_mapin.ensure(size_t(mapin_words) * 8 + 16)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(JobDev),
-                               hipMemcpyHostToDevice));
   for (size_t i = 0; i < p->jobs.size(); ++i)
     if (p->jobs[i].has_map_in && p->jobs[i].active)
       RSX_HIP_CHECK(ctx, hipMemcpy(static_cast<uint64_t*>(p->d_mapin.ptr) + p->jobs[i].mapin_off,

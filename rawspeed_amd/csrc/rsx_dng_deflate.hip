@@ -30,11 +30,11 @@
 #include "rsx_inflate_core.h"
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 
 namespace rsx {
 namespace {
 
-constexpr uint32_t DFL_NONE = 0xFFFFFFFFu;
 constexpr uint64_t DFL_MAX_SCRATCH = uint64_t(1) << 30; // what the LJPEG pipeline accepts
 
 struct DflJobDev {
@@ -225,9 +225,8 @@ __global__ void __launch_bounds__(64) dfl_row_kernel(DflArgs A) {
 struct DflPlan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<DflJobDev> jobs;
-  std::vector<int32_t> host_status;
-  DeviceBuffer d_jobs, d_rows, d_status, d_scratch;
-  std::vector<uint32_t> h_status;
+  JobStatus status; // two words a job: the verdict, the input bytes consumed
+  DeviceBuffer d_jobs, d_rows, d_scratch;
   uint32_t total_rows = 0, live = 0;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
@@ -263,7 +262,7 @@ int dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job*
                             std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<DflPlan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   p->jobs.resize(n_jobs);
   std::vector<DflRowDev> rows;
   uint64_t scratch = 0;
@@ -275,7 +274,7 @@ int dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job*
                                   j.in_bytes, j.img);
     if (st == RSX_OK && j.img_offset % 4 != 0)
       st = RSX_ERR_INVALID_ARG;
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     if (st != RSX_OK)
       continue;
     J.in_off = j.in_offset;
@@ -302,16 +301,9 @@ int dng_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_deflate_job*
   }
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(DflJobDev) + 16)) ||
-      (st = p->d_rows.ensure(rows.size() * sizeof(DflRowDev) + 16)) ||
-      (st = p->d_status.ensure(size_t(n_jobs) * 8 + 16)) || (st = p->d_scratch.ensure(size_t(scratch) + 16)))
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_rows, rows)) ||
+      (st = p->status.init(2)) || (st = p->d_scratch.ensure(size_t(scratch) + 16)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(DflJobDev),
-                               hipMemcpyHostToDevice));
-  if (!rows.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_rows.ptr, rows.data(), rows.size() * sizeof(DflRowDev),
-                                 hipMemcpyHostToDevice));
-  p->h_status.assign(size_t(n_jobs) * 2, DFL_NONE);
   *out = std::move(p);
   return RSX_OK;
 }
@@ -331,8 +323,9 @@ int DflPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* 
   A.scratch = static_cast<uint8_t*>(d_scratch.ptr);
   A.jobs = static_cast<const DflJobDev*>(d_jobs.ptr);
   A.rows = static_cast<const DflRowDev*>(d_rows.ptr);
-  A.status = static_cast<uint32_t*>(d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, jobs.size() * 8, s));
+  A.status = static_cast<uint32_t*>(status.dev.ptr);
+  if (int st = status.reset(ctx, s))
+    return st;
   hipLaunchKernelGGL(dfl_inflate_kernel, dim3(uint32_t(jobs.size())), dim3(64), 0, s, A);
   if (timer)
     timer->mark("dfl_inflate_kernel");
@@ -347,31 +340,24 @@ int DflPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* 
 int DflPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
     std::fill(job_consumed, job_consumed + jobs.size(), 0u);
-  if (ran && live != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    int st = host_status[i];
+  if (ran && live != 0)
+    if (int st = status.fetch(ctx, s))
+      return st;
+  return fold_jobs(jobs.size(), FoldOrder::LAST_FAILING, job_status, [&](size_t i) {
+    int st = status.host[i];
     if (st == RSX_OK && ran) {
       // libz's Z_OK with exactly dstLen bytes; Z_OK with fewer (the reference then reads
       // indeterminate bytes: the CPU gets the tile); everything libz rejects
-      const uint32_t v = h_status[2 * i];
+      const uint32_t v = status.words[2 * i];
       st = v == uint32_t(rsx_inflate::V_OK)      ? RSX_OK
            : v == uint32_t(rsx_inflate::V_SHORT) ? RSX_ERR_UNSUPPORTED
            : v == uint32_t(rsx_inflate::V_FAIL)  ? RSX_ERR_IO
                                                  : RSX_ERR_DEVICE;
       if (job_consumed && v != uint32_t(rsx_inflate::V_FAIL) && st != RSX_ERR_DEVICE)
-        job_consumed[i] = h_status[2 * i + 1];
+        job_consumed[i] = status.words[2 * i + 1];
     }
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+    return st;
+  });
 }
 
 } // namespace

@@ -29,6 +29,7 @@
 #include "rsx_internal.h"
 #include "rsx_jpeg_core.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 
 namespace rsx {
 namespace {
@@ -307,20 +308,10 @@ int dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
     return RSX_ERR_UNSUPPORTED; // (the finish kernel's grid)
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_tiles.ensure(tiles.size() * sizeof(Tile) + 16)) ||
-      (st = p->d_segs.ensure(segs.size() * sizeof(Segment) + 16)) ||
-      (st = p->d_tables.ensure(tables.size() * sizeof(Tables) + 16)) ||
-      (st = p->d_status.ensure(tiles.size() * 4 + 16)) || (st = p->d_planes.ensure(size_t(scratch) + 16)))
+  if ((st = upload(ctx, p->d_tiles, tiles)) || (st = upload(ctx, p->d_segs, segs)) ||
+      (st = upload(ctx, p->d_tables, tables)) || (st = p->d_status.ensure(tiles.size() * 4 + 16)) ||
+      (st = p->d_planes.ensure(size_t(scratch) + 16)))
     return st;
-  if (!tiles.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_tiles.ptr, tiles.data(), tiles.size() * sizeof(Tile),
-                                 hipMemcpyHostToDevice));
-  if (!segs.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_segs.ptr, segs.data(), segs.size() * sizeof(Segment),
-                                 hipMemcpyHostToDevice));
-  if (!tables.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_tables.ptr, tables.data(), tables.size() * sizeof(Tables),
-                                 hipMemcpyHostToDevice));
   p->h_status.assign(tiles.size(), 0u);
   *out = std::move(p);
   return RSX_OK;
@@ -361,14 +352,12 @@ int JpegPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* jo
   const size_t n_jobs = job_host_status.size();
   if (job_consumed)
     std::fill(job_consumed, job_consumed + n_jobs, 0u);
-  if (ran && n_segs != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
+  if (ran && n_segs != 0)
+    if (int st = fetch_words(ctx, s, d_status, 0, h_status.size(), h_status.data()))
+      return st;
   tile_final.assign(n_tiles, RSX_OK);
-  int rc = RSX_OK;
-  for (size_t i = 0; i < n_jobs; ++i) {
+  // a job's tiles fold into RSX_ERR_TILE_ERRORS, or RSX_ERR_DEVICE if one of them says so
+  return fold_jobs(n_jobs, FoldOrder::LAST_FAILING, job_status, [&](size_t i) {
     int st = job_host_status[i];
     for (uint32_t t = job_first[i]; t < job_first[i + 1]; ++t) {
       int ts = windows[i][t - job_first[i]].host_status;
@@ -380,12 +369,8 @@ int JpegPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* jo
       if (ts != RSX_OK)
         st = ts == RSX_ERR_DEVICE ? RSX_ERR_DEVICE : RSX_ERR_TILE_ERRORS;
     }
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+    return st;
+  });
 }
 
 } // namespace

@@ -32,6 +32,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_dng_post.h"
 #include "rsx_dng_post_core.h"
 
@@ -173,10 +174,6 @@ struct DpPlan final : DecoderPlan {
   DeviceBuffer d_jobs, d_ops, d_tables, d_deltas, d_luts, d_pw, d_hits, d_counts;
   uint32_t max_blocks = 0;
   bool any_u16 = false, any_f32 = false, any_bad = false, have_results = false;
-  ~DpPlan() override {
-    for (DeviceBuffer* b : {&d_jobs, &d_ops, &d_tables, &d_deltas, &d_luts, &d_pw, &d_hits, &d_counts})
-      b->release();
-  }
   int run(const void*, void* out_dev, hipStream_t s, KernelTimer* timer) override {
     have_results = false;
     if (max_blocks == 0)
@@ -340,23 +337,12 @@ int dng_post_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_post_job* jobs,
   const std::vector<uint32_t> pw = dither_powers8(max_vpr);
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(JobDev) + 16)) ||
-      (st = p->d_ops.ensure(ops.size() * sizeof(OpDev) + 16)) ||
-      (st = p->d_tables.ensure(tables.size() * 2 + 16)) ||
-      (st = p->d_deltas.ensure(deltas.size() * 4 + 16)) ||
-      (st = p->d_luts.ensure(luts.size() * 4 + 16)) || (st = p->d_pw.ensure(pw.size() * 4 + 16)) ||
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_ops, ops)) ||
+      (st = upload(ctx, p->d_tables, tables)) || (st = upload(ctx, p->d_deltas, deltas)) ||
+      (st = upload(ctx, p->d_luts, luts)) || (st = upload(ctx, p->d_pw, pw)) ||
       (st = p->d_hits.ensure(size_t(hit_entries) * 8 + 16)) ||
       (st = p->d_counts.ensure(p->jobs.size() * sizeof(unsigned long long) + 16)))
     return st;
-  auto up = [&](DeviceBuffer& b, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpy(b.ptr, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-  };
-  RSX_HIP_CHECK(ctx, up(p->d_jobs, p->jobs.data(), p->jobs.size() * sizeof(JobDev)));
-  RSX_HIP_CHECK(ctx, up(p->d_ops, ops.data(), ops.size() * sizeof(OpDev)));
-  RSX_HIP_CHECK(ctx, up(p->d_tables, tables.data(), tables.size() * 2));
-  RSX_HIP_CHECK(ctx, up(p->d_deltas, deltas.data(), deltas.size() * 4));
-  RSX_HIP_CHECK(ctx, up(p->d_luts, luts.data(), luts.size() * 4));
-  RSX_HIP_CHECK(ctx, up(p->d_pw, pw.data(), pw.size() * 4));
   *out = std::move(p);
   return RSX_OK;
 }

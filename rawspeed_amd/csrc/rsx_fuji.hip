@@ -26,6 +26,7 @@
 #include "rsx_fuji.h"
 #include "rsx_fuji_core.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 
 namespace rsx {
 
@@ -39,7 +40,6 @@ constexpr int FJ_CHUNK = 32; // iterations of a pass between two looks at the wi
 // a chunk's worst case without an overlong zero run: 4 samples an iteration, each at most
 // 47 zeros, a 1 and 16 bits
 constexpr int FJ_CHUNK_WORDS = FJ_CHUNK * 4 * 2 + 2;
-constexpr uint32_t FJ_NONE = 0xFFFFFFFFu;
 
 struct FjStripDev {
   uint64_t in_off;  // the strip's bytes, from the run's input base
@@ -230,13 +230,12 @@ __global__ void __launch_bounds__(FJ_THREADS) fuji_strip_kernel(FjArgs A) {
 namespace {
 struct FujiPlan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
-  std::vector<int32_t> host_status;           // validation result per job
+  JobStatus status;
   std::vector<uint32_t> strip_base, n_strips; // per job, into the plan's strips
-  DeviceBuffer d_strips, d_strip_status, d_status;
-  std::vector<uint32_t> h_status, h_strip_status;
+  DeviceBuffer d_strips, d_strip_status;
+  std::vector<uint32_t> h_strip_status;
   uint32_t total_strips = 0;
   bool launched = false;
-  ~FujiPlan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
   int row_status(hipStream_t s, int job, int32_t* statuses) override;
@@ -247,7 +246,7 @@ int fuji_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fuji_job* jobs,
                      std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<FujiPlan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   p->strip_base.assign(n_jobs, 0u);
   p->n_strips.assign(n_jobs, 0u);
   std::vector<FjStripDev> strips;
@@ -258,7 +257,7 @@ int fuji_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fuji_job* jobs,
       st = check_strips(j.desc, j.in_bytes);
     if (st == RSX_OK && (j.img_offset % 2 != 0 || j.img.pitch_bytes % 2 != 0))
       st = RSX_ERR_INVALID_ARG;
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     p->strip_base[i] = uint32_t(strips.size());
     if (st != RSX_OK)
       continue;
@@ -282,21 +281,11 @@ int fuji_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fuji_job* jobs,
   p->total_strips = uint32_t(strips.size());
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_strips.ensure(strips.size() * sizeof(FjStripDev) + 16)) ||
-      (st = p->d_strip_status.ensure(strips.size() * 4 + 16)) ||
-      (st = p->d_status.ensure(size_t(n_jobs) * 4 + 16)))
+  if ((st = upload(ctx, p->d_strips, strips)) ||
+      (st = p->d_strip_status.ensure(strips.size() * 4 + 16)) || (st = p->status.init()))
     return st;
-  if (!strips.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_strips.ptr, strips.data(), strips.size() * sizeof(FjStripDev),
-                                 hipMemcpyHostToDevice));
-  p->h_status.assign(n_jobs, FJ_NONE);
   *out = std::move(p);
   return RSX_OK;
-}
-
-FujiPlan::~FujiPlan() {
-  for (DeviceBuffer* b : {&d_strips, &d_strip_status, &d_status})
-    b->release();
 }
 
 int FujiPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -309,8 +298,9 @@ int FujiPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer*
   A.out_base = static_cast<uint8_t*>(out_dev);
   A.strips = static_cast<const FjStripDev*>(d_strips.ptr);
   A.strip_status = static_cast<uint32_t*>(d_strip_status.ptr);
-  A.job_status = static_cast<uint32_t*>(d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, host_status.size() * 4, s));
+  A.job_status = static_cast<uint32_t*>(status.dev.ptr);
+  if (int st = status.reset(ctx, s))
+    return st;
   hipLaunchKernelGGL(fuji_strip_kernel, dim3(total_strips), dim3(FJ_THREADS), 0, s, A);
   if (timer)
     timer->mark("fuji_strip_kernel");
@@ -321,37 +311,15 @@ int FujiPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer*
 
 int FujiPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
-    std::fill(job_consumed, job_consumed + host_status.size(), 0u);
-  if (ran && total_strips != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < host_status.size(); ++i) {
-    int st = host_status[i];
-    if (st == RSX_OK && ran && h_status[i] != FJ_NONE)
-      st = int(h_status[i] & 0xFFu);
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+    std::fill(job_consumed, job_consumed + status.host.size(), 0u);
+  return status.fold(ctx, s, ran && total_strips != 0, 0xFFu, FoldOrder::LAST_FAILING, job_status);
 }
 
 int FujiPlan::row_status(hipStream_t s, int job, int32_t* statuses) {
-  if (job < 0 || size_t(job) >= host_status.size() || !launched || n_strips[job] == 0 || !statuses)
+  if (job < 0 || size_t(job) >= status.host.size() || !launched || n_strips[job] == 0 || !statuses)
     return RSX_ERR_INVALID_ARG;
-  const uint32_t n = n_strips[job];
-  h_strip_status.resize(n);
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_strip_status.data(),
-                                    static_cast<const uint32_t*>(d_strip_status.ptr) + strip_base[job],
-                                    size_t(n) * 4, hipMemcpyDeviceToHost, s));
-  RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  for (uint32_t r = 0; r < n; ++r)
-    statuses[r] = int32_t(h_strip_status[r]);
-  return RSX_OK;
+  return fetch_words(ctx, s, d_strip_status, strip_base[job], n_strips[job], h_strip_status,
+                     statuses);
 }
 
 } // namespace rsx

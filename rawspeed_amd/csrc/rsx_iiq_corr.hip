@@ -35,6 +35,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_iiq_corr.h"
 #include "rsx_iiq_corr_core.h"
 
@@ -123,10 +124,6 @@ struct IqPlan final : DecoderPlan {
   size_t n_jobs = 0, n_ops = 0;
   DeviceBuffer d_jobs, d_ops, d_tables, d_curves, d_payloads;
   uint32_t max_blocks = 0, max_row_blocks = 0, max_col_blocks = 0;
-  ~IqPlan() override {
-    for (DeviceBuffer* b : {&d_jobs, &d_ops, &d_tables, &d_curves, &d_payloads})
-      b->release();
-  }
   IqArgs args(void* out_dev) const {
     IqArgs A{};
     A.out_base = static_cast<uint8_t*>(out_dev);
@@ -266,17 +263,11 @@ int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job*
     return RSX_ERR_UNSUPPORTED; // (a grid's second dimension)
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(jd.size() * sizeof(JobDev) + 16)) ||
-      (st = p->d_ops.ensure(ops.size() * sizeof(OpDev) + 16)) ||
+  if ((st = upload(ctx, p->d_jobs, jd)) || (st = upload(ctx, p->d_ops, ops)) ||
       (st = p->d_tables.ensure(size_t(table_floats) * 4 + 16)) ||
       (st = p->d_curves.ensure(curves.size() * 4 * 65536 * 2 + 16)) ||
-      (st = p->d_payloads.ensure(payloads.size() + 16)))
+      (st = upload(ctx, p->d_payloads, payloads)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, jd.data(), jd.size() * sizeof(JobDev), hipMemcpyHostToDevice));
-  if (!ops.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_ops.ptr, ops.data(), ops.size() * sizeof(OpDev), hipMemcpyHostToDevice));
-  if (!payloads.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_payloads.ptr, payloads.data(), payloads.size(), hipMemcpyHostToDevice));
   for (size_t k = 0; k < curves.size(); ++k)
     RSX_HIP_CHECK(ctx, hipMemcpy(static_cast<uint16_t*>(p->d_curves.ptr) + k * 4 * 65536, curves[k],
                                  size_t(4) * 65536 * 2, hipMemcpyHostToDevice));

@@ -169,9 +169,10 @@ struct DeviceBuffer {
   void release();
 };
 
-// The device plan of a decoder (the LJPEG family, SamsungV2, Phase One, ARW2): what a
-// rsx_plan of such a decoder runs, whichever decoder made it.  The destructor releases the
-// plan's device memory.
+// The device plan of a decoder or of a post-decode stage (every plan but the unpack and sRaw
+// ones of rsx_api.hip): what a rsx_plan of it runs, whichever decoder made it.  A plan's device
+// memory goes back with its DeviceBuffer members; rsx_plan_host.h has the uploads, the status
+// fetches and the per-job fold that the plans outside the LJPEG family share.
 struct KernelTimer; // rsx_ljpeg_dev.h: an event after every launch of a timed run
 struct LJpegPlan;   // rsx_ljpeg.hip
 struct DecoderPlan {

@@ -43,6 +43,7 @@
 #include "rsx_dither_dev.h"
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_nikon_snef.h"
 
 #pragma clang fp contract(off)
@@ -274,7 +275,6 @@ struct NikonSnefPlan final : DecoderPlan {
   std::vector<uint32_t> h_tables;   // device form of every job's table
   DeviceBuffer d_jobs, d_items, d_tables, d_pow;
   uint32_t n_items = 0;
-  ~NikonSnefPlan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
 };
@@ -344,27 +344,12 @@ int nikon_snef_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_nikon_snef_job* j
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const std::vector<uint32_t> pw = dither_powers(6u * SN_RUN, SN_MAX_RUNS); // 15700^(24 run) mod m
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(SnJobDev) + 16)) ||
-      (st = p->d_items.ensure(items.size() * sizeof(SnItem) + 16)) ||
-      (st = p->d_tables.ensure(p->h_tables.size() * 4 + 16)) ||
-      (st = p->d_pow.ensure(pw.size() * 4)))
+  // (no pad behind d_pow: the kernel reads it one word at an index, pow24[run])
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_items, items)) ||
+      (st = upload(ctx, p->d_tables, p->h_tables)) || (st = upload(ctx, p->d_pow, pw, 0)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(SnJobDev),
-                               hipMemcpyHostToDevice));
-  if (!items.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_items.ptr, items.data(), items.size() * sizeof(SnItem),
-                                 hipMemcpyHostToDevice));
-  if (!p->h_tables.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_tables.ptr, p->h_tables.data(), p->h_tables.size() * 4,
-                                 hipMemcpyHostToDevice));
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_pow.ptr, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
   *out = std::move(p);
   return RSX_OK;
-}
-
-NikonSnefPlan::~NikonSnefPlan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_items, &d_tables, &d_pow})
-    b->release();
 }
 
 int nikon_snef_plan_set_table(DecoderPlan* plan, int job, const rsx_nikon_snef_desc* desc, hipStream_t s) {
@@ -406,14 +391,8 @@ int NikonSnefPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_
     std::copy(consumed.begin(), consumed.end(), job_consumed);
   if (ran && n_items != 0)
     RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    if (job_status)
-      job_status[i] = host_status[i];
-    if (host_status[i] != RSX_OK)
-      rc = host_status[i];
-  }
-  return rc;
+  return fold_jobs(jobs.size(), FoldOrder::LAST_FAILING, job_status,
+                   [&](size_t i) { return int(host_status[i]); });
 }
 
 } // namespace rsx

@@ -35,6 +35,7 @@
 #include "rsx_olympus.h"
 #include "rsx_olympus_core.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 
 namespace rsx {
 
@@ -48,7 +49,6 @@ constexpr int OL_WIN_WORDS = 64 * OL_WIN_REGS; // words of the stream in the win
 constexpr int OL_BATCH = 64;                   // symbols between two looks at the window
 // words a batch loads at most: 64 symbols of 31 bits, and one for the cache's level
 constexpr int OL_BATCH_WORDS = (OL_BATCH * 31 + 31) / 32 + 2;
-constexpr uint32_t OL_NONE = 0xFFFFFFFFu;
 
 constexpr int OL_BAND = 64;                // plane rows in flight
 constexpr int OL_TILE = 64;                // plane columns of a tile
@@ -68,7 +68,7 @@ struct OlArgs {
   const uint8_t* in_base;
   uint8_t* out_base;
   const OlJobDev* jobs;
-  uint32_t* job_status; // per job of the plan: OL_NONE, or the walk's status
+  uint32_t* job_status; // per job of the plan: STATUS_NONE, or the walk's status
 };
 
 // bytes 4 k .. 4 k + 3 of the stream as a big-endian word; bytes behind the stream read as zero
@@ -257,12 +257,10 @@ __global__ void __launch_bounds__(OL_THREADS) olympus_recon_kernel(OlArgs A) {
 namespace {
 struct OlympusPlan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
-  std::vector<int32_t> host_status; // validation result per job
-  DeviceBuffer d_jobs, d_status;
-  std::vector<uint32_t> h_status;
+  JobStatus status;
+  DeviceBuffer d_jobs;
   uint32_t n_dev = 0; // jobs that go to the device
-  bool launched = false, fetched = false;
-  ~OlympusPlan() override;
+  bool launched = false;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
   int row_status(hipStream_t s, int job, int32_t* statuses) override;
@@ -273,14 +271,14 @@ int olympus_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_olympus_job* jobs,
                         std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<OlympusPlan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   std::vector<OlJobDev> dev;
   for (int i = 0; i < n_jobs; ++i) {
     const rsx_olympus_job& j = jobs[i];
     int st = validate(j.in_bytes, &j.img);
     if (st == RSX_OK && (j.img_offset % 2 != 0 || j.img.pitch_bytes % 2 != 0))
       st = RSX_ERR_INVALID_ARG;
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     if (st != RSX_OK)
       continue;
     OlJobDev D;
@@ -297,24 +295,13 @@ int olympus_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_olympus_job* jobs,
   p->n_dev = uint32_t(dev.size());
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(dev.size() * sizeof(OlJobDev) + 16)) ||
-      (st = p->d_status.ensure(size_t(n_jobs) * 4 + 16)))
+  if ((st = upload(ctx, p->d_jobs, dev)) || (st = p->status.init()))
     return st;
-  if (!dev.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, dev.data(), dev.size() * sizeof(OlJobDev),
-                                 hipMemcpyHostToDevice));
-  p->h_status.assign(n_jobs, OL_NONE);
   *out = std::move(p);
   return RSX_OK;
 }
 
-OlympusPlan::~OlympusPlan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_status})
-    b->release();
-}
-
 int OlympusPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
-  fetched = false;
   if (n_dev == 0)
     return RSX_OK; // (every job was rejected by the host)
   if (timer)
@@ -323,8 +310,9 @@ int OlympusPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTim
   A.in_base = static_cast<const uint8_t*>(in_dev);
   A.out_base = static_cast<uint8_t*>(out_dev);
   A.jobs = static_cast<const OlJobDev*>(d_jobs.ptr);
-  A.job_status = static_cast<uint32_t*>(d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, host_status.size() * 4, s));
+  A.job_status = static_cast<uint32_t*>(status.dev.ptr);
+  if (int st = status.reset(ctx, s))
+    return st;
   hipLaunchKernelGGL(olympus_parse_kernel, dim3(n_dev), dim3(OL_THREADS), 0, s, A);
   if (timer)
     timer->mark("olympus_parse_kernel");
@@ -339,35 +327,19 @@ int OlympusPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTim
 // The status of the lowest-numbered failing job, or RSX_OK.
 int OlympusPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
-    std::fill(job_consumed, job_consumed + host_status.size(), 0u);
-  if (ran && n_dev != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-    fetched = true;
-  }
-  int rc = RSX_OK;
-  for (size_t i = host_status.size(); i-- > 0;) {
-    int st = host_status[i];
-    if (st == RSX_OK && ran && h_status[i] != OL_NONE)
-      st = int(h_status[i]);
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+    std::fill(job_consumed, job_consumed + status.host.size(), 0u);
+  return status.fold(ctx, s, ran && n_dev != 0, ~0u, FoldOrder::LOWEST_FAILING, job_status);
 }
 
 // One status a job: what results() gave for it.
 int OlympusPlan::row_status(hipStream_t, int job, int32_t* statuses) {
-  if (job < 0 || size_t(job) >= host_status.size() || !statuses)
+  if (job < 0 || size_t(job) >= status.host.size() || !statuses)
     return RSX_ERR_INVALID_ARG;
-  int st = host_status[job];
+  int st = status.host[job];
   if (st == RSX_OK) {
-    if (!launched || !fetched || h_status[job] == OL_NONE)
+    if (!launched || !status.fetched || status.words[job] == STATUS_NONE)
       return RSX_ERR_INVALID_ARG; // (before a run and its results)
-    st = int(h_status[job]);
+    st = int(status.words[job]);
   }
   statuses[0] = st;
   return RSX_OK;

@@ -41,6 +41,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_panasonic.h"
 #include "rsx_panasonic_dev.h"
 
@@ -239,7 +240,6 @@ struct PanasonicPlan final : DecoderPlan {
   std::vector<uint32_t> consumed;   // input bytes a job takes (peekStream)
   DeviceBuffer d_jobs, d_items;
   uint32_t first[PN_LAYOUTS + 1] = {}; // the items of layout l: [first[l], first[l + 1])
-  ~PanasonicPlan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
 };
@@ -323,21 +323,10 @@ int panasonic_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_job* job
   p->first[PN_LAYOUTS] = uint32_t(all.size());
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(PnJobDev) + 16)) ||
-      (st = p->d_items.ensure(all.size() * sizeof(PnItem) + 16)))
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_items, all)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(PnJobDev),
-                               hipMemcpyHostToDevice));
-  if (!all.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_items.ptr, all.data(), all.size() * sizeof(PnItem),
-                                 hipMemcpyHostToDevice));
   *out = std::move(p);
   return RSX_OK;
-}
-
-PanasonicPlan::~PanasonicPlan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_items})
-    b->release();
 }
 
 int PanasonicPlan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -368,14 +357,8 @@ int PanasonicPlan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_
     std::copy(consumed.begin(), consumed.end(), job_consumed);
   if (ran && first[PN_LAYOUTS] != 0)
     RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    if (job_status)
-      job_status[i] = host_status[i];
-    if (host_status[i] != RSX_OK)
-      rc = host_status[i];
-  }
-  return rc;
+  return fold_jobs(jobs.size(), FoldOrder::LAST_FAILING, job_status,
+                   [&](size_t i) { return int(host_status[i]); });
 }
 
 } // namespace rsx

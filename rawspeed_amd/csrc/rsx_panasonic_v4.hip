@@ -42,6 +42,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_panasonic_dev.h"
 #include "rsx_panasonic_v4.h"
 
@@ -250,7 +251,6 @@ struct P4Plan final : DecoderPlan {
   std::vector<std::vector<uint32_t>> h_lists; // ... and the jobs' sorted lists
   uint32_t n_items = 0;
   bool have_lists = false;
-  ~P4Plan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
   int bad_pixels(int job, uint32_t* out, uint32_t cap, uint64_t* n_bad) override;
@@ -329,23 +329,12 @@ int panasonic_v4_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_panasonic_v4_jo
   p->n_items = uint32_t(items.size());
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(P4JobDev) + 16)) ||
-      (st = p->d_items.ensure(items.size() * sizeof(P4Item) + 16)) ||
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_items, items)) ||
       (st = p->d_counts.ensure(size_t(n_jobs) * 4 + 16)) ||
       (st = p->d_lists.ensure(size_t(entries) * 4 + 16)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(P4JobDev),
-                               hipMemcpyHostToDevice));
-  if (!items.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_items.ptr, items.data(), items.size() * sizeof(P4Item),
-                                 hipMemcpyHostToDevice));
   *out = std::move(p);
   return RSX_OK;
-}
-
-P4Plan::~P4Plan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_items, &d_counts, &d_lists})
-    b->release();
 }
 
 int P4Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -377,9 +366,8 @@ int P4Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_
   for (std::vector<uint32_t>& l : h_lists)
     l.clear();
   if (ran && n_items != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_counts.data(), d_counts.ptr, h_counts.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    if (int st = fetch_words(ctx, s, d_counts, 0, h_counts.size(), h_counts.data()))
+      return st;
     // the lists that fit, in the reference's single-thread order
     for (size_t i = 0; i < jobs.size(); ++i) {
       if (host_status[i] != RSX_OK || h_counts[i] == 0 || h_counts[i] > jobs[i].bad_cap)
@@ -394,17 +382,11 @@ int P4Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_
       std::sort(l.begin(), l.end());
     have_lists = true;
   }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    int st = host_status[i];
-    if (st == RSX_OK && h_counts[i] > jobs[i].bad_cap)
-      st = RSX_ERR_UNSUPPORTED; // (the image is complete; the list did not fit)
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+  return fold_jobs(jobs.size(), FoldOrder::LAST_FAILING, job_status, [&](size_t i) {
+    // (the image is complete; the list did not fit)
+    return host_status[i] == RSX_OK && h_counts[i] > jobs[i].bad_cap ? int(RSX_ERR_UNSUPPORTED)
+                                                                     : int(host_status[i]);
+  });
 }
 
 int P4Plan::bad_pixels(int job, uint32_t* out, uint32_t cap, uint64_t* n_bad) {

@@ -36,6 +36,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_phase_one.h"
 
 namespace rsx {
@@ -44,7 +45,6 @@ namespace {
 
 constexpr int P1_THREADS = 192; // lanes of a row: 64 pixels each (11976 / 64 -> 188)
 constexpr int P1_WAVES = P1_THREADS / 64;
-constexpr uint32_t P1_NONE = 0xFFFFFFFFu;
 constexpr int32_t P1_MAX_W = 11976, P1_MAX_H = 8854; // PhaseOneDecompressor.cpp:52-56
 // len = {8, 7, 6, 9, 11, 10, 5, 12, 14, 13}[2 (j - 1) + b] (:93-94), a nibble each
 constexpr uint64_t P1_LENGTHS = 0xDEC5AB9678ull;
@@ -73,7 +73,7 @@ struct P1Args {
   const P1RowDev* rows;
   const P1JobDev* jobs;
   uint32_t* row_status; // [row of the plan]: rsx_status
-  uint32_t* job_status; // [job]: first failing row << 8 | status, P1_NONE = fine
+  uint32_t* job_status; // [job]: first failing row << 8 | status, STATUS_NONE = fine
 };
 
 // The most bits a row of `width` pixels can read: 12 header bits + 8 x 16 per group, 16 per
@@ -298,13 +298,12 @@ namespace {
 struct P1Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<P1JobDev> jobs;
-  std::vector<int32_t> host_status; // validation result per job
-  std::vector<uint32_t> job_rows;   // rows of a job (0 when rejected)
-  DeviceBuffer d_jobs, d_rows, d_row_status, d_status;
-  std::vector<uint32_t> h_status, h_row_status;
+  JobStatus status;
+  std::vector<uint32_t> job_rows; // rows of a job (0 when rejected)
+  DeviceBuffer d_jobs, d_rows, d_row_status;
+  std::vector<uint32_t> h_row_status;
   uint32_t total_rows = 0, max_words = 0;
   bool launched = false;
-  ~P1Plan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
   int row_status(hipStream_t s, int job, int32_t* statuses) override;
@@ -341,7 +340,7 @@ int phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* job
                           std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<P1Plan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   p->job_rows.assign(n_jobs, 0);
   p->jobs.resize(n_jobs);
   std::vector<P1RowDev> rows;
@@ -354,7 +353,7 @@ int phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* job
       st = RSX_ERR_INVALID_ARG;
     if (st == RSX_OK && j.in_bytes >= (1ull << 32))
       st = RSX_ERR_UNSUPPORTED; // (strip sizes are 32-bit on the device)
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     if (st != RSX_OK)
       continue;
     J.img_offset = j.img_offset;
@@ -374,24 +373,11 @@ int phase_one_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_phase_one_job* job
   }
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(P1JobDev) + 16)) ||
-      (st = p->d_rows.ensure(rows.size() * sizeof(P1RowDev) + 16)) ||
-      (st = p->d_row_status.ensure(size_t(p->total_rows) * 4 + 16)) ||
-      (st = p->d_status.ensure(size_t(n_jobs) * 4 + 16)))
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_rows, rows)) ||
+      (st = p->d_row_status.ensure(size_t(p->total_rows) * 4 + 16)) || (st = p->status.init()))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(P1JobDev),
-                               hipMemcpyHostToDevice));
-  if (!rows.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_rows.ptr, rows.data(), rows.size() * sizeof(P1RowDev),
-                                 hipMemcpyHostToDevice));
-  p->h_status.assign(n_jobs, P1_NONE);
   *out = std::move(p);
   return RSX_OK;
-}
-
-P1Plan::~P1Plan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_rows, &d_row_status, &d_status})
-    b->release();
 }
 
 int P1Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -405,8 +391,9 @@ int P1Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* t
   A.rows = static_cast<const P1RowDev*>(d_rows.ptr);
   A.jobs = static_cast<const P1JobDev*>(d_jobs.ptr);
   A.row_status = static_cast<uint32_t*>(d_row_status.ptr);
-  A.job_status = static_cast<uint32_t*>(d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, jobs.size() * 4, s));
+  A.job_status = static_cast<uint32_t*>(status.dev.ptr);
+  if (int st = status.reset(ctx, s))
+    return st;
   const size_t lds = (size_t(P1_LDS_HEAD) + max_words) * 4;
   hipLaunchKernelGGL(p1_row_kernel, dim3(total_rows), dim3(P1_THREADS), lds, s, A);
   if (timer)
@@ -419,36 +406,13 @@ int P1Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* t
 int P1Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
     std::fill(job_consumed, job_consumed + jobs.size(), 0u);
-  if (ran && total_rows != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    int st = host_status[i];
-    if (st == RSX_OK && ran && h_status[i] != P1_NONE)
-      st = int(h_status[i] & 0xFFu);
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+  return status.fold(ctx, s, ran && total_rows != 0, 0xFFu, FoldOrder::LAST_FAILING, job_status);
 }
 
 int P1Plan::row_status(hipStream_t s, int job, int32_t* statuses) {
   if (job < 0 || size_t(job) >= jobs.size() || !launched || job_rows[job] == 0)
     return RSX_ERR_INVALID_ARG;
-  const uint32_t n = job_rows[job];
-  h_row_status.resize(n);
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_row_status.data(),
-                                    static_cast<const uint32_t*>(d_row_status.ptr) + jobs[job].row_base,
-                                    size_t(n) * 4, hipMemcpyDeviceToHost, s));
-  RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  for (uint32_t r = 0; r < n; ++r)
-    statuses[r] = int32_t(h_row_status[r]);
-  return RSX_OK;
+  return fetch_words(ctx, s, d_row_status, jobs[job].row_base, job_rows[job], h_row_status, statuses);
 }
 
 } // namespace rsx

@@ -48,6 +48,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_samsung_v0.h"
 
 namespace rsx {
@@ -60,7 +61,6 @@ constexpr int SV0_THREADS = 384; // reconstruction: one lane per block of 16 col
 constexpr int SV0_PARSE_THREADS = 192;
 constexpr int SV0_PARSE_WAVES = SV0_PARSE_THREADS / 64;
 constexpr int SV0_PASSES = SV0_THREADS / SV0_PARSE_THREADS;
-constexpr uint32_t SV0_NONE = 0xFFFFFFFFu;
 constexpr uint32_t SV0_UP = 0xFFFFu; // root code of a dir = 1 block
 constexpr int32_t SV0_MIN_W = 16, SV0_MAX_W = 5546, SV0_MAX_H = 3714; // SamsungV0Decompressor.cpp:54
 constexpr uint32_t SV0_BLOCK_BITS = 281; // 9 + 4 x 4 + 16 x 16
@@ -101,7 +101,7 @@ struct Sv0Args {
   uint16_t* local;      // [block of the plan][16]
   uint32_t* codes;      // [block of the plan]
   uint32_t* row_status; // [row of the plan]: rsx_status
-  uint32_t* job_status; // [job]: first failing row << 8 | status, SV0_NONE = fine
+  uint32_t* job_status; // [job]: first failing row << 8 | status, STATUS_NONE = fine
 };
 
 __host__ __device__ inline uint32_t sv0_row_words(uint32_t nblk) {
@@ -584,13 +584,12 @@ namespace {
 struct Sv0Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<Sv0JobDev> jobs;
-  std::vector<int32_t> host_status; // validation result per job
-  DeviceBuffer d_jobs, d_rows, d_row_status, d_status, d_local, d_codes;
-  std::vector<uint32_t> h_status, h_row_status;
+  JobStatus status;
+  DeviceBuffer d_jobs, d_rows, d_row_status, d_local, d_codes;
+  std::vector<uint32_t> h_row_status;
   uint32_t total_rows = 0, max_words = 0, max_nblk = 0;
   uint64_t total_blocks = 0;
   bool launched = false;
-  ~Sv0Plan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
   int row_status(hipStream_t s, int job, int32_t* statuses) override;
@@ -630,7 +629,7 @@ int samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_job* j
                            std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<Sv0Plan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   p->jobs.resize(n_jobs);
   std::vector<Sv0RowDev> rows;
   for (int i = 0; i < n_jobs; ++i) {
@@ -640,7 +639,7 @@ int samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_job* j
     int st = samsung_v0_validate(j.row_offsets, j.n_offsets, size_t(j.in_bytes), j.img);
     if (st == RSX_OK && (j.img_offset % 2 != 0 || j.img.pitch_bytes % 2 != 0))
       st = RSX_ERR_INVALID_ARG;
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     if (st != RSX_OK)
       continue;
     J.img_offset = j.img_offset;
@@ -663,26 +662,13 @@ int samsung_v0_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v0_job* j
   }
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(Sv0JobDev) + 16)) ||
-      (st = p->d_rows.ensure(rows.size() * sizeof(Sv0RowDev) + 16)) ||
-      (st = p->d_row_status.ensure(size_t(p->total_rows) * 4 + 16)) ||
-      (st = p->d_status.ensure(size_t(n_jobs) * 4 + 16)) ||
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_rows, rows)) ||
+      (st = p->d_row_status.ensure(size_t(p->total_rows) * 4 + 16)) || (st = p->status.init()) ||
       (st = p->d_local.ensure(size_t(p->total_blocks) * 32 + 16)) ||
       (st = p->d_codes.ensure(size_t(p->total_blocks) * 4 + 16)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(Sv0JobDev),
-                               hipMemcpyHostToDevice));
-  if (!rows.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_rows.ptr, rows.data(), rows.size() * sizeof(Sv0RowDev),
-                                 hipMemcpyHostToDevice));
-  p->h_status.assign(n_jobs, SV0_NONE);
   *out = std::move(p);
   return RSX_OK;
-}
-
-Sv0Plan::~Sv0Plan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_rows, &d_row_status, &d_status, &d_local, &d_codes})
-    b->release();
 }
 
 int Sv0Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -698,8 +684,9 @@ int Sv0Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* 
   A.local = static_cast<uint16_t*>(d_local.ptr);
   A.codes = static_cast<uint32_t*>(d_codes.ptr);
   A.row_status = static_cast<uint32_t*>(d_row_status.ptr);
-  A.job_status = static_cast<uint32_t*>(d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, jobs.size() * 4, s));
+  A.job_status = static_cast<uint32_t*>(status.dev.ptr);
+  if (int st = status.reset(ctx, s))
+    return st;
   const size_t lds = (size_t(SV0_LDS_HEAD) + max_words) * 4;
   hipLaunchKernelGGL(sv0_parse_kernel, dim3(total_rows), dim3(SV0_PARSE_THREADS), lds, s, A);
   if (timer)
@@ -717,36 +704,14 @@ int Sv0Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* 
 int Sv0Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
     std::fill(job_consumed, job_consumed + jobs.size(), 0u);
-  if (ran && total_rows != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    int st = host_status[i];
-    if (st == RSX_OK && ran && h_status[i] != SV0_NONE)
-      st = int(h_status[i] & 0xFFu);
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+  return status.fold(ctx, s, ran && total_rows != 0, 0xFFu, FoldOrder::LAST_FAILING, job_status);
 }
 
 int Sv0Plan::row_status(hipStream_t s, int job, int32_t* statuses) {
   if (job < 0 || size_t(job) >= jobs.size() || !launched || jobs[job].height == 0)
     return RSX_ERR_INVALID_ARG;
-  const uint32_t n = jobs[job].height;
-  h_row_status.resize(n);
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_row_status.data(),
-                                    static_cast<const uint32_t*>(d_row_status.ptr) + jobs[job].row_base,
-                                    size_t(n) * 4, hipMemcpyDeviceToHost, s));
-  RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  for (uint32_t r = 0; r < n; ++r)
-    statuses[r] = int32_t(h_row_status[r]);
-  return RSX_OK;
+  return fetch_words(ctx, s, d_row_status, jobs[job].row_base, jobs[job].height, h_row_status,
+                     statuses);
 }
 
 } // namespace rsx

@@ -47,6 +47,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_samsung_v2.h"
 
 namespace rsx {
@@ -665,12 +666,10 @@ namespace {
 struct Sv2Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<Sv2JobDev> jobs;
-  std::vector<int32_t> host_status; // validation result per job
-  DeviceBuffer d_jobs, d_next, d_ja, d_jb, d_row_start, d_row_status, d_hdr, d_dq, d_diffs, d_status;
-  std::vector<uint32_t> h_status;
+  JobStatus status;
+  DeviceBuffer d_jobs, d_next, d_ja, d_jb, d_row_start, d_row_status, d_hdr, d_dq, d_diffs;
   uint32_t max_bounds = 0, max_rows = 0, max_blocks = 0;
   bool aligned8 = true; // every job's image rows start at multiples of 8 bytes
-  ~Sv2Plan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
 };
@@ -697,7 +696,7 @@ int samsung_v2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v2_job* j
                            std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<Sv2Plan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   p->jobs.resize(n_jobs);
   uint64_t bounds = 0, rows = 0, blocks = 0, px = 0;
   for (int i = 0; i < n_jobs; ++i) {
@@ -710,7 +709,7 @@ int samsung_v2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v2_job* j
       st = RSX_ERR_INVALID_ARG;
     if (st == RSX_OK && j.in_bytes >= (1ull << 32) - 64)
       st = RSX_ERR_UNSUPPORTED;
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     if (st != RSX_OK)
       continue;
     J.valid = 1;
@@ -743,23 +742,16 @@ int samsung_v2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_samsung_v2_job* j
   }
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(Sv2JobDev))) ||
+  // (d_jobs: exactly its entries, no pad behind them)
+  if ((st = upload(ctx, p->d_jobs, p->jobs, 0)) ||
       (st = p->d_next.ensure(bounds * 4 + 16)) || (st = p->d_ja.ensure(bounds * 4 + 16)) ||
       (st = p->d_jb.ensure(bounds * 4 + 16)) || (st = p->d_row_start.ensure(rows * 4 + 16)) ||
-      (st = p->d_row_status.ensure(rows * 4 + 16)) || (st = p->d_hdr.ensure(blocks * 4 + 16)) || (st = p->d_dq.ensure(blocks * 4 + 16)) ||
-      (st = p->d_diffs.ensure(px * 2 + 16)) || (st = p->d_status.ensure(size_t(n_jobs) * 4 + 16)))
+      (st = p->d_row_status.ensure(rows * 4 + 16)) || (st = p->d_hdr.ensure(blocks * 4 + 16)) ||
+      (st = p->d_dq.ensure(blocks * 4 + 16)) || (st = p->d_diffs.ensure(px * 2 + 16)) ||
+      (st = p->status.init()))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(Sv2JobDev),
-                               hipMemcpyHostToDevice));
-  p->h_status.assign(n_jobs, SV2_NONE);
   *out = std::move(p);
   return RSX_OK;
-}
-
-Sv2Plan::~Sv2Plan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_next, &d_ja, &d_jb, &d_row_start, &d_row_status, &d_hdr,
-                          &d_dq, &d_diffs, &d_status})
-    b->release();
 }
 
 int Sv2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -790,13 +782,14 @@ int Sv2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* 
   A.hdr = static_cast<uint32_t*>(d_hdr.ptr);
   A.dq = static_cast<uint32_t*>(d_dq.ptr);
   A.diffs = static_cast<int16_t*>(d_diffs.ptr);
-  A.job_status = static_cast<uint32_t*>(d_status.ptr);
+  A.job_status = static_cast<uint32_t*>(status.dev.ptr);
   A.n_jobs = n;
   auto mark = [&](const char* name) {
     if (timer)
       timer->mark(name);
   };
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, size_t(n) * 4, s));
+  if (int st = status.reset(ctx, s))
+    return st;
   const dim3 gb((max_bounds + 255) / 256, n);
   hipLaunchKernelGGL(sv2_spec_kernel, gb, dim3(256), 0, s, A);
   mark("sv2_spec_kernel");
@@ -830,22 +823,15 @@ int Sv2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* 
 int Sv2Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
     std::fill(job_consumed, job_consumed + jobs.size(), 0u);
-  if (ran && max_rows != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    int st = host_status[i];
-    if (st == RSX_OK && ran && h_status[i] != SV2_NONE)
-      st = int(int8_t(h_status[i] & 0xFFu));
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+  if (ran && max_rows != 0)
+    if (int st = status.fetch(ctx, s))
+      return st;
+  // (the status byte of a word is signed here)
+  return fold_jobs(jobs.size(), FoldOrder::LAST_FAILING, job_status, [&](size_t i) {
+    return status.host[i] == RSX_OK && ran && status.words[i] != STATUS_NONE
+               ? int(int8_t(status.words[i] & 0xFFu))
+               : int(status.host[i]);
+  });
 }
 
 } // namespace rsx

@@ -40,6 +40,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_scale.h"
 #include "rsx_scale_core.h"
 
@@ -393,10 +394,6 @@ struct ScPlan final : DecoderPlan {
   uint32_t init_blocks = 1, est_xb = 0, est_rows = 0, hist_blocks = 0, chain_blocks = 0, pass_xb = 0,
            pass_rows = 0;
   bool have_results = false;
-  ~ScPlan() override {
-    for (DeviceBuffer* b : {&d_jobs, &d_areas, &d_accs, &d_recs, &d_hist, &d_chk, &d_pw})
-      b->release();
-  }
   int run(const void*, void* out_dev, hipStream_t s, KernelTimer* timer) override {
     have_results = false;
     ScArgs A{};
@@ -456,16 +453,9 @@ struct ScPlan final : DecoderPlan {
                                         hipMemcpyDeviceToHost, s));
       RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
     }
-    int rc = RSX_OK;
-    for (size_t i = 0; i < n_jobs; ++i) {
-      const int32_t st = h_rec[i].status;
-      if (job_status)
-        job_status[i] = st;
-      if (st)
-        rc = st;
-    }
     have_results = ran;
-    return rc;
+    return fold_jobs(n_jobs, FoldOrder::LAST_FAILING, job_status,
+                     [&](size_t i) { return int(h_rec[i].status); });
   }
   int scale_result(int job, rsx_scale_result* out) override {
     if (job < 0 || size_t(job) >= n_jobs || !out || !have_results)
@@ -550,20 +540,12 @@ int scale_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_scale_job* jobs,
   const std::vector<uint32_t> pw = Gen::powers(1, max_gw + 1u);
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(Job) + 16)) ||
-      (st = p->d_areas.ensure(areas.size() * sizeof(rsx_scale_area) + 16)) ||
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_areas, areas)) ||
       (st = p->d_accs.ensure(p->jobs.size() * sizeof(Acc) + 16)) ||
       (st = p->d_recs.ensure(p->jobs.size() * sizeof(Rec) + 16)) ||
       (st = p->d_hist.ensure(size_t(hist_cells) * 4 + 16)) ||
-      (st = p->d_chk.ensure(size_t(chk_states) * 2 + 16)) ||
-      (st = p->d_pw.ensure(pw.size() * 4 + 16)))
+      (st = p->d_chk.ensure(size_t(chk_states) * 2 + 16)) || (st = upload(ctx, p->d_pw, pw)))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(Job),
-                               hipMemcpyHostToDevice));
-  if (!areas.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_areas.ptr, areas.data(), areas.size() * sizeof(rsx_scale_area),
-                                 hipMemcpyHostToDevice));
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_pw.ptr, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
   *out = std::move(p);
   return RSX_OK;
 }

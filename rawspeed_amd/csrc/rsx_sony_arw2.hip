@@ -43,6 +43,7 @@
 #include "rsx_dither_dev.h"
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_sony_arw2.h"
 
 namespace rsx {
@@ -56,7 +57,6 @@ constexpr int32_t A2_MAX_W = 9600, A2_MAX_H = 6376;      // SonyArw2Decompressor
 constexpr uint32_t A2_MAX_BLOCKS = A2_MAX_W / 16;        // blocks a row (at most)
 constexpr uint32_t A2_LUT = 2048;                        // table entries: p = 0 .. 0x7ff
 constexpr uint32_t A2_NO_TABLE = 0xFFFFFFFFu;
-constexpr uint32_t A2_NONE = 0xFFFFFFFFu;
 
 struct A2JobDev {
   uint64_t in_off;     // first byte of row 0 in the plan's input
@@ -80,7 +80,7 @@ struct A2Args {
   const uint32_t* tables; // [job's table][p]: base | delta << 16
   const uint32_t* pow16;  // [b]: 15700^(16 b) mod m
   uint32_t* row_status;   // [row of the plan]: rsx_status
-  uint32_t* job_status;   // [job]: first failing row << 8 | status, A2_NONE = fine
+  uint32_t* job_status;   // [job]: first failing row << 8 | status, STATUS_NONE = fine
 };
 
 // the 16 bytes of a block at any byte address: 16-byte aligned -> one load; else the five
@@ -277,16 +277,15 @@ namespace {
 struct Arw2Plan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   std::vector<A2JobDev> jobs;
-  std::vector<int32_t> host_status; // validation result per job
-  std::vector<uint32_t> consumed;   // input bytes a job reads (w * h when validated)
-  std::vector<uint32_t> job_rows;   // rows of a job (0 when rejected)
-  std::vector<int32_t> job_mode;    // table mode per job
-  std::vector<uint32_t> h_tables;   // device form of every job's table
-  DeviceBuffer d_jobs, d_items, d_tables, d_pow, d_row_status, d_status;
-  std::vector<uint32_t> h_status, h_row_status;
+  JobStatus status;
+  std::vector<uint32_t> consumed; // input bytes a job reads (w * h when validated)
+  std::vector<uint32_t> job_rows; // rows of a job (0 when rejected)
+  std::vector<int32_t> job_mode;  // table mode per job
+  std::vector<uint32_t> h_tables; // device form of every job's table
+  DeviceBuffer d_jobs, d_items, d_tables, d_pow, d_row_status;
+  std::vector<uint32_t> h_row_status;
   uint32_t n_items = 0, total_rows = 0;
   bool launched = false;
-  ~Arw2Plan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
   int row_status(hipStream_t s, int job, int32_t* statuses) override;
@@ -320,7 +319,7 @@ int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* job
                           std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<Arw2Plan>();
   p->ctx = ctx;
-  p->host_status.assign(n_jobs, RSX_OK);
+  p->status.host.assign(n_jobs, RSX_OK);
   p->consumed.assign(n_jobs, 0);
   p->job_rows.assign(n_jobs, 0);
   p->job_mode.assign(n_jobs, RSX_ARW2_TABLE_NONE);
@@ -336,7 +335,7 @@ int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* job
       p->consumed[i] = uint32_t(j.img.dim_x) * uint32_t(j.img.dim_y);
     if (st == RSX_OK && (j.img_offset % 2 != 0 || j.img.pitch_bytes % 2 != 0))
       st = RSX_ERR_INVALID_ARG;
-    p->host_status[i] = st;
+    p->status.host[i] = st;
     if (st != RSX_OK)
       continue;
     J.in_off = j.in_offset;
@@ -362,35 +361,18 @@ int sony_arw2_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_arw2_job* job
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const std::vector<uint32_t> pw = dither_powers(16, A2_MAX_BLOCKS); // 15700^(16 b) mod m
   int st;
-  if ((st = p->d_jobs.ensure(p->jobs.size() * sizeof(A2JobDev) + 16)) ||
-      (st = p->d_items.ensure(items.size() * sizeof(A2Item) + 16)) ||
-      (st = p->d_tables.ensure(p->h_tables.size() * 4 + 16)) ||
-      (st = p->d_pow.ensure(pw.size() * 4)) ||
-      (st = p->d_row_status.ensure(size_t(p->total_rows) * 4 + 16)) ||
-      (st = p->d_status.ensure(size_t(n_jobs) * 4 + 16)))
+  // (no pad behind d_pow: the kernel reads it one word at an index, pow16[block])
+  if ((st = upload(ctx, p->d_jobs, p->jobs)) || (st = upload(ctx, p->d_items, items)) ||
+      (st = upload(ctx, p->d_tables, p->h_tables)) || (st = upload(ctx, p->d_pow, pw, 0)) ||
+      (st = p->d_row_status.ensure(size_t(p->total_rows) * 4 + 16)) || (st = p->status.init()))
     return st;
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(A2JobDev),
-                               hipMemcpyHostToDevice));
-  if (!items.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_items.ptr, items.data(), items.size() * sizeof(A2Item),
-                                 hipMemcpyHostToDevice));
-  if (!p->h_tables.empty())
-    RSX_HIP_CHECK(ctx, hipMemcpy(p->d_tables.ptr, p->h_tables.data(), p->h_tables.size() * 4,
-                                 hipMemcpyHostToDevice));
-  RSX_HIP_CHECK(ctx, hipMemcpy(p->d_pow.ptr, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
-  p->h_status.assign(n_jobs, A2_NONE);
   *out = std::move(p);
   return RSX_OK;
 }
 
-Arw2Plan::~Arw2Plan() {
-  for (DeviceBuffer* b : {&d_jobs, &d_items, &d_tables, &d_pow, &d_row_status, &d_status})
-    b->release();
-}
-
 int sony_arw2_plan_set_table(DecoderPlan* plan, int job, const rsx_sony_arw2_desc* desc, hipStream_t s) {
   Arw2Plan* p = dynamic_cast<Arw2Plan*>(plan);
-  if (!p || job < 0 || size_t(job) >= p->jobs.size() || !desc || p->host_status[job] != RSX_OK ||
+  if (!p || job < 0 || size_t(job) >= p->jobs.size() || !desc || p->status.host[job] != RSX_OK ||
       desc->table_mode != p->job_mode[job])
     return RSX_ERR_INVALID_ARG;
   rsx_ctx* ctx = p->ctx;
@@ -418,8 +400,9 @@ int Arw2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer*
   A.tables = static_cast<const uint32_t*>(d_tables.ptr);
   A.pow16 = static_cast<const uint32_t*>(d_pow.ptr);
   A.row_status = static_cast<uint32_t*>(d_row_status.ptr);
-  A.job_status = static_cast<uint32_t*>(d_status.ptr);
-  RSX_HIP_CHECK(ctx, hipMemsetAsync(d_status.ptr, 0xFF, jobs.size() * 4, s));
+  A.job_status = static_cast<uint32_t*>(status.dev.ptr);
+  if (int st = status.reset(ctx, s))
+    return st;
   if (timer)
     timer->begin(s);
   hipLaunchKernelGGL(arw2_kernel, dim3(n_items), dim3(A2_THREADS), 0, s, A);
@@ -433,36 +416,13 @@ int Arw2Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer*
 int Arw2Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) {
   if (job_consumed)
     std::copy(consumed.begin(), consumed.end(), job_consumed);
-  if (ran && n_items != 0) {
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_status.data(), d_status.ptr, h_status.size() * 4,
-                                      hipMemcpyDeviceToHost, s));
-    RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  }
-  int rc = RSX_OK;
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    int st = host_status[i];
-    if (st == RSX_OK && ran && h_status[i] != A2_NONE)
-      st = int(h_status[i] & 0xFFu);
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+  return status.fold(ctx, s, ran && n_items != 0, 0xFFu, FoldOrder::LAST_FAILING, job_status);
 }
 
 int Arw2Plan::row_status(hipStream_t s, int job, int32_t* statuses) {
   if (job < 0 || size_t(job) >= jobs.size() || !launched || job_rows[job] == 0)
     return RSX_ERR_INVALID_ARG;
-  const uint32_t n = job_rows[job];
-  h_row_status.resize(n);
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(h_row_status.data(),
-                                    static_cast<const uint32_t*>(d_row_status.ptr) + jobs[job].row_base,
-                                    size_t(n) * 4, hipMemcpyDeviceToHost, s));
-  RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  for (uint32_t r = 0; r < n; ++r)
-    statuses[r] = int32_t(h_row_status[r]);
-  return RSX_OK;
+  return fetch_words(ctx, s, d_row_status, jobs[job].row_base, job_rows[job], h_row_status, statuses);
 }
 
 } // namespace rsx

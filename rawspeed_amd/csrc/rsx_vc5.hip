@@ -43,6 +43,7 @@
 
 #include "rsx_internal.h"
 #include "rsx_ljpeg_dev.h"
+#include "rsx_plan_host.h"
 #include "rsx_vc5.h"
 #include "rsx_vc5_core.h"
 
@@ -369,7 +370,6 @@ struct Vc5Plan final : DecoderPlan {
   uint32_t n_lp = 0, n_hp = 0;      // bands[0, n_lp) low-pass, [n_lp, n_lp + n_hp) high-pass
   uint32_t level_first[3] = {}, level_count[3] = {}; // items of level 3, 2, 1
   uint32_t merge_first = 0, merge_count = 0;
-  ~Vc5Plan() override;
   int run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) override;
   int results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job_consumed) override;
 };
@@ -526,41 +526,21 @@ int vc5_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_vc5_job* jobs,
     (k < 3 ? p->level_count[k] : p->merge_count) = uint32_t(items[k].size());
     all.insert(all.end(), items[k].begin(), items[k].end());
   }
-  p->h_status.assign(size_t(n_jobs) * 40, B_NONE);
+  p->h_status.assign(size_t(n_jobs) * 40, STATUS_NONE);
   p->h_stats.assign(size_t(n_jobs) * 80, 0);
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st;
-  if ((st = p->d_store.ensure(store * 2 + 16)) ||
-      (st = p->d_bands.ensure(bands.size() * sizeof(VcBand) + 16)) ||
-      (st = p->d_levels.ensure(levels.size() * sizeof(VcLevel) + 16)) ||
-      (st = p->d_items.ensure(all.size() * sizeof(VcItem) + 16)) ||
-      (st = p->d_merges.ensure(merges.size() * sizeof(VcMerge) + 16)) ||
-      (st = p->d_tables.ensure(tables.size() * sizeof(Table) + 16)) ||
-      (st = p->d_logs.ensure(logs.size() * 2 + 16)) ||
-      (st = p->d_status.ensure(p->h_status.size() * 4 + 16)) ||
-      (st = p->d_stats.ensure(p->h_stats.size() * 4 + 16)) ||
+  // (d_status and d_stats start as STATUS_NONE and zeros: bands of jobs the host turned down
+  // keep these)
+  if ((st = p->d_store.ensure(store * 2 + 16)) || (st = upload(ctx, p->d_bands, bands)) ||
+      (st = upload(ctx, p->d_levels, levels)) || (st = upload(ctx, p->d_items, all)) ||
+      (st = upload(ctx, p->d_merges, merges)) || (st = upload(ctx, p->d_tables, tables)) ||
+      (st = upload(ctx, p->d_logs, logs)) || (st = upload(ctx, p->d_status, p->h_status)) ||
+      (st = upload(ctx, p->d_stats, p->h_stats)) ||
       (st = p->d_flags.ensure(size_t(n_jobs) * 4 + 16)))
     return st;
-  auto up = [&](DeviceBuffer& d, const void* src, size_t n) {
-    return n == 0 ? hipSuccess : hipMemcpy(d.ptr, src, n, hipMemcpyHostToDevice);
-  };
-  RSX_HIP_CHECK(ctx, up(p->d_bands, bands.data(), bands.size() * sizeof(VcBand)));
-  RSX_HIP_CHECK(ctx, up(p->d_levels, levels.data(), levels.size() * sizeof(VcLevel)));
-  RSX_HIP_CHECK(ctx, up(p->d_items, all.data(), all.size() * sizeof(VcItem)));
-  RSX_HIP_CHECK(ctx, up(p->d_merges, merges.data(), merges.size() * sizeof(VcMerge)));
-  RSX_HIP_CHECK(ctx, up(p->d_tables, tables.data(), tables.size() * sizeof(Table)));
-  RSX_HIP_CHECK(ctx, up(p->d_logs, logs.data(), logs.size() * 2));
-  // (B_NONE and zeros: bands of jobs the host turned down keep these)
-  RSX_HIP_CHECK(ctx, up(p->d_status, p->h_status.data(), p->h_status.size() * 4));
-  RSX_HIP_CHECK(ctx, up(p->d_stats, p->h_stats.data(), p->h_stats.size() * 4));
   *out = std::move(p);
   return RSX_OK;
-}
-
-Vc5Plan::~Vc5Plan() {
-  for (DeviceBuffer* b : {&d_store, &d_bands, &d_levels, &d_items, &d_merges, &d_tables, &d_logs,
-                          &d_status, &d_stats, &d_flags})
-    b->release();
 }
 
 int Vc5Plan::run(const void* in_dev, void* out_dev, hipStream_t s, KernelTimer* timer) {
@@ -614,18 +594,13 @@ int Vc5Plan::results(hipStream_t s, bool ran, int32_t* job_status, uint32_t* job
                                       hipMemcpyDeviceToHost, s));
     RSX_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
-  int rc = RSX_OK;
-  for (int i = 0; i < n_jobs; ++i) {
+  return fold_jobs(size_t(n_jobs), FoldOrder::LAST_FAILING, job_status, [&](size_t i) {
     int st = host_status[i];
     if (st == RSX_OK && have) // the first failing band in (channel, subband) order
       for (int b = 0; b < 40 && st == RSX_OK; ++b)
-        st = h_status[size_t(i) * 40 + b] == B_NONE ? RSX_ERR_DEVICE : int(h_status[size_t(i) * 40 + b]);
-    if (job_status)
-      job_status[i] = st;
-    if (st != RSX_OK)
-      rc = st;
-  }
-  return rc;
+        st = h_status[i * 40 + b] == STATUS_NONE ? RSX_ERR_DEVICE : int(h_status[i * 40 + b]);
+    return st;
+  });
 }
 
 int vc5_plan_bands(DecoderPlan* plan, int job, int32_t* band_status, uint32_t* windows,

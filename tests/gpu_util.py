@@ -1,5 +1,6 @@
 """Helpers for the -m gpu parity tests: device buffers come from torch
 (plumbing only); every decode goes through the C-ABI (rawspeed_amd/librsx.so)."""
+import ctypes
 import os
 
 import numpy as np
@@ -28,6 +29,16 @@ def image_job_view(dim_x, dim_y, cpp, pitch, is_cfa=True):
     v.dim_x, v.dim_y, v.cpp = dim_x, dim_y, cpp
     v.is_cfa = 1 if is_cfa else 0
     return v
+
+
+def plan_row_status(plan, job, n):
+    """After results(): (status, the n row or strip statuses of job `job` of the last run) as the
+    plan's row_status gives them.  Phase One, Samsung V0 and ARW2 plans have no getter under their
+    own name; rsx_fuji_plan_strip_status hands the call to the plan whichever decoder made it
+    (decoder_plan_get, rsx_api.hip)."""
+    st = (ctypes.c_int32 * max(1, n))()
+    rc = capi.lib().rsx_fuji_plan_strip_status(plan._h, job, st)
+    return rc, list(st)[:n]
 
 
 class env:

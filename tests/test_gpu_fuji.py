@@ -152,6 +152,37 @@ def test_plan_of_mixed_jobs(gpu):
     plan.close()
 
 
+def test_plan_returns_the_last_failing_jobs_status(gpu):
+    """Three one-strip 768 x 6 jobs: the host refuses job 0 (its strip ends behind its in_bytes),
+    job 1 decodes, the strip of job 2 fails on the device with another status.  Every job gets its
+    own status and results() returns job 2's, the last failing job's; the strip statuses of a
+    refused job are not to be had, those of job 2 name the strip."""
+    names = ["b14_768x6_flat", "x14_768x6_flat", "b14_plant_escape"]
+    jobs, data, expect, out_bytes = _lay_out(names, 0x5A, lambda k: 3)
+    jobs[0].in_bytes -= 1
+    IO = abi.RSX_ERR_IO
+    bad_st, bad_strips, _ = F.expected(names[2])
+    assert bad_st not in (F.OK, IO) and bad_strips == [bad_st] and F.expected(names[1])[0] == F.OK
+    inp = torch.from_numpy(data).cuda()
+    out = torch.full((out_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    plan = gpu.fuji_plan(jobs)
+    plan.run(inp.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    rc, st, _ = plan.results()
+    assert st == [IO, F.OK, bad_st] and rc == bad_st
+    assert plan.strip_status(0, 1)[0] == abi.RSX_ERR_INVALID_ARG
+    assert plan.strip_status(2, 1) == (abi.RSX_OK, bad_strips)
+    plan.close()
+    host = out.cpu().numpy()
+    rect = np.lib.stride_tricks.as_strided
+    outside = np.ones(host.size, bool)
+    for name, off, pitch, w, h in expect[1:]:  # (job 1: every pixel; job 2: its whole lines)
+        px = np.ascontiguousarray(rect(host[off:], (h, 2 * w), (pitch, 1))).view(np.uint16)
+        F.check_pixels(name, px, 0xA5A5)
+        assert name != names[1] or np.array_equal(px, F.expected(name)[2])
+        rect(outside[off:], (h, 2 * w), (pitch, 1))[:] = False
+    assert (host[outside] == 0xA5).all(), "bytes outside the two images were written"
+
+
 def _lay_out(names, gap, gap_len, share=False):
     """the cases as jobs of one plan: every job its own image rectangle at its own pitch class;
     the inputs one behind the other with gap_len(k) bytes of `gap` between them (share: the jobs

@@ -141,6 +141,52 @@ def test_plan_jobs_of_different_geometry(gpu):
         assert np.array_equal(px, img)
 
 
+def test_plan_returns_the_last_failing_jobs_status(gpu):
+    """Three 8 x 3 jobs: the host refuses job 0 (a strip ends behind its in_bytes), job 1 decodes,
+    row 1 of job 2 fails on the device with another status.  Every job gets its own status and
+    results() returns job 2's, the last failing job's; the row statuses of a refused job are not
+    to be had, those of job 2 name the row."""
+    import gpu_util
+    w, h, pitch = 8, 3, 2 * 8 + 2
+    jobs, keep, parts, imgs = [], [], [], []
+    in_off = 0
+    for k in range(3):
+        img, rows, blob, rng = _file(90 + k, w, h)
+        if k == 2:
+            blob = I.iiq_file(I.damage(rows, 1, "col0", rng), w, rng)
+            bad_st, _, bad_rows = I.model_file(blob)
+        raw, strips, _, _ = I.iiq_strips(blob)
+        keep.append(abi.phase_one_strips(strips))
+        j = abi.PhaseOneJob()
+        j.strips = keep[-1]
+        j.n_strips = len(strips)
+        j.in_offset, j.in_bytes, j.img_offset = in_off, len(raw) - (k == 0), k * (pitch * h + 6)
+        j.img = abi.Image(None, pitch, w, h, 1, 1)
+        jobs.append(j)
+        parts.append(np.frombuffer(raw, np.uint8))
+        imgs.append(img)
+        in_off += len(raw)
+    INV = abi.RSX_ERR_INVALID_ARG
+    assert bad_st == I.RSX_ERR_BAD_HUFFMAN_CODE != INV and bad_rows == [0, bad_st, 0]
+    inp = torch.from_numpy(np.concatenate(parts)).cuda()
+    out = torch.full((3 * (pitch * h + 6),), 0xA5, dtype=torch.uint8, device="cuda")
+    plan = gpu.phase_one_plan(jobs)
+    plan.run(inp.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    rc, st, _ = plan.results()
+    assert st == [INV, abi.RSX_OK, bad_st] and rc == bad_st
+    assert gpu_util.plan_row_status(plan, 0, h)[0] == INV
+    assert gpu_util.plan_row_status(plan, 2, h) == (abi.RSX_OK, bad_rows)
+    plan.close()
+    host = out.cpu().numpy()
+    rect = np.lib.stride_tricks.as_strided
+    px = np.ascontiguousarray(rect(host[jobs[1].img_offset:], (h, 2 * w), (pitch, 1)))
+    assert np.array_equal(px.view(np.uint16), imgs[1])
+    outside = np.ones(host.size, bool)
+    for k in (1, 2):
+        rect(outside[jobs[k].img_offset:], (h, 2 * w), (pitch, 1))[:] = False
+    assert (host[outside] == 0xA5).all(), "bytes outside the two images were written"
+
+
 def test_two_threads_share_a_context(gpu):
     files = [_file(70 + t, w, h) for t, (w, h) in enumerate([(2000, 40), (1338, 57)])]
     results = [None, None]

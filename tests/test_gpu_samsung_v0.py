@@ -201,6 +201,52 @@ def test_plan_jobs_of_different_geometry(gpu):
     plan.close()
 
 
+def test_plan_returns_the_last_failing_jobs_status(gpu):
+    """Three 48 x 3 jobs: the host refuses job 0 (its in_bytes end inside row 0), job 1 decodes,
+    row 2 of job 2 fails on the device with another status.  Every job gets its own status and
+    results() returns job 2's, the last failing job's; the row statuses of a refused job are not
+    to be had, those of job 2 name the row."""
+    import gpu_util
+    w, h, planted, bad, bad_st, _ = M.planted("len_below_0")
+    good = S.random_rows(np.random.default_rng(0x9B), w, h, p_up=0.0)
+    _, bad_rows, _ = S.model_decode(w, h, planted)
+    mst, _, img = S.model_decode(w, h, good)
+    IO = abi.RSX_ERR_IO
+    assert mst == S.OK and bad_st == abi.RSX_ERR_VALUE_RANGE != IO and bad_rows[bad] == bad_st
+    pitch = 2 * w + 2
+    jobs, keep, parts = [], [], []
+    in_off = 0
+    for k, rows in enumerate([good, good, planted]):
+        strip, offs = S.strip_and_offsets(rows)
+        keep.append(abi.samsung_v0_offsets(offs))
+        j = abi.SamsungV0Job()
+        j.row_offsets = keep[-1]
+        j.n_offsets = len(offs)
+        j.in_offset, j.img_offset = in_off, k * (pitch * h + 6)
+        j.in_bytes = offs[1] - 1 if k == 0 else len(strip)
+        j.img = abi.Image(None, pitch, w, h, 1, 1)
+        jobs.append(j)
+        parts.append(strip)
+        in_off += len(strip)
+    inp = torch.from_numpy(np.concatenate(parts)).cuda()
+    out = torch.full((3 * (pitch * h + 6),), 0xA5, dtype=torch.uint8, device="cuda")
+    plan = gpu.samsung_v0_plan(jobs)
+    plan.run(inp.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    rc, st, _ = plan.results()
+    assert st == [IO, abi.RSX_OK, bad_st] and rc == bad_st
+    assert gpu_util.plan_row_status(plan, 0, h)[0] == abi.RSX_ERR_INVALID_ARG
+    assert gpu_util.plan_row_status(plan, 2, h) == (abi.RSX_OK, bad_rows)
+    plan.close()
+    host = out.cpu().numpy()
+    rect = np.lib.stride_tricks.as_strided
+    px = np.ascontiguousarray(rect(host[jobs[1].img_offset:], (h, 2 * w), (pitch, 1)))
+    assert np.array_equal(px.view(np.uint16), img)
+    outside = np.ones(host.size, bool)
+    for k in (1, 2):
+        rect(outside[jobs[k].img_offset:], (h, 2 * w), (pitch, 1))[:] = False
+    assert (host[outside] == 0xA5).all(), "bytes outside the two images were written"
+
+
 def test_plan_timing_names_both_kernels(gpu):
     rng = np.random.default_rng(0x71)
     w, h = 200, 9

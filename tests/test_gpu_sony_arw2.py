@@ -198,6 +198,38 @@ def test_plan_rejects_jobs_it_cannot_run(gpu):
     assert np.array_equal(px, img)
 
 
+def test_plan_returns_the_last_failing_jobs_status(gpu):
+    """Three 32 x 2 jobs: the host refuses job 0 (in_bytes one short of w * h), job 1 decodes,
+    row 1 of job 2 fails on the device with another status.  Every job gets its own status and
+    results() returns job 2's, the last failing job's; the row statuses of a refused job are not
+    to be had, those of job 2 name the row."""
+    import gpu_util
+    specs = [(32, 2, A.NONE, (0, 0, 0, 0), None, 0, 2, 6),
+             (32, 2, A.DITHER, A.REALISTIC_CURVE, None, 0, 2, 6),
+             (32, 2, A.PLAIN, A.REALISTIC_CURVE, 1, 0, 2, 6)]
+    jobs, keep, inp, expect, out_bytes = _plan_case(specs)
+    jobs[0].in_bytes = 32 * 2 - 1
+    IO = abi.RSX_ERR_IO
+    din = torch.from_numpy(inp).cuda()
+    out = torch.full((out_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    plan = gpu.sony_arw2_plan(jobs)
+    plan.run(din.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    rc, st, cons = plan.results()
+    assert IO != TILE and st == [IO, OK, TILE] and rc == TILE and cons == [0, 64, 64]
+    assert gpu_util.plan_row_status(plan, 0, 2)[0] == INV
+    assert gpu_util.plan_row_status(plan, 2, 2) == (OK, [OK, INV])
+    plan.close()
+    host = out.cpu().numpy()
+    rect = np.lib.stride_tricks.as_strided
+    off, pitch, w, h, img, _ = expect[1]
+    px = np.ascontiguousarray(rect(host[off:], (h, 2 * w), (pitch, 1)))
+    assert np.array_equal(px.view(np.uint16), img)
+    outside = np.ones(host.size, bool)
+    for off, pitch, w, h, _, _ in expect[1:]:
+        rect(outside[off:], (h, 2 * w), (pitch, 1))[:] = False
+    assert (host[outside] == 0xA5).all(), "bytes outside the two images were written"
+
+
 def test_kernel_table_names_the_arw2_kernel(gpu):
     specs = [(6048, 16, A.DITHER, A.REALISTIC_CURVE, None, 0, 0, 0),
              (6048, 16, A.NONE, (0, 0, 0, 0), None, 0, 0, 0)]
