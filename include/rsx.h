@@ -965,6 +965,78 @@ int rsx_olympus_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
                            const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 3w. KodakDecompressor (Kodak DCR, TIFF compression 65000)                 */
+/*    replaces KodakDecompressor::decompress()                               */
+/*    (decompressors/KodakDecompressor.cpp:120-150, per segment              */
+/*    decodeSegment :67-118), reached from DcrDecoder::decodeRawInternal     */
+/*    (decoders/DcrDecoder.cpp:58-120), with setWithLookUp                   */
+/*    (common/RawImage.h:335-353) and the curve guard (:355-383) that        */
+/*    installs mRaw->table before the call.                                  */
+/*    Rows top to bottom, each cut into segments of len = min(256, dim_x -   */
+/*    col) pixels: n = dim_x / 256 full ones, then a tail of t = dim_x % 256 */
+/*    if t != 0.  A segment is, in order:                                    */
+/*      len / 2 bytes of lengths: pixel 2k the low nibble of byte k, pixel   */
+/*        2k + 1 the high nibble (0..15);                                    */
+/*      the bit area, big-endian 16-bit units, each consumed from its least  */
+/*        significant bit upward: one unit up front if (len & 7) == 4        */
+/*        (init = 16 bits, else 0), then two units (4 bytes) whenever the    */
+/*        bits held are fewer than the next pixel's length.                  */
+/*    With cum(i) the sum of the lengths of pixels 0..i-1, pixel i's field   */
+/*    is bits [cum(i), cum(i) + len_i) of the units' concatenation (bit p:   */
+/*    bit p % 16 of the unit at byte 2 (p / 16)), there are                  */
+/*    r = ceil(max(0, cum(len) - init) / 32) 4-byte reads, and the segment   */
+/*    takes len / 2 + init / 8 + 4 r bytes: always an even number, so every  */
+/*    segment starts at an even offset of the stream.                        */
+/*    diff = 0 for length 0, else the JPEG extend of the field; pred[2] =    */
+/*    {0, 0} at every segment's start, pred[i & 1] += diff, and value =      */
+/*    pred[i & 1] must lie in 0 .. 2^bps - 1 ("Value out of bounds").  The   */
+/*    value stored is setWithLookUp(value) with the table `desc` describes:  */
+/*      RSX_KODAK_TABLE_NONE    no table (uncorrectedRawValues): the value   */
+/*      RSX_KODAK_TABLE_PLAIN   table[value] (2^bps entries read)            */
+/*      RSX_KODAK_TABLE_DITHER  table[2 value] (2^(bps + 1) entries read):   */
+/*                              the generator starts at 0 for the whole      */
+/*                              image and 15700 * 0 + 0 is 0, so the delta   */
+/*                              never contributes ((delta * 0 + 1024) >> 12  */
+/*                              is 0)                                        */
+/*    The table is copied during the call (or at plan creation).             */
+/*    rsx_kodak_validate: desc or img NULL, an unknown table_mode, or a NULL */
+/*    table with a mode other than NONE -> RSX_ERR_INVALID_ARG; then the     */
+/*    constructor's checks in its order (:46-65): cpp 1; dim positive,       */
+/*    dim_x % 4 == 0, dim_x <= 4516, dim_y <= 3012; bps 10 or 12 (and        */
+/*    pitch_bytes >= 2 dim_x) -> RSX_ERR_INVALID_ARG; in_bytes <             */
+/*    dim_x dim_y / 2 (input.check) -> RSX_ERR_IO.                           */
+/*    `in` is what DcrDecoder hands over: the rest of the file from the      */
+/*    strip's offset, so there usually are trailing bytes.  An image cannot  */
+/*    consume more than dim_y times the sum over a row's segments of         */
+/*    len / 2 + 2 + 4 ceil(15 len / 32) bytes; what lies behind is not read  */
+/*    (and not uploaded by a host-pointer call).                             */
+/*    Statuses of a decode, as the reference reaches them in decode order    */
+/*    (the first failing segment decides; inside a segment the read comes    */
+/*    first, decodeSegment reads all of it before the values are summed):    */
+/*      RSX_ERR_IO           a segment reads past in_bytes (getByte)         */
+/*      RSX_ERR_VALUE_RANGE  a value below 0 or above 2^bps - 1              */
+/*    `in` and `img->data` are both host or both device pointers.  Through   */
+/*    host pointers a failing call leaves the caller's image untouched;      */
+/*    through device pointers the image behind a failure is unspecified      */
+/*    (segments are decoded side by side), its pitch padding untouched.      */
+/* ------------------------------------------------------------------------ */
+enum {
+  RSX_KODAK_TABLE_NONE = 0,
+  RSX_KODAK_TABLE_PLAIN = 1,
+  RSX_KODAK_TABLE_DITHER = 2
+};
+
+typedef struct rsx_kodak_desc {
+  int32_t bps;           /* 10 or 12 */
+  int32_t table_mode;    /* RSX_KODAK_TABLE_* */
+  const uint16_t* table; /* TableLookUp::tables: 2^bps (PLAIN) / 2^(bps + 1) (DITHER) entries */
+} rsx_kodak_desc;
+
+int rsx_kodak_validate(const rsx_kodak_desc* desc, const rsx_image* img, size_t in_bytes);
+int rsx_kodak_decompress(rsx_ctx* ctx, const rsx_kodak_desc* desc, const uint8_t* in,
+                         size_t in_bytes, const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -1938,6 +2010,23 @@ int rsx_olympus_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_olympus_job* job
  * job): the status of job `job` of the last run.  RSX_ERR_INVALID_ARG for another plan or before
  * a run's results. */
 int rsx_olympus_plan_job_status(rsx_plan* plan, int job, int32_t* status);
+
+/* one Kodak DCR frame (section 3w); its table is copied at plan creation.  Jobs of different
+ * geometry, depth and table may share a plan: the frames' successor maps are made side by side and
+ * all their segments go into one launch.  Any in_offset, any even pitch_bytes >= 2 dim_x and any
+ * even img_offset.  Only the first min(in_bytes, what the image can consume) bytes are read.  The
+ * plan owns 6 bytes of maps per byte it reads.  rsx_plan_results gives every job its own status;
+ * a failing job does not disturb the others. */
+typedef struct rsx_kodak_job {
+  rsx_kodak_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_kodak_job;
+
+int rsx_kodak_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_kodak_job* jobs,
+                          rsx_plan** out_plan);
 
 int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
                              rsx_plan** out_plan);

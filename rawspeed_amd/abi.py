@@ -745,3 +745,33 @@ class OlympusJob(C.Structure):
     """rsx_olympus_job (include/rsx.h section 3v)"""
     _fields_ = [("in_offset", C.c_uint64), ("in_bytes", C.c_uint64), ("img_offset", C.c_uint64),
                 ("img", Image)]
+
+
+RSX_KODAK_TABLE_NONE, RSX_KODAK_TABLE_PLAIN, RSX_KODAK_TABLE_DITHER = 0, 1, 2
+
+
+class KodakDesc(C.Structure):
+    """rsx_kodak_desc (include/rsx.h section 3w)"""
+    _fields_ = [("bps", C.c_int32), ("table_mode", C.c_int32), ("table", C.POINTER(C.c_uint16))]
+
+
+class KodakJob(C.Structure):
+    """rsx_kodak_job"""
+    _fields_ = [("desc", KodakDesc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def kodak_table_entries(bps, mode):
+    """entries of TableLookUp::tables a mode reads: 1024 / 2048 (bps 10), 4096 / 8192 (bps 12)"""
+    return 0 if mode == RSX_KODAK_TABLE_NONE else (2 if mode == RSX_KODAK_TABLE_DITHER else 1) << bps
+
+
+def kodak_desc(bps, mode, table=None):
+    """(desc, keep-alive array): `table` as TableLookUp holds it (uint16; None for NONE)"""
+    d = KodakDesc()
+    d.bps, d.table_mode = bps, mode
+    arr = None
+    if table is not None:
+        arr = np.ascontiguousarray(table, dtype=np.uint16)
+        d.table = arr.ctypes.data_as(C.POINTER(C.c_uint16))
+    return d, arr

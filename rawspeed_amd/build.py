@@ -20,6 +20,8 @@
                                 the compressed-RAF core (rsx_fuji_core.h) as host C++ (g++)
   rawspeed_amd/librsx_olympus_host.so, rawspeed_amd/rsx_olympus_host_check
                                 the compressed-ORF core (rsx_olympus_core.h) as host C++ (g++)
+  rawspeed_amd/librsx_kodak_host.so, rawspeed_amd/rsx_kodak_host_check
+                                the Kodak DCR core (rsx_kodak_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -53,13 +55,16 @@ LIB_FUJI_HOST = os.path.join(PKG, "librsx_fuji_host.so")
 BIN_FUJI_CHECK = os.path.join(PKG, "rsx_fuji_host_check")
 LIB_OLYMPUS_HOST = os.path.join(PKG, "librsx_olympus_host.so")
 BIN_OLYMPUS_CHECK = os.path.join(PKG, "rsx_olympus_host_check")
+LIB_KODAK_HOST = os.path.join(PKG, "librsx_kodak_host.so")
+BIN_KODAK_CHECK = os.path.join(PKG, "rsx_kodak_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
                 "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_vc5.hip",
                 "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_scale.hip",
-                "rsx_dng_jpeg.hip", "rsx_fuji.hip", "rsx_olympus.hip", "rsx_host.cpp"]
+                "rsx_dng_jpeg.hip", "rsx_fuji.hip", "rsx_olympus.hip", "rsx_kodak.hip",
+                "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
@@ -69,7 +74,7 @@ CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.
                 "rsx_dng_post.h", "rsx_dng_post_core.h", "rsx_bad_pixels.h",
                 "rsx_bad_pixels_core.h", "rsx_scale.h", "rsx_scale_core.h",
                 "rsx_dng_jpeg.h", "rsx_jpeg_core.h", "rsx_fuji.h", "rsx_fuji_core.h",
-                "rsx_olympus.h", "rsx_olympus_core.h"]
+                "rsx_olympus.h", "rsx_olympus_core.h", "rsx_kodak.h", "rsx_kodak_core.h"]
 
 
 def _hipcc():
@@ -202,6 +207,13 @@ def build_olympus_host(force=False):
                             ["-I" + INCLUDE], force)
 
 
+def build_kodak_host(force=False):
+    """rsx_kodak_core.h: integers only, one thread a frame"""
+    return _build_host_core(LIB_KODAK_HOST, BIN_KODAK_CHECK, "rsx_kodak_host.cpp",
+                            ["rsx_kodak_core.h", _RSX_H], "RSX_KODAK_HOST_MAIN",
+                            ["-I" + INCLUDE], force)
+
+
 def _compile_objects(objdir, extra_flags, force=False):
     """One object per source under `objdir`, rebuilt when the source or any header is newer;
     the stale ones in parallel (the sources are independent translation units: one hipcc run
@@ -258,7 +270,7 @@ def build_all(force=False):
     return (build_core(force), build_synth(force), build_inflate_host(force),
             build_vc5_host(force), build_iiq_corr_host(force), build_dng_post_host(force),
             build_bad_pixels_host(force), build_scale_host(force), build_jpeg_host(force),
-            build_fuji_host(force), build_olympus_host(force))
+            build_fuji_host(force), build_olympus_host(force), build_kodak_host(force))
 
 
 if __name__ == "__main__":

@@ -55,6 +55,7 @@ EXPORTS = [
     "rsx_fuji_plan_strip_status",
     "rsx_olympus_validate", "rsx_olympus_decompress", "rsx_olympus_plan_create",
     "rsx_olympus_plan_job_status",
+    "rsx_kodak_validate", "rsx_kodak_decompress", "rsx_kodak_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -190,6 +191,9 @@ def lib():
         L.rsx_olympus_validate.argtypes = [C.c_size_t, C.c_void_p]
         L.rsx_olympus_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsx_olympus_plan_job_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_kodak_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_kodak_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -216,7 +220,8 @@ def lib():
                      "rsx_vc5_plan_create", "rsx_iiq_correct_plan_create",
                      "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
                      "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create",
-                     "rsx_fuji_plan_create", "rsx_olympus_plan_create"):
+                     "rsx_fuji_plan_create", "rsx_olympus_plan_create",
+                     "rsx_kodak_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -343,6 +348,13 @@ def fuji_validate(desc, img_view):
 def olympus_validate(in_bytes, img_view):
     """rsx_olympus_validate; None passes NULL"""
     return lib().rsx_olympus_validate(in_bytes, None if img_view is None else C.byref(img_view))
+
+
+def kodak_validate(bps, mode, table, img_view, in_bytes):
+    """rsx_kodak_validate; bps None passes a NULL desc, img_view None a NULL image"""
+    d, keep = (None, None) if bps is None else abi.kodak_desc(bps, mode, table)
+    return lib().rsx_kodak_validate(None if d is None else C.byref(d),
+                                    None if img_view is None else C.byref(img_view), in_bytes)
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -685,6 +697,16 @@ class Context:
         return lib().rsx_olympus_decompress(self._h, C.c_void_p(in_ptr), in_bytes,
                                             C.byref(img_view))
 
+    def kodak_decompress(self, bps, mode, table, data, img_view, in_ptr=None, in_bytes=None):
+        """data: the stream (host bytes), or the device buffer at in_ptr (then img_view.data is a
+        device pointer too).  Returns the status."""
+        d, keep = abi.kodak_desc(bps, mode, table)
+        if in_ptr is None:
+            a = _u8(np.frombuffer(bytes(data) + b"\0", np.uint8))  # (a pointer for no bytes)
+            in_ptr, in_bytes = a.ctypes.data, len(data)
+        return lib().rsx_kodak_decompress(self._h, C.byref(d), C.c_void_p(in_ptr), in_bytes,
+                                          C.byref(img_view))
+
     def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
         """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
         tiles' zlib streams.  Returns (status, per-tile statuses)."""
@@ -830,6 +852,11 @@ class Context:
     def olympus_plan(self, jobs):
         """jobs: abi.OlympusJob, one per frame (geometries may mix)"""
         return OlympusPlan(self, "rsx_olympus_plan_create", abi.OlympusJob, jobs)
+
+    def kodak_plan(self, jobs):
+        """jobs: abi.KodakJob, one per frame (geometries, depths and tables may mix; the tables
+        are copied at plan creation)"""
+        return Plan(self, "rsx_kodak_plan_create", abi.KodakJob, jobs)
 
     def dng_jpeg_plan(self, jobs):
         """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""

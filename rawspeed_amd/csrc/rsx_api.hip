@@ -16,6 +16,8 @@
 #include "rsx_fuji_core.h"
 #include "rsx_olympus.h"
 #include "rsx_olympus_core.h"
+#include "rsx_kodak.h"
+#include "rsx_kodak_core.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
@@ -4045,6 +4047,59 @@ extern "C" int rsx_olympus_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in
   }
   std::vector<uint8_t> key = one_job_key(rsx_olympus_plan_create, job);
   return single_image_host(ctx, key, rsx_olympus_plan_create, job, in, in_bytes, img, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// KodakDecompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_kodak_validate(const rsx_kodak_desc* desc, const rsx_image* img,
+                                  size_t in_bytes) {
+  return rsx_kodak::validate(desc, img, in_bytes);
+}
+
+extern "C" int rsx_kodak_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_kodak_job* jobs,
+                                     rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, kodak_plan_create);
+}
+
+// Device pointers: a plan of the call's own runs on them, on the context's stream behind the null
+// stream's work so far, and the call returns when it is done.  Host pointers (single_image_host):
+// the bytes the image can consume go up as one copy; the plan is keyed by the geometry, that
+// size, the depth and the table mode; the table itself is call data and goes up on every call.
+extern "C" int rsx_kodak_decompress(rsx_ctx* ctx, const rsx_kodak_desc* desc, const uint8_t* in,
+                                    size_t in_bytes, const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_kodak::validate(desc, img, in_bytes))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool in_dev = is_device_pointer(in), out_dev = is_device_pointer(img->data);
+  if (in_dev != out_dev)
+    return RSX_ERR_INVALID_ARG;
+  const size_t span = size_t(
+      std::min<uint64_t>(in_bytes, rsx_kodak::image_bound(img->dim_x, img->dim_y)));
+  rsx_kodak_job job;
+  one_job_init(job, span, img);
+  job.desc.bps = desc->bps;
+  job.desc.table_mode = desc->table_mode;
+  if (in_dev) {
+    job.desc.table = desc->table;
+    CallPlan call;
+    if (int st = rsx_kodak_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    return call.run(in, img->data, nullptr);
+  }
+  // (desc.table is NULL here: not in the key)
+  std::vector<uint8_t> key = one_job_key(rsx_kodak_plan_create, job);
+  job.desc.table = desc->table;
+  SingleImageHooks hooks;
+  hooks.on_reuse = [desc](rsx_plan* plan, hipStream_t s) {
+    return kodak_plan_set_table(plan->dec.get(), 0, desc, s);
+  };
+  return single_image_host(ctx, key, rsx_kodak_plan_create, job, in, span, img, nullptr, hooks);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

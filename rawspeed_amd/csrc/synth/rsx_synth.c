@@ -1127,3 +1127,56 @@ size_t rsx_synth_olympus_plant(int w, int h, const int32_t* syms, int n_syms, ui
   const size_t n = oly_finish(&bw);
   return bw.overflow ? 0 : n + 7;
 }
+
+/* ------------------------------------------------------------------------ */
+/* Kodak DCR (KodakDecompressor.cpp:67-150): rows of segments of at most 256 */
+/* pixels; a segment is one 4-bit length a pixel, then the fields as         */
+/* big-endian 16-bit units filled from the least significant bit: one unit   */
+/* up front if (len & 7) == 4, then 4 bytes whenever the reader runs dry.    */
+/* Every pixel gets the shortest length that holds its difference from the   */
+/* pixel two to its left (0 at a segment's start).                           */
+/* ------------------------------------------------------------------------ */
+size_t rsx_synth_kodak_encode(int w, int h, const uint16_t* target, uint8_t* out, size_t cap) {
+  if (w <= 0 || h <= 0 || (w & 3))
+    return 0;
+  size_t pos = 0;
+  for (int row = 0; row < h; ++row) {
+    for (int col = 0; col < w; col += 256) {
+      const int len = w - col < 256 ? w - col : 256;
+      const uint16_t* px = target + (size_t)row * (size_t)w + col;
+      uint8_t n[256];
+      uint32_t field[256];
+      uint32_t total = 0;
+      int32_t pred[2] = {0, 0};
+      for (int i = 0; i < len; ++i) {
+        const int32_t d = (int32_t)px[i] - pred[i & 1];
+        pred[i & 1] = px[i];
+        const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+        int bits = 0;
+        while (bits < 16 && (a >> bits))
+          ++bits;
+        if (bits > 15)
+          return 0;
+        n[i] = (uint8_t)bits;
+        field[i] = (uint32_t)(d >= 0 ? d : d + (1 << bits) - 1);
+        total += (uint32_t)bits;
+      }
+      const uint32_t init = (len & 7) == 4 ? 16u : 0u;
+      const uint32_t over = total > init ? total - init : 0u;
+      const size_t area = init / 8u + 4u * ((over + 31u) / 32u);
+      if (pos + (size_t)len / 2 + area > cap)
+        return 0;
+      for (int k = 0; k < len / 2; ++k)
+        out[pos++] = (uint8_t)(n[2 * k] | n[2 * k + 1] << 4);
+      memset(out + pos, 0, area);
+      uint32_t cum = 0;
+      for (int i = 0; i < len; ++i) {
+        for (int b = 0; b < n[i]; ++b, ++cum)
+          if ((field[i] >> b) & 1u)
+            out[pos + 2 * (cum >> 4) + ((cum & 15u) < 8u ? 1 : 0)] |= (uint8_t)(1u << (cum & 7u));
+      }
+      pos += area;
+    }
+  }
+  return pos;
+}

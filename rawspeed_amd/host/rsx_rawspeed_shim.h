@@ -282,6 +282,23 @@ inline int olympus(const ByteStream& input, const RawImage& img) {
   return rsx_olympus_decompress(rsx, in.begin(), in.getSize(), &v);
 }
 
+// KodakDecompressor::decompress(): `input` is what DcrDecoder hands over, the
+// rest of the file from the strip's offset; `t` the table the curve guard installed (mRaw->table
+// through the accessor of 3i; the dithering one, or none with uncorrectedRawValues)
+inline int kodak(const ByteStream& input, const RawImage& img, int bps, const TableLookUp* t) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  rsx_kodak_desc d{};
+  d.bps = bps;
+  d.table_mode = !t ? RSX_KODAK_TABLE_NONE
+                    : (t->dither ? RSX_KODAK_TABLE_DITHER : RSX_KODAK_TABLE_PLAIN);
+  d.table = t ? t->tables.data() : nullptr; // (table 0; the call reads its first 2^bps / 2^(bps + 1))
+  const rsx_image v = view(img);
+  const Buffer in = input.peekRemainingBuffer();
+  return rsx_kodak_decompress(rsx, &d, in.begin(), in.getSize(), &v);
+}
+
 // DngDecoder::decodeRawInternal() / handleMetadata(): what follows the tiles --
 // OpcodeList1 and the LinearizationTable look-up -- handed to the tile fan-out so that it runs on
 // the device in front of the ONE download.  The hunk fills this BEFORE decodeData (the entries,

@@ -73,6 +73,9 @@ def lib():
         _lib.rsx_synth_olympus_plant.restype = C.c_size_t
         _lib.rsx_synth_olympus_plant.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                  C.c_size_t]
+        _lib.rsx_synth_kodak_encode.restype = C.c_size_t
+        _lib.rsx_synth_kodak_encode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_size_t]
     return _lib
 
 
@@ -374,6 +377,19 @@ def olympus_plant(w, h, syms):
     n = lib().rsx_synth_olympus_plant(w, h, a.ctypes.data, a.shape[0], out.ctypes.data, cap)
     if n == 0:
         raise ValueError("Olympus plant failed")
+    return out[:n].tobytes()
+
+
+def kodak_encode(target):
+    """The Kodak DCR stream (KodakDecompressor.cpp:67-150) that decodes to `target`, (h, w) uint16
+    with w a multiple of 4: every pixel with the shortest length that holds its difference."""
+    target = np.ascontiguousarray(target, dtype=np.uint16)
+    h, w = target.shape
+    cap = target.size * 3 + 16  # (half a byte of length and at most 15 bits a pixel, 6 a segment)
+    out = np.empty(cap, dtype=np.uint8)
+    n = lib().rsx_synth_kodak_encode(w, h, target.ctypes.data, out.ctypes.data, cap)
+    if n == 0:
+        raise ValueError("Kodak encode failed")
     return out[:n].tobytes()
 
 
