@@ -1037,6 +1037,69 @@ int rsx_kodak_decompress(rsx_ctx* ctx, const rsx_kodak_desc* desc, const uint8_t
                          size_t in_bytes, const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 3x. CrwDecompressor (Canon CRW: EOS D30 / D60 / 10D / 300D, PowerShot G, S) */
+/*    replaces CrwDecompressor::decompress()                                 */
+/*    (decompressors/CrwDecompressor.cpp:210-286, per block decodeBlock      */
+/*    :167-207), reached from CrwDecoder::decodeRawInternal                  */
+/*    (decoders/CrwDecoder.cpp:71-123).                                      */
+/*    `in` is the scan: Huffman-coded and JPEG-stuffed (FF 00 is a data FF,  */
+/*    FF xx with xx != 00 ends the stream), one chain for the whole frame.   */
+/*    It holds dim_x dim_y / 64 blocks of 64 differences.  A symbol is a     */
+/*    code of the table number's first tree (coefficient 0) or second tree   */
+/*    (behind it) whose value is run << 4 | len: 00 behind coefficient 0     */
+/*    ends the block, ff moves on by one, else the index moves on by run,    */
+/*    len == 0 moves on by one more, and otherwise len bits follow (consumed */
+/*    even when the run has passed coefficient 63) and are the JPEG extend   */
+/*    of coefficient i.  Coefficient 0 carries a running sum over all blocks */
+/*    of the frame.  Pixel k of the frame (row-major) adds difference k to   */
+/*    one of two running sums, by the parity of k & 63 -- which is the       */
+/*    parity of the column, dim_x being even -- both 512 at every row's      */
+/*    start; a sum outside 0..1023 is "Error decompressing".  With low bits, */
+/*    a pixel becomes pixel << 2 | two bits of `low` (one byte per four      */
+/*    pixels, the first pixel in bits 0..1), and where dim_x == 2672 a       */
+/*    result below 512 gets + 2.                                             */
+/*    The refill rule as a closed form of consumed bits: the reader calls    */
+/*    fill(32) in front of every symbol, so in front of a symbol that starts */
+/*    at consumed bit c it has fetched 4 (ceil(c / 32) + 1) data bytes, and  */
+/*    fill k (from 0) is taken at the first symbol start c > 32 (k - 1).     */
+/*    Behind the data the reader supplies zeros.  Without a marker, with N   */
+/*    data bytes in in_bytes raw bytes that end at R (in_bytes, or           */
+/*    in_bytes + 1 when the last byte is FF), the first symbol start         */
+/*    c > 32 floor((in_bytes + 16 + N - R) / 4) is the overflow read.  A     */
+/*    marker behind M data bytes is met by fill floor(M / 4), at symbol      */
+/*    start cm; it leaves 64 bits in the cache and four more fills pass, so  */
+/*    the first symbol start c > cm + 160 is the overflow read.  A frame     */
+/*    whose last block ends in front of that decodes.                        */
+/*    rsx_crw_validate: desc or img NULL -> RSX_ERR_INVALID_ARG; then the    */
+/*    constructor's checks (:46-72, :87-89): cpp 1; dim positive, dim_x % 4  */
+/*    == 0, dim_x <= 4104, dim_y <= 3048, dim_x dim_y % 64 == 0; dec_table   */
+/*    <= 2; with has_lowbits, low_bytes >= dim_x dim_y / 4 (and pitch_bytes  */
+/*    >= 2 dim_x) -> RSX_ERR_INVALID_ARG; in_bytes < 8 (the reader's         */
+/*    MaxProcessBytes) -> RSX_ERR_IO.                                        */
+/*    Statuses of a decode: the first failure in the reference's order,      */
+/*    which is block b's parse, then block b's 64 pixels, then block b + 1:  */
+/*      RSX_ERR_BAD_HUFFMAN_CODE  no code of the tree matches                */
+/*      RSX_ERR_INPUT_OVERFLOW    the overflow read above                    */
+/*      RSX_ERR_VALUE_RANGE       a pixel outside 0..1023                    */
+/*    `in`, `low` (NULL without low bits) and `img->data` are all host or    */
+/*    all device pointers; pitch_bytes is even.  Only the first              */
+/*    min(in_bytes, 496 dim_x dim_y / 64 + 2) bytes of `in` and the first    */
+/*    dim_x dim_y / 4 of `low` are read.  Bytes of the image outside its     */
+/*    rows are untouched.  Through host pointers a failing call leaves the   */
+/*    caller's image untouched; through device pointers the image behind a   */
+/*    failure is unspecified.                                                */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_crw_desc {
+  uint32_t dec_table;   /* 0..2: which pair of trees */
+  uint32_t has_lowbits; /* != 0: the two low bits of every pixel come from `low` */
+} rsx_crw_desc;
+
+int rsx_crw_validate(const rsx_crw_desc* desc, const rsx_image* img, size_t in_bytes,
+                     size_t low_bytes);
+int rsx_crw_decompress(rsx_ctx* ctx, const rsx_crw_desc* desc, const uint8_t* in, size_t in_bytes,
+                       const uint8_t* low, size_t low_bytes, const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -2027,6 +2090,33 @@ typedef struct rsx_kodak_job {
 
 int rsx_kodak_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_kodak_job* jobs,
                           rsx_plan** out_plan);
+
+/* one Canon CRW frame (section 3x).  The scan and the low bits are two ranges of the run's input
+ * buffer (low_bytes is ignored without low bits).  Jobs of different geometry and table may share
+ * a plan; the windows of all their scans are parsed side by side.  Any in_offset and low_offset,
+ * any even pitch_bytes >= 2 dim_x and any even img_offset.  The plan owns about 1.3 bytes per
+ * byte of scan it reads.  rsx_plan_results gives every job its own status; a failing job does
+ * not disturb the others.  Job results report 0 bytes consumed. */
+typedef struct rsx_crw_job {
+  rsx_crw_desc desc;
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t low_offset;
+  uint64_t low_bytes;
+  uint64_t img_offset;
+  rsx_image img; /* .data ignored */
+} rsx_crw_job;
+
+int rsx_crw_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_crw_job* jobs, rsx_plan** out_plan);
+
+/* After rsx_plan_results: how job `job` of the last run was parsed.  stats[0] the windows of its
+ * scan, stats[1] the most rounds a window took to settle its segments, stats[2] the last of the
+ * speculative rounds over the windows in which a window's head still changed (0: the first pass
+ * had them right), stats[3] != 0 if the settling kernel had to re-parse a window.  The number of
+ * speculative rounds is read from RSX_CRW_SPEC_ROUNDS when the context is created (default 4; 0
+ * leaves every window behind the first to the settling kernel; values above 32 count as 32).  The result of a run does not
+ * depend on it. */
+int rsx_crw_plan_stats(rsx_plan* plan, int job, uint32_t stats[4]);
 
 int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
                              rsx_plan** out_plan);

@@ -775,3 +775,21 @@ def kodak_desc(bps, mode, table=None):
         arr = np.ascontiguousarray(table, dtype=np.uint16)
         d.table = arr.ctypes.data_as(C.POINTER(C.c_uint16))
     return d, arr
+
+
+class CrwDesc(C.Structure):
+    """rsx_crw_desc (include/rsx.h section 3x)"""
+    _fields_ = [("dec_table", C.c_uint32), ("has_lowbits", C.c_uint32)]
+
+
+class CrwJob(C.Structure):
+    """rsx_crw_job: the scan and the low bits are two ranges of the run's input buffer"""
+    _fields_ = [("desc", CrwDesc), ("in_offset", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("low_offset", C.c_uint64), ("low_bytes", C.c_uint64),
+                ("img_offset", C.c_uint64), ("img", Image)]
+
+
+def crw_desc(dec_table, has_lowbits):
+    d = CrwDesc()
+    d.dec_table, d.has_lowbits = dec_table, 1 if has_lowbits else 0
+    return d

@@ -22,6 +22,8 @@
                                 the compressed-ORF core (rsx_olympus_core.h) as host C++ (g++)
   rawspeed_amd/librsx_kodak_host.so, rawspeed_amd/rsx_kodak_host_check
                                 the Kodak DCR core (rsx_kodak_core.h) as host C++ (g++)
+  rawspeed_amd/librsx_crw_host.so, rawspeed_amd/rsx_crw_host_check
+                                the Canon CRW core (rsx_crw_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -57,6 +59,8 @@ LIB_OLYMPUS_HOST = os.path.join(PKG, "librsx_olympus_host.so")
 BIN_OLYMPUS_CHECK = os.path.join(PKG, "rsx_olympus_host_check")
 LIB_KODAK_HOST = os.path.join(PKG, "librsx_kodak_host.so")
 BIN_KODAK_CHECK = os.path.join(PKG, "rsx_kodak_host_check")
+LIB_CRW_HOST = os.path.join(PKG, "librsx_crw_host.so")
+BIN_CRW_CHECK = os.path.join(PKG, "rsx_crw_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
@@ -64,7 +68,7 @@ CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_dir
                 "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_vc5.hip",
                 "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_scale.hip",
                 "rsx_dng_jpeg.hip", "rsx_fuji.hip", "rsx_olympus.hip", "rsx_kodak.hip",
-                "rsx_host.cpp"]
+                "rsx_crw.hip", "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
@@ -74,7 +78,8 @@ CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.
                 "rsx_dng_post.h", "rsx_dng_post_core.h", "rsx_bad_pixels.h",
                 "rsx_bad_pixels_core.h", "rsx_scale.h", "rsx_scale_core.h",
                 "rsx_dng_jpeg.h", "rsx_jpeg_core.h", "rsx_fuji.h", "rsx_fuji_core.h",
-                "rsx_olympus.h", "rsx_olympus_core.h", "rsx_kodak.h", "rsx_kodak_core.h"]
+                "rsx_olympus.h", "rsx_olympus_core.h", "rsx_kodak.h", "rsx_kodak_core.h",
+                "rsx_crw.h", "rsx_crw_core.h", "rsx_crw_tables.h"]
 
 
 def _hipcc():
@@ -116,7 +121,7 @@ def _links_with_sanitizers():
 
 def build_synth(force=False):
     src = os.path.join(CSRC, "synth", "rsx_synth.c")
-    if force or _stale(LIB_SYNTH, [src]):
+    if force or _stale(LIB_SYNTH, [src, os.path.join(CSRC, "rsx_crw_tables.h")]):
         _run(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-Wall", "-Wextra",
               "-o", LIB_SYNTH, src])
     return LIB_SYNTH
@@ -214,6 +219,13 @@ def build_kodak_host(force=False):
                             ["-I" + INCLUDE], force)
 
 
+def build_crw_host(force=False):
+    """rsx_crw_core.h: integers only, one thread a frame"""
+    return _build_host_core(LIB_CRW_HOST, BIN_CRW_CHECK, "rsx_crw_host.cpp",
+                            ["rsx_crw_core.h", "rsx_crw_tables.h", _RSX_H], "RSX_CRW_HOST_MAIN",
+                            ["-I" + INCLUDE], force)
+
+
 def _compile_objects(objdir, extra_flags, force=False):
     """One object per source under `objdir`, rebuilt when the source or any header is newer;
     the stale ones in parallel (the sources are independent translation units: one hipcc run
@@ -270,7 +282,8 @@ def build_all(force=False):
     return (build_core(force), build_synth(force), build_inflate_host(force),
             build_vc5_host(force), build_iiq_corr_host(force), build_dng_post_host(force),
             build_bad_pixels_host(force), build_scale_host(force), build_jpeg_host(force),
-            build_fuji_host(force), build_olympus_host(force), build_kodak_host(force))
+            build_fuji_host(force), build_olympus_host(force), build_kodak_host(force),
+            build_crw_host(force))
 
 
 if __name__ == "__main__":

@@ -56,6 +56,7 @@ EXPORTS = [
     "rsx_olympus_validate", "rsx_olympus_decompress", "rsx_olympus_plan_create",
     "rsx_olympus_plan_job_status",
     "rsx_kodak_validate", "rsx_kodak_decompress", "rsx_kodak_plan_create",
+    "rsx_crw_validate", "rsx_crw_decompress", "rsx_crw_plan_create", "rsx_crw_plan_stats",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -194,6 +195,10 @@ def lib():
         L.rsx_kodak_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsx_kodak_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p]
+        L.rsx_crw_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        L.rsx_crw_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_crw_plan_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -221,7 +226,7 @@ def lib():
                      "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
                      "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create",
                      "rsx_fuji_plan_create", "rsx_olympus_plan_create",
-                     "rsx_kodak_plan_create"):
+                     "rsx_kodak_plan_create", "rsx_crw_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -355,6 +360,14 @@ def kodak_validate(bps, mode, table, img_view, in_bytes):
     d, keep = (None, None) if bps is None else abi.kodak_desc(bps, mode, table)
     return lib().rsx_kodak_validate(None if d is None else C.byref(d),
                                     None if img_view is None else C.byref(img_view), in_bytes)
+
+
+def crw_validate(dec_table, has_lowbits, img_view, in_bytes, low_bytes):
+    """rsx_crw_validate; dec_table None passes a NULL desc, img_view None a NULL image"""
+    d = None if dec_table is None else abi.crw_desc(dec_table, has_lowbits)
+    return lib().rsx_crw_validate(None if d is None else C.byref(d),
+                                  None if img_view is None else C.byref(img_view), in_bytes,
+                                  low_bytes)
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -707,6 +720,23 @@ class Context:
         return lib().rsx_kodak_decompress(self._h, C.byref(d), C.c_void_p(in_ptr), in_bytes,
                                           C.byref(img_view))
 
+    def crw_decompress(self, dec_table, data, low, img_view, in_ptr=None, in_bytes=None,
+                       low_ptr=None, low_bytes=None):
+        """data, low: the scan and the low bits (host bytes; low None: no low bits), or the device
+        buffers at in_ptr / low_ptr (then img_view.data is a device pointer too).  Returns the
+        status."""
+        has_low = low is not None or low_ptr is not None
+        d = abi.crw_desc(dec_table, has_low)
+        if in_ptr is None:
+            a = _u8(np.frombuffer(bytes(data) + b"\0", np.uint8))  # (a pointer for no bytes)
+            in_ptr, in_bytes = a.ctypes.data, len(data)
+            if has_low:
+                b = _u8(np.frombuffer(bytes(low) + b"\0", np.uint8))
+                low_ptr, low_bytes = b.ctypes.data, len(low)
+        return lib().rsx_crw_decompress(self._h, C.byref(d), C.c_void_p(in_ptr), in_bytes,
+                                        C.c_void_p(low_ptr or 0), low_bytes or 0,
+                                        C.byref(img_view))
+
     def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
         """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
         tiles' zlib streams.  Returns (status, per-tile statuses)."""
@@ -858,6 +888,10 @@ class Context:
         are copied at plan creation)"""
         return Plan(self, "rsx_kodak_plan_create", abi.KodakJob, jobs)
 
+    def crw_plan(self, jobs):
+        """jobs: abi.CrwJob, one per frame (geometries and tables may mix)"""
+        return CrwPlan(self, "rsx_crw_plan_create", abi.CrwJob, jobs)
+
     def dng_jpeg_plan(self, jobs):
         """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""
         return DngJpegPlan(self, "rsx_dng_jpeg_plan_create", abi.DngJpegJob, jobs)
@@ -993,6 +1027,17 @@ class PanasonicV4Plan(Plan):
         st = lib().rsx_panasonic_v4_plan_bad_pixels(self._h, job, bad.ctypes.data if cap else None,
                                                     cap, C.byref(n))
         return st, n.value, (bad[:n.value].copy() if st == abi.RSX_OK else None)
+
+
+class CrwPlan(Plan):
+    def stats(self, job):
+        """after results(): (windows, inner rounds, outer rounds used, settling work) of job
+        `job` of the last run"""
+        v = (C.c_uint32 * 4)()
+        rc = lib().rsx_crw_plan_stats(self._h, job, v)
+        if rc != abi.RSX_OK:
+            raise RsxError(rc, "rsx_crw_plan_stats")
+        return tuple(int(x) for x in v)
 
 
 class Vc5Plan(Plan):

@@ -18,6 +18,8 @@
 #include "rsx_olympus_core.h"
 #include "rsx_kodak.h"
 #include "rsx_kodak_core.h"
+#include "rsx_crw.h"
+#include "rsx_crw_core.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
@@ -501,6 +503,11 @@ extern "C" int rsx_ctx_create(int device, rsx_ctx** out_ctx) {
   // (read once per context, not per call: RSX_HOST_NO_OVERLAP=1 keeps large host-pointer
   // calls of the unpack family in one piece -- what the tests compare the banded path with)
   ctx->host_overlap = getenv("RSX_HOST_NO_OVERLAP") == nullptr;
+  // (likewise once per context: the launches of crw_parse_kernel behind a CRW plan's first pass;
+  // 0 leaves every window behind the first to the settling kernel; at most 32, so that a timed
+  // run's 9 + rounds launches fit the KernelTimer's 48 marks)
+  if (const char* e = getenv("RSX_CRW_SPEC_ROUNDS"))
+    ctx->crw_spec_rounds = uint32_t(std::min(std::max(atoi(e), 0), 32));
   if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
     delete ctx;
     return RSX_ERR_DEVICE;
@@ -4100,6 +4107,71 @@ extern "C" int rsx_kodak_decompress(rsx_ctx* ctx, const rsx_kodak_desc* desc, co
     return kodak_plan_set_table(plan->dec.get(), 0, desc, s);
   };
   return single_image_host(ctx, key, rsx_kodak_plan_create, job, in, span, img, nullptr, hooks);
+}
+
+// ---------------------------------------------------------------------------
+// CrwDecompressor
+// ---------------------------------------------------------------------------
+extern "C" int rsx_crw_validate(const rsx_crw_desc* desc, const rsx_image* img, size_t in_bytes,
+                                size_t low_bytes) {
+  return rsx_crw::validate(desc, img, in_bytes, low_bytes);
+}
+
+extern "C" int rsx_crw_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_crw_job* jobs,
+                                   rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, crw_plan_create);
+}
+
+extern "C" int rsx_crw_plan_stats(rsx_plan* plan, int job, uint32_t stats[4]) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return crw_plan_stats(d, job, stats); });
+}
+
+// Device pointers: a plan of the call's own runs on them (the scan and the low bits are two
+// ranges from the lower of the two addresses), on the context's stream behind the null stream's
+// work so far, and the call returns when it is done.  Host pointers (single_image_host): the
+// bytes the image can consume and the low bits it needs go up as one copy, the low bits behind
+// the scan; the plan is keyed by the geometry, those sizes, the table number and the flag.
+extern "C" int rsx_crw_decompress(rsx_ctx* ctx, const rsx_crw_desc* desc, const uint8_t* in,
+                                  size_t in_bytes, const uint8_t* low, size_t low_bytes,
+                                  const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data || !desc || (desc->has_lowbits && !low))
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_crw::validate(desc, img, in_bytes, low_bytes))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool with_low = desc->has_lowbits != 0;
+  const bool in_dev = is_device_pointer(in), out_dev = is_device_pointer(img->data);
+  if (in_dev != out_dev || (with_low && is_device_pointer(low) != in_dev))
+    return RSX_ERR_INVALID_ARG;
+  const size_t span =
+      size_t(std::min<uint64_t>(in_bytes, rsx_crw::image_bound(img->dim_x, img->dim_y)));
+  const size_t low_need = with_low ? size_t(img->dim_x) * size_t(img->dim_y) / 4 : 0;
+  rsx_crw_job job;
+  one_job_init(job, span, img);
+  job.desc.dec_table = desc->dec_table;
+  job.desc.has_lowbits = with_low ? 1u : 0u;
+  job.low_bytes = low_need;
+  if (in_dev) {
+    const uint8_t* base = with_low && low < in ? low : in;
+    job.in_offset = uint64_t(in - base);
+    job.low_offset = with_low ? uint64_t(low - base) : 0;
+    CallPlan call;
+    if (int st = rsx_crw_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    return call.run(base, img->data, nullptr);
+  }
+  job.low_offset = (span + 15) / 16 * 16;
+  std::vector<uint8_t> key = one_job_key(rsx_crw_plan_create, job);
+  if (!with_low)
+    return single_image_host(ctx, key, rsx_crw_plan_create, job, in, span, img, nullptr);
+  std::vector<uint8_t> both(size_t(job.low_offset) + low_need);
+  std::memcpy(both.data(), in, span);
+  std::memcpy(both.data() + job.low_offset, low, low_need);
+  return single_image_host(ctx, key, rsx_crw_plan_create, job, both.data(), both.size(), img,
+                           nullptr);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

@@ -304,6 +304,7 @@ struct rsx_ctx {
   std::atomic<uint64_t> host_calls{0}; // host-pointer entry points served
   std::atomic<uint64_t> chunked_calls{0}; // ... of which ran one large stream in chunks
   bool host_overlap = true;            // large unpack-family host calls run in row bands
+  uint32_t crw_spec_rounds = 4;        // CRW plans: speculative rounds over the windows (rsx_crw.hip)
   std::mutex upload_mu, download_mu;   // LJPEG-family host calls: one copy per direction at a time
   // The single-pass LJPEG kernel takes a workgroup's place in its stream's order from its
   // block index (rsx_ljpeg_fast.hip): safe while the dispatcher starts one grid's workgroups

@@ -1180,3 +1180,113 @@ size_t rsx_synth_kodak_encode(int w, int h, const uint16_t* target, uint8_t* out
   }
   return pos;
 }
+
+/* ------------------------------------------------------------------------ */
+/* Canon CRW (CrwDecompressor.cpp:167-286): blocks of 64 differences, the    */
+/* first tree for coefficient 0 (a running sum over the frame's blocks), the */
+/* second for run << 4 | len behind it, f0 for sixteen zeros, 00 behind the  */
+/* last coefficient that is not zero; JPEG-stuffed.  `target` holds the      */
+/* 10-bit values (0..1023); every difference gets the shortest length.       */
+/* ------------------------------------------------------------------------ */
+#include "../rsx_crw_tables.h"
+
+typedef struct {
+  uint8_t* out;
+  size_t cap, pos;
+  uint32_t acc;
+  int held;
+  int overflow;
+} crw_bits;
+
+static void crw_put(crw_bits* b, uint32_t v, int n) {
+  for (int k = n - 1; k >= 0; --k) {
+    b->acc = (b->acc << 1) | ((v >> k) & 1u);
+    if (++b->held == 8) {
+      const uint8_t byte = (uint8_t)b->acc;
+      if (b->pos + 2 > b->cap) {
+        b->overflow = 1;
+      } else {
+        b->out[b->pos++] = byte;
+        if (byte == 0xFF)
+          b->out[b->pos++] = 0;
+      }
+      b->acc = 0;
+      b->held = 0;
+    }
+  }
+}
+
+/* the first code of the tree whose value is cv */
+static int crw_code(const uint8_t* ncpl, const uint8_t* values, uint32_t cv, uint32_t* code) {
+  uint32_t c = 0, at = 0;
+  for (int len = 1; len <= 16; ++len) {
+    for (int k = 0; k < ncpl[len - 1]; ++k, ++c, ++at)
+      if (values[at] == cv) {
+        *code = c;
+        return len;
+      }
+    c <<= 1;
+  }
+  return 0;
+}
+
+size_t rsx_synth_crw_encode(int w, int h, int table, const uint16_t* target, uint8_t* out,
+                            size_t cap) {
+  if (w <= 0 || h <= 0 || (w & 3) || ((size_t)w * (size_t)h) % 64 || table < 0 || table > 2)
+    return 0;
+  uint32_t code[2][256];
+  uint8_t len[2][256];
+  for (int cv = 0; cv < 256; ++cv) {
+    len[0][cv] = (uint8_t)crw_code(RSX_CRW_FIRST_NCPL[table], RSX_CRW_FIRST_VALUES[table], (uint32_t)cv,
+                                   &code[0][cv]);
+    len[1][cv] = (uint8_t)crw_code(RSX_CRW_SECOND_NCPL[table], RSX_CRW_SECOND_VALUES[table], (uint32_t)cv,
+                                   &code[1][cv]);
+  }
+  crw_bits bw = {out, cap, 0, 0, 0, 0};
+  const size_t n_blocks = (size_t)w * (size_t)h / 64;
+  int32_t carry = 0;
+  for (size_t b = 0; b < n_blocks; ++b) {
+    int32_t d[64];
+    for (int k = 0; k < 64; ++k) {
+      const size_t p = 64 * b + (size_t)k, col = p % (size_t)w;
+      const int32_t pred = col < 2 ? 512 : (int32_t)target[p - 2];
+      d[k] = (int32_t)target[p] - pred;
+    }
+    const int32_t first = d[0];
+    d[0] -= carry;
+    carry = first;
+    int last = 0;
+    for (int k = 1; k < 64; ++k)
+      if (d[k])
+        last = k;
+    for (int i = 0; i <= last;) {
+      int run = 0;
+      if (i > 0) {
+        while (d[i + run] == 0)
+          ++run;
+        while (run >= 16) {
+          crw_put(&bw, code[1][0xF0], len[1][0xF0]);
+          run -= 16;
+          i += 16;
+        }
+      }
+      const int32_t v = d[i + run];
+      const uint32_t a = (uint32_t)(v < 0 ? -v : v);
+      int n = 0;
+      while (a >> n)
+        ++n;
+      const uint32_t cv = (uint32_t)(run << 4 | n);
+      const int tree = i > 0;
+      if (n > (tree ? 10 : 11) || len[tree][cv] == 0)
+        return 0;
+      crw_put(&bw, code[tree][cv], len[tree][cv]);
+      crw_put(&bw, (uint32_t)(v >= 0 ? v : v + (1 << n) - 1), n);
+      i += run + 1;
+    }
+    if (last < 63)
+      crw_put(&bw, code[1][0x00], len[1][0x00]);
+  }
+  if (bw.held)
+    crw_put(&bw, 0, 8 - bw.held);
+  return bw.overflow ? 0 : bw.pos;
+}

@@ -299,6 +299,21 @@ inline int kodak(const ByteStream& input, const RawImage& img, int bps, const Ta
   return rsx_kodak_decompress(rsx, &d, in.begin(), in.getSize(), &v);
 }
 
+// CrwDecompressor::decompress(): `input` is the scan behind the 514 bytes
+// CrwDecoder skips, `low` the low-bit array the constructor cropped (NULL when the camera has none)
+inline int crw(const Array1DRef<const uint8_t>& input, const Array1DRef<const uint8_t>* low,
+               const RawImage& img, uint32_t dec_table) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  rsx_crw_desc d{};
+  d.dec_table = dec_table;
+  d.has_lowbits = low ? 1u : 0u;
+  const rsx_image v = view(img);
+  return rsx_crw_decompress(rsx, &d, input.begin(), size_t(input.size()), low ? low->begin() : nullptr,
+                            low ? size_t(low->size()) : 0, &v);
+}
+
 // DngDecoder::decodeRawInternal() / handleMetadata(): what follows the tiles --
 // OpcodeList1 and the LinearizationTable look-up -- handed to the tile fan-out so that it runs on
 // the device in front of the ONE download.  The hunk fills this BEFORE decodeData (the entries,

@@ -76,6 +76,9 @@ def lib():
         _lib.rsx_synth_kodak_encode.restype = C.c_size_t
         _lib.rsx_synth_kodak_encode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_size_t]
+        _lib.rsx_synth_crw_encode.restype = C.c_size_t
+        _lib.rsx_synth_crw_encode.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_size_t]
     return _lib
 
 
@@ -390,6 +393,20 @@ def kodak_encode(target):
     n = lib().rsx_synth_kodak_encode(w, h, target.ctypes.data, out.ctypes.data, cap)
     if n == 0:
         raise ValueError("Kodak encode failed")
+    return out[:n].tobytes()
+
+
+def crw_encode(target, table=0):
+    """The Canon CRW scan (CrwDecompressor.cpp:167-286) that decodes, without low bits, to
+    `target`: (h, w) uint16 of 10-bit values with w a multiple of 4 and w h of 64; every
+    difference with the shortest length."""
+    target = np.ascontiguousarray(target, dtype=np.uint16)
+    h, w = target.shape
+    cap = target.size * 8 + 64  # (at most 31 bits a coefficient, every byte stuffed)
+    out = np.empty(cap, dtype=np.uint8)
+    n = lib().rsx_synth_crw_encode(w, h, table, target.ctypes.data, out.ctypes.data, cap)
+    if n == 0:
+        raise ValueError("CRW encode failed")
     return out[:n].tobytes()
 
 
