@@ -1,7 +1,9 @@
 """Records tests/golden/dng_jpeg_ref.json and tests/golden/dng_jpeg_bench_tile.json: JPEG streams
 written by Pillow's encoder (libjpeg-turbo) and the SHA-256 of what Pillow's decoder -- libjpeg-
 turbo with every default left alone, as JpegDecompressor leaves them -- makes of each.  Damaged and
-forged streams carry Pillow's outcome: an exception, or the hash of what it returned.
+forged streams carry Pillow's outcome: an exception, or the hash of what it returned.  The long and
+wide streams (long_wide_cases, long_damaged_cases) come last in their lists, so that the entries in
+front of them stay as they were.
 
     python scripts/record_dng_jpeg_ref.py
 
@@ -148,6 +150,92 @@ def damaged_cases(cases):
     return out
 
 
+def _segments(s):
+    """[(start, end)] of a stream's entropy segments"""
+    return [(a, b) for _, _, a, b in J.segments(s, J.parse_header(s))]
+
+
+def _stuffed(s, a, b):
+    """offsets of the FF of every stuffed FF 00 pair in bytes [a, b) of s"""
+    return [i for i in range(a, b - 1) if s[i] == 0xFF and s[i + 1] == 0]
+
+
+def long_wide_cases():
+    """Streams past one byte window (8192 bytes in LDS, reloaded every 4096) and tiles past one
+    finish workgroup (1024 samples of a row) of rsx_dng_jpeg.hip.  Every property the tests rely on
+    is asserted here: a re-recording cannot quietly lose it."""
+    out = []
+
+    def add(name, img, cpp, **kw):
+        s = encode(img, **kw)
+        e = entry(name, s, cpp)
+        assert e["sha256"] is not None and (e["width"], e["height"]) == img.size, name
+        out.append(e)
+        return s
+
+    rng = np.random.default_rng(9601)
+    grey = Image.fromarray(rng.integers(0, 256, (96, 96), dtype=np.uint8), "L")
+    s = add("long_grey_96x96", grey, 1, quality=100)
+    (a, b), = _segments(s)
+    assert b - a >= 3 * 4096
+    assert _stuffed(s, a, a + 4096) and _stuffed(s, a + 8192, b)
+    # (noise in all three components: RGB noise leaves the chroma planes half as loud)
+    ycc = Image.fromarray(np.random.default_rng(6401).integers(0, 256, (64, 64, 3), dtype=np.uint8), "YCbCr")
+    s = add("long_420_64x64", ycc, 3, quality=100, subsampling=2)
+    (a, b), = _segments(s)
+    assert b - a > 8192
+    s = add("long_restart_grey_96x96", grey, 1, quality=100, restart_marker_blocks=60)
+    later = [b - a for a, b in _segments(s)[1:]]
+    assert any(n > 4096 for n in later) and any(n < 4096 for n in later), later
+    for name, w, h, cpp, kw in (("wide_grey_2064x8", 2064, 8, 1, {}),
+                                ("wide_444_704x8", 704, 8, 3, dict(subsampling=0)),
+                                ("wide_422_704x8", 704, 8, 3, dict(subsampling=1)),
+                                ("wide_420_704x16", 704, 16, 3, dict(subsampling=2))):
+        s = add(name, picture(200 + len(out), w, h, cpp), cpp, quality=75, **kw)
+        assert w * cpp > 2048 and len(s) < 4096, (name, len(s))
+    return out
+
+
+FILL_RUNS = (1, 4095, 4096, 4097, 8192, 9000)
+
+
+def long_damaged_cases(cases):
+    """long_grey_96x96 cut inside its second and its last window's worth of bytes (with and without
+    an EOI behind the cut: only the first gets past the host's marker scan to the kernel), and runs
+    of fill bytes in front of a stuffed FF 00 pair, which libjpeg skips: those decode to the base's
+    image.  Already as edits of the base (`repeat`: a byte and a count in front of `insert`)."""
+    base = "long_grey_96x96"
+    c = next(e for e in cases if e["name"] == base)
+    s = base64.b64decode(c["stream"])
+    (a, b), = _segments(s)
+    out = []
+
+    def add(kind, head, insert, tail, **extra):
+        rep = extra.get("repeat", (0, 0))
+        t = s[:head] + bytes([rep[0]]) * rep[1] + insert + s[len(s) - tail:]
+        e = entry("%s/%s" % (base, kind), t, 1, base=base)
+        del e["stream"]
+        e.update(head=head, insert=insert.hex(), tail=tail, **extra)
+        out.append(e)
+        return e
+
+    assert a + 4096 < 6000 < a + 8192 and b - 4096 < 12000 < b
+    for at in (6000, 12000):
+        assert s[at - 1] != 0xFF
+        assert add("cut_at_%d" % at, at, b"", 0)["sha256"] is None
+        add("cut_at_%d_eoi_kept" % at, at, b"\xff\xd9", 0)
+        assert J.model_decode(s[:at] + b"\xff\xd9", 1)[0] == J.OVERFLOW
+    add("cut_one_byte_before_eoi", len(s) - 3, b"", 0)
+    first = next(i for i in _stuffed(s, a, b) if i - a >= 16)
+    beyond = _stuffed(s, a + 8192 + 1, b)[0]
+    assert first - a < 4096
+    for where, at in (("first_window", first), ("past_8192", beyond)):
+        for n in FILL_RUNS:
+            e = add("fill_%d_%s" % (n, where), at, b"", len(s) - at, repeat=[255, n])
+            assert e["sha256"] == c["sha256"], e["name"]  # (libjpeg skipped the fill bytes)
+    return out
+
+
 def forged_cases():
     """Coefficients no encoder makes from 8-bit pixels, by raising quantisers of a quality-100
     stream (all ones): `moderate` leaves the sample range by more than 512 (where libjpeg's masked
@@ -172,7 +260,8 @@ def forged_cases():
 
 def as_edit(e, by):
     """a damaged stream as an edit of its base: the base's first `head` bytes, `insert` (hex), the
-    base's last `tail` bytes -- what tests/dng_jpeg_files.py puts together again"""
+    base's last `tail` bytes -- what tests/dng_jpeg_files.py puts together again (it also knows
+    `repeat`, a byte and a count in front of `insert`: long_damaged_cases)"""
     s, b = base64.b64decode(e.pop("stream")), by[e["base"]]
     head = next((i for i in range(min(len(s), len(b))) if s[i] != b[i]), min(len(s), len(b)))
     tail = 0
@@ -187,9 +276,11 @@ def main():
     cases = base_cases()
     import PIL
     by = {e["name"]: base64.b64decode(e["stream"]) for e in cases}
+    damaged = [as_edit(e, by) for e in damaged_cases(cases)]
+    cases += long_wide_cases()  # (behind everything older: those entries stay as they are)
+    damaged += long_damaged_cases(cases)
     doc = dict(pillow=PIL.__version__, libjpeg_turbo=features.version("libjpeg_turbo"),
-               cases=cases, damaged=[as_edit(e, by) for e in damaged_cases(cases)],
-               forged=forged_cases())
+               cases=cases, damaged=damaged, forged=forged_cases())
     path = os.path.join(ROOT, "tests", "golden", "dng_jpeg_ref.json")
     with open(path, "w") as f:  # (an entry a line)
         f.write("{")
@@ -209,6 +300,7 @@ def main():
     with open(os.path.join(ROOT, "tests", "golden", "dng_jpeg_bench_tile.json"), "w") as f:
         json.dump(tile, f, sort_keys=True)
         f.write("\n")
+    assert os.path.getsize(path) < 160000
     print(path, os.path.getsize(path), "bytes;", len(cases), "cases,", len(doc["damaged"]), "damaged;",
           "bench tile", len(s), "bytes")
     for e in doc["forged"]:

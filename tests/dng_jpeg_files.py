@@ -33,7 +33,9 @@ def golden():
         by = {c["name"]: c["stream"] for c in _golden["cases"]}
         for c in _golden["damaged"]:  # (kept as an edit of its base)
             b = by[c["base"]]
-            c["stream"] = b[:c["head"]] + bytes.fromhex(c["insert"]) + b[len(b) - c["tail"]:]
+            byte, count = c.get("repeat", (0, 0))  # (a run of one byte in front of `insert`)
+            c["stream"] = b[:c["head"]] + bytes([byte]) * count + bytes.fromhex(c["insert"]) + \
+                b[len(b) - c["tail"]:]
     return _golden
 
 

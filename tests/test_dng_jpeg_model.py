@@ -57,6 +57,53 @@ def test_the_damaged_set_holds_both_outcomes():
     assert {J.BAD_CODE, J.RESTART, J.OVERFLOW, J.IO} <= set(verdicts)
 
 
+def _segment_bounds(name):
+    s = J.case(name)["stream"]
+    return s, [(a, b) for _, _, a, b in J.segments(s, J.parse_header(s))]
+
+
+def test_the_long_and_wide_fixtures_are_what_the_device_tests_take_them_for():
+    """rsx_dng_jpeg.hip keeps 8192 bytes of a segment in LDS and reloads them once the walk is more
+    than 4096 past their first; a workgroup of its finish kernel covers 1024 samples of a row.  The
+    device tests cannot see a reload or a workgroup index: what makes them reach both is here."""
+    s, ((a, b),) = _segment_bounds("long_grey_96x96")
+    assert b - a >= 3 * 4096
+    stuffed = [i - a for i in range(a, b - 1) if s[i] == 0xFF and s[i + 1] == 0]
+    assert any(i < 4096 for i in stuffed) and any(i > 8192 for i in stuffed)
+    _, ((a, b),) = _segment_bounds("long_420_64x64")
+    assert b - a > 8192 and J.case("long_420_64x64")["cpp"] == 3
+    _, segs = _segment_bounds("long_restart_grey_96x96")
+    later = [b - a for a, b in segs[1:]]  # (they start deep inside the tile)
+    assert max(later) > 4096 and min(later) < 4096 and segs[1][0] > 4096
+    for name, samples in (("wide_grey_2064x8", 2064), ("wide_444_704x8", 2112),
+                          ("wide_422_704x8", 2112), ("wide_420_704x16", 2112)):
+        c = J.case(name)
+        assert c["width"] * c["cpp"] == samples > 2 * 1024  # three workgroups a row
+    H = J.parse_header(J.case("wide_422_704x8")["stream"])
+    assert (H["hs"], H["vs"]) == (2, 1)
+    H = J.parse_header(J.case("wide_420_704x16")["stream"])
+    assert (H["hs"], H["vs"]) == (2, 2)
+    # the fill runs: in front of a stuffed pair of the base, inside the first window and past 8192
+    s, ((a, b),) = _segment_bounds("long_grey_96x96")
+    fills = [c for c in J.damaged() if "repeat" in c]
+    assert sorted((c["repeat"][1], c["head"] - a < 4096) for c in fills) == \
+        sorted((n, near) for n in (1, 4095, 4096, 4097, 8192, 9000) for near in (True, False))
+    for c in fills:
+        at = c["head"]
+        assert c["base"] == "long_grey_96x96" and c["repeat"][0] == 0xFF and s[at:at + 2] == b"\xff\x00"
+        assert 16 <= at - a < 4096 or 8192 < at - a < b - a
+        assert c["stream"] == s[:at] + b"\xff" * c["repeat"][1] + s[at:]
+        assert c["sha256"] == J.case("long_grey_96x96")["sha256"]
+    # the cuts: inside the second and the last 4096 bytes of the segment, and in front of EOI
+    cuts = {c["name"].split("/")[1]: c for c in J.damaged() if c["name"].startswith("long_grey_96x96/cut")}
+    assert a + 4096 < cuts["cut_at_6000"]["head"] < a + 8192
+    assert b - 4096 < cuts["cut_at_12000"]["head"] < b
+    assert cuts["cut_one_byte_before_eoi"]["stream"] == s[:-3]
+    for k in ("cut_at_6000_eoi_kept", "cut_at_12000_eoi_kept"):  # (these reach the kernel)
+        assert cuts[k]["stream"][-2:] == b"\xff\xd9"
+        assert J.model_decode(cuts[k]["stream"], 1)[0] == J.OVERFLOW
+
+
 def test_the_overshoot_fork():
     """the range limit saturates (libjpeg-turbo's SIMD code), it is not libjpeg's masked table;
     coefficients that leave 16 bits are refused"""
