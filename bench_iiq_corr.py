@@ -12,6 +12,16 @@ quadrant curves.  Not part of bench.py.  One JSON line:
                columns keep a start value every 32; before that, width - 1)
   host         rsx_phase_one_decompress_corrected against rsx_phase_one_decompress alone on the
                same frame through host pointers: what the corrections add before the one download
+  defects      the same list with a sensor-defects op (RSX_IIQ_OP_SENSOR_DEFECTS): 16 bad columns
+               scattered over the frame in front of and behind the flat fields, and a chain of 8
+               adjacent columns (8 dependent launches).  Whole plan runs between two events, no
+               per-kernel timing, the variants alternating inside every repeat; `added_us` is the
+               median over the repeats of (variant - the same repeat's list without the op).  Next
+               to it iiq_bad_columns_kernel's own time from a timed run, and the host build of the
+               core on one thread for the op alone.  The front-16 list is compared bit for bit
+               with the host build.
+  host         ... and, with the op in front, rsx_phase_one_decompress_corrected with and without
+               it, alternating
   reference    where oracle/_ref is built: the unmodified reference's whole-file decode with the
                correction block minus the one without, same process, one thread (its loops have
                no threads) -- luma + quadrant only, because its chroma needs a CFA that a decode
@@ -123,6 +133,74 @@ def device_leg(ctx, torch, abi, K, img, args):
             "pixels_changed_frac": round(changed, 4), "bit_exact": bool(exact)}, dev, s, want
 
 
+def scattered_columns(n=16):
+    return [int(c) | 1 for c in np.linspace(100, W - 100, n)]
+
+
+def defects_leg(ctx, torch, abi, K, D, dev, s, img, args):
+    from rawspeed_amd import build
+    base = make_ops(K, args.cell, args.cell)
+    far = ("defects", D.columns(scattered_columns()))
+    chain = ("defects", D.columns(list(range(5001, 5009))))
+    variants = {"list": base, "front16": [far] + base, "back16": base + [far], "chain8": [chain] + base}
+    plans, keeps = {}, []
+    for name, ops in variants.items():
+        job, keep = job_for(abi, ops)
+        keeps.append(keep)
+        plans[name] = (ctx.iiq_correct_plan([job]), job)
+    # the front-16 list against the host build of the core, bit for bit
+    dev.copy_(torch.from_numpy(img.reshape(-1).view(np.uint8)))
+    plans["front16"][0].run(dev.data_ptr(), dev.data_ptr(), s)
+    rc, _, _ = plans["front16"][0].results()
+    got = dev.cpu().numpy().view(np.uint16).reshape(H, W)
+    L = C.CDLL(build.build_iiq_corr_host()[0])
+    L.rsx_iiq_corr_host_apply.argtypes = [C.c_void_p, C.c_void_p]
+    want = img.copy()
+    st = L.rsx_iiq_corr_host_apply(C.byref(plans["front16"][1].corr), C.byref(abi.Image(want.ctypes.data, 2 * W, W, H, 1, 1)))
+    exact = rc == 0 and st == 0 and np.array_equal(got, want)
+    # the op alone on the host, one thread
+    alone, keep = job_for(abi, [far])
+    scratch = img.copy()
+    host_ms = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        L.rsx_iiq_corr_host_apply(C.byref(alone.corr), C.byref(abi.Image(scratch.ctypes.data, 2 * W, W, H, 1, 1)))
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    # whole runs on a stream of their own (a plan run on the null stream goes to the context's
+    # stream, where these events would not see it), the variants alternating inside a repeat
+    own = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for plan, _ in plans.values():
+        for _ in range(3):
+            plan.run(dev.data_ptr(), dev.data_ptr(), own.cuda_stream)
+    own.synchronize()
+    per = {k: [] for k in plans}
+    for _ in range(args.repeats):
+        for name, (plan, _) in plans.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(own)
+            for _ in range(args.steps):
+                plan.run(dev.data_ptr(), dev.data_ptr(), own.cuda_stream)
+            e1.record(own)
+            e1.synchronize()
+            per[name].append(e0.elapsed_time(e1) / args.steps * 1e3)
+    out = {"columns": {"front16": scattered_columns(), "chain8": [5001, 5008]},
+           "run_us": {k: round(float(np.median(v)), 2) for k, v in per.items()},
+           "run_us_all": {k: [round(x, 2) for x in v] for k, v in per.items()},
+           "added_us": {k: round(float(np.median(np.array(per[k]) - np.array(per["list"]))), 2)
+                        for k in per if k != "list"},
+           "host_core_1t_op_alone_ms": round(float(np.median(host_ms)), 4),
+           "bit_exact": bool(exact)}
+    kernel = {}
+    for name in ("front16", "chain8"):
+        med, _ = timed(plans[name][0], dev.data_ptr(), s, args.steps, 3)
+        kernel[name] = round(med.get("iiq_bad_columns_kernel", 0.0) * 1e3, 2)
+    out["bad_columns_kernel_us_per_run"] = kernel
+    for plan, _ in plans.values():
+        plan.close()
+    return out, want
+
+
 def sweep_leg(ctx, abi, K, dev, s, args):
     out = {}
     for cw in (8, 32, 128, 512):
@@ -136,7 +214,7 @@ def sweep_leg(ctx, abi, K, dev, s, args):
     return out
 
 
-def host_leg(ctx, abi, K, F, img, want, args, reps=3):
+def host_leg(ctx, abi, K, F, img, want, args, reps=3, D=None, want_defects=None):
     from oracle_lib import HostImage
     rows = F.encode(img, 1)
     raw = np.frombuffer(b"".join(rows), np.uint8)
@@ -163,8 +241,25 @@ def host_leg(ctx, abi, K, F, img, want, args, reps=3):
         corrected = dt if corrected is None else min(corrected, dt)
         ok &= st == 0
     ok &= np.array_equal(out.pixels(), want)
-    return {"phase_one_decompress_ms": round(plain, 2), "decompress_corrected_ms": round(corrected, 2),
-            "corrections_add_ms": round(corrected - plain, 2), "in_bytes": int(raw.size)}, ok
+    res = {"phase_one_decompress_ms": round(plain, 2), "decompress_corrected_ms": round(corrected, 2),
+           "corrections_add_ms": round(corrected - plain, 2), "in_bytes": int(raw.size)}
+    if D is not None:
+        # the list with 16 scattered bad columns in front, and without, alternating
+        d2, keep2 = abi.iiq_corr([("defects", D.columns(scattered_columns()))] + ops, GRBG)
+        t = {"without": [], "with": []}
+        for _ in range(2 * reps):
+            for name, desc, expect in (("without", d, want), ("with", d2, want_defects)):
+                t0 = time.perf_counter()
+                st, _ = ctx.phase_one_decompress_corrected(raw, strips, desc, out.view())
+                t[name].append((time.perf_counter() - t0) * 1e3)
+                ok &= st == 0
+                if len(t[name]) == 1:
+                    ok &= np.array_equal(out.pixels(), expect)
+        res["corrected_ms_all"] = {k: [round(x, 2) for x in v] for k, v in t.items()}
+        res["corrected_with_defects_ms"] = round(float(np.median(t["with"])), 2)
+        res["corrected_without_defects_ms"] = round(float(np.median(t["without"])), 2)
+        res["defects_add_ms"] = round(float(np.median(np.array(t["with"]) - np.array(t["without"]))), 3)
+    return res, ok
 
 
 def ref_leg(K, img, args, reps=2):
@@ -202,6 +297,7 @@ def main():
     args = ap.parse_args()
     import torch
     import iiq_corr_files as K
+    import iiq_defect_files as D
     import iiq_files as F
     from rawspeed_amd import abi, capi
     ctx = capi.Context(0)
@@ -210,10 +306,11 @@ def main():
            "note": "cell sizes of real camera files are not known here; see cell_sweep"}
     res["device"], dev, s, want = device_leg(ctx, torch, abi, K, img, args)
     res["cell_sweep"] = sweep_leg(ctx, abi, K, dev, s, args)
-    exact = res["device"]["bit_exact"]
+    res["defects"], want_defects = defects_leg(ctx, torch, abi, K, D, dev, s, img, args)
+    exact = res["device"]["bit_exact"] and res["defects"]["bit_exact"]
     del dev
     if not args.no_host:
-        res["host"], ok = host_leg(ctx, abi, K, F, img, want, args)
+        res["host"], ok = host_leg(ctx, abi, K, F, img, want, args, D=D, want_defects=want_defects)
         exact &= ok
     if not args.no_ref:
         res["reference"] = ref_leg(K, img, args)

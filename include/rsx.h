@@ -762,15 +762,18 @@ int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc, con
                               size_t in_bytes, const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
-/* 3n. IiqDecoder::CorrectPhaseOneC: flat field and quadrant curves          */
+/* 3n. IiqDecoder::CorrectPhaseOneC: flat field, quadrant curves, defects    */
 /*    replaces the pixel passes of PhaseOneFlatField (decoders/IiqDecoder    */
 /*    .cpp:410-479) and CorrectQuadrantMultipliersCombined (:335-405) behind */
 /*    PhaseOneDecompressor::decompress().  IiqDecoder keeps the parse of the */
 /*    correction block (:280-325), the spline (Spline<>::calculateCurve, its */
-/*    checks included), the defect list and correctBadColumn (which reads    */
-/*    neighbouring pixels).  The image is uint16, cpp 1.  Every operation    */
-/*    reads and writes only the pixel it stands on, so a list of them, in    */
-/*    file order, is ONE pass on the device: each pixel gets the whole list. */
+/*    checks included) and mBadPixelPositions.  The image is uint16,         */
+/*    cpp 1.  A flat field and the curves read and write only the pixel they */
+/*    stand on, so a run of them, in file order, is ONE pass on the device:  */
+/*    each pixel gets the whole run.  The sensor defects (entry 0x400) read  */
+/*    neighbouring columns: such an op ends a run, runs as a launch over     */
+/*    (record, row) of its own on the same stream, and the ops behind it are */
+/*    the next run.                                                          */
 /*    RSX_IIQ_OP_FLAT_FIELD: `payload` is the entry's bytes as they are in   */
 /*    the file; nc = 2 (luma, entry 0x410) or 4 (`chroma`, entry 0x40b).     */
 /*    head[0..7] = eight little-endian u16.  Any of head[2..5] zero: the op  */
@@ -795,9 +798,35 @@ int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc, con
 /*    [quadRow][quadCol]; quadRow = row >= split_row, quadCol = col >=       */
 /*    split_col; diff = pixel < black_level ? pixel : uint16(black_level);   */
 /*    pixel = uint16(curve[pixel - diff] + diff).                            */
+/*    RSX_IIQ_OP_SENSOR_DEFECTS (correctSensorDefects, :499-576): `payload`  */
+/*    / `payload_bytes` are the bytes of entry 0x400 as the file has them:   */
+/*    8-byte records of little-endian u16 col, row, type and 2 ignored       */
+/*    bytes.  Ops apply in list order: a defects op sees the image as the    */
+/*    ops in front of it left it, the ops behind it see its result.  Records */
+/*    apply in file order.  A record with col >= dim_x is skipped whatever   */
+/*    its type; type 129 (a bad pixel) touches no pixel -- its position goes */
+/*    to mBadPixelPositions, see rsx_iiq_defect_positions; any type other    */
+/*    than 131 / 137 does nothing.  Type 131 / 137 (a bad column): for row   */
+/*    in 2 .. dim_y - 3, colour = cfa[(col mod cfa_w) + (row mod cfa_h)      */
+/*    cfa_w] -- getColorAt(col, row), NOT the transposed look-up of chroma.  */
+/*    Green (1): val[0..3] = the pixels at (row - 1, col - 1), (row + 1,     */
+/*    col - 1), (row - 1, col + 1), (row + 1, col + 1), sum their total,     */
+/*    dev[i] = |4 val[i] - sum|; the FIRST largest dev is dropped (the       */
+/*    comparison is a strict <, four equal values drop val[0]): pixel =      */
+/*    (sum - val[max] + 1) / 3 in integers.  Any other colour: diags = the   */
+/*    sum of the four pixels at (row +- 2, col +- 2), horiz = the sum of the */
+/*    two at (row, col +- 2), pixel = lround(diags * 0.0732233 + horiz *     */
+/*    0.3535534) in binary64, each operation rounded on its own (at most     */
+/*    65535).  A column is written from other columns only, so the rows of a */
+/*    record are independent and records whose columns differ by more than 2 */
+/*    commute; records within 2 of each other (the same column twice         */
+/*    included) take effect in file order: the host sorts the records into   */
+/*    levels, one launch a level -- a list of columns far apart is a single  */
+/*    launch.                                                                */
 /*    rsx_iiq_correct_validate, in this order: corr or img NULL, cpp != 1,   */
 /*    dim_x or dim_y <= 0, pitch_bytes < 2 dim_x -> RSX_ERR_INVALID_ARG;     */
-/*    n_ops outside 0..16, an unknown kind, a NULL payload or curves ->      */
+/*    n_ops outside 0..16, an unknown kind (2 is not used and stays unknown),*/
+/*    a NULL payload of a flat field or NULL curves ->                       */
 /*    RSX_ERR_INVALID_ARG; then per op in list order: a payload shorter than */
 /*    16 bytes, or shorter than 16 + 2 high wide nc/2 when no head field     */
 /*    2..5 is zero -> RSX_ERR_IO (the reference throws half-way through the  */
@@ -810,7 +839,18 @@ int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc, con
 /*    (256 MiB; 1 x 1 cells over a full 11976 x 8854 frame would take 848    */
 /*    MiB, cells of 4 x 4 and up fit; cells wider than 32 columns keep a     */
 /*    start value every 32 columns on top, rows x width / 32 x nc/2 floats)  */
-/*    -> RSX_ERR_UNSUPPORTED.                                                */
+/*    -> RSX_ERR_UNSUPPORTED.  Behind all of these, the defects ops: a       */
+/*    second one in a list -> RSX_ERR_INVALID_ARG (the reference throws      */
+/*    "Second sensor defects entry seen"); payload NULL with payload_bytes > */
+/*    0 -> RSX_ERR_INVALID_ARG (payload_bytes == 0: the op does nothing);    */
+/*    payload_bytes no multiple of 8 -> RSX_ERR_IO (the reference's reader   */
+/*    throws half-way and the file fails); then the records in file order,   */
+/*    the first offender decides -- only records of type 131 / 137 with col  */
+/*    < dim_x count, and only when dim_y >= 5 (otherwise the loop has no row */
+/*    and nothing is read): cfa_w cfa_h == 0 or > 64 -> RSX_ERR_INVALID_ARG  */
+/*    ("No CFA size set"); col < 2 or col > dim_x - 3 -> RSX_ERR_UNSUPPORTED */
+/*    (the reference reads outside the row there; the host path keeps what-  */
+/*    ever it does); more than 4096 such records -> RSX_ERR_UNSUPPORTED.     */
 /*    On any status but RSX_OK the image is untouched.  n_ops == 0 is        */
 /*    RSX_OK and writes nothing; pixels outside every op's area and pitch    */
 /*    padding are never written.  Payloads and curves are copied during the  */
@@ -821,17 +861,36 @@ int rsx_nikon_snef_decompress(rsx_ctx* ctx, const rsx_nikon_snef_desc* desc, con
 /*    rsx_phase_one_decompress_corrected = rsx_phase_one_decompress, the     */
 /*    list applied to the decoded image on the device, ONE download.  A      */
 /*    failing strip or a refused list leaves the caller's image untouched.   */
+/*    rsx_iiq_defect_positions (host only): the type-129 records of an entry */
+/*    0x400 with col < dim_x, in file order, as (row << 16) + col -- what    */
+/*    handleBadPixel inserts into mBadPixelPositions; row is not checked, as */
+/*    in the reference.  Up to `cap` go to `out` (may be NULL with cap 0),   */
+/*    *n is the full count even past cap.  payload_bytes no multiple of 8 -> */
+/*    RSX_ERR_IO; payload NULL with payload_bytes > 0, out NULL with cap >   */
+/*    0, n NULL -> RSX_ERR_INVALID_ARG.                                      */
+/*    rsx_phase_one_decompress_fixed = rsx_phase_one_decompress_corrected,   */
+/*    then the stage of section 5 on the positions of the list's defects op  */
+/*    (is_cfa as img has it), in front of the ONE download.  map_out (may be */
+/*    NULL; createBadPixelMap's pitch as map_pitch, 0 allowed without        */
+/*    map_out) receives the map, result (may be NULL) the counts.  With no   */
+/*    positions (no defects op included) there is no map: map_made = 0,      */
+/*    map_out untouched, and the call is the _corrected call.  Statuses as   */
+/*    the _corrected call, then the stage's own (section 5: an image         */
+/*    dimension past 65536, a wrong map_pitch, a position at row >= dim_y);  */
+/*    on anything but RSX_OK the caller's image and map_out are untouched.   */
 /* ------------------------------------------------------------------------ */
 #define RSX_IIQ_MAX_OPS 16
 typedef enum rsx_iiq_op_kind {
   RSX_IIQ_OP_FLAT_FIELD = 0,
-  RSX_IIQ_OP_QUADRANT_CURVES = 1
+  RSX_IIQ_OP_QUADRANT_CURVES = 1,
+  /* (2 is not used: rsx_iiq_correct_validate refuses it as an unknown kind) */
+  RSX_IIQ_OP_SENSOR_DEFECTS = 3
 } rsx_iiq_op_kind;
 
 typedef struct rsx_iiq_op {
   int32_t kind;           /* rsx_iiq_op_kind */
   int32_t chroma;         /* flat field: 0 luma (0x410), 1 chroma (0x40b) */
-  const uint8_t* payload; /* flat field: the entry's bytes, head included */
+  const uint8_t* payload; /* flat field: the entry's bytes, head included; defects: entry 0x400 */
   uint32_t payload_bytes;
   uint32_t black_level;   /* quadrant curves: IiqDecoder::black_level */
   const uint16_t* curves; /* quadrant curves: 4 x 65536, [quadRow][quadCol] */
@@ -851,6 +910,13 @@ int rsx_phase_one_decompress_corrected(rsx_ctx* ctx, const uint8_t* in, size_t i
                                        int n_strips, const rsx_phase_one_strip* strips,
                                        const rsx_iiq_corr* corr, const rsx_image* img,
                                        int32_t* strip_status);
+int rsx_iiq_defect_positions(const uint8_t* payload, uint32_t payload_bytes, int32_t dim_x,
+                             uint32_t* out, uint32_t cap, uint32_t* n);
+struct rsx_bad_pixels_result; /* section 5 */
+int rsx_phase_one_decompress_fixed(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes, int n_strips,
+                                    const rsx_phase_one_strip* strips, const rsx_iiq_corr* corr,
+                                    const rsx_image* img, int32_t* strip_status, uint8_t* map_out,
+                                    uint32_t map_pitch, struct rsx_bad_pixels_result* result);
 
 /* ------------------------------------------------------------------------ */
 /* 3u. FujiDecompressor (compressed RAF)                                     */

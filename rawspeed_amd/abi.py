@@ -299,6 +299,7 @@ def vc5_desc(phase, log_table, codes, bands, prescale):
 
 RSX_IIQ_MAX_OPS = 16
 RSX_IIQ_OP_FLAT_FIELD, RSX_IIQ_OP_QUADRANT_CURVES = 0, 1
+RSX_IIQ_OP_SENSOR_DEFECTS = 3  # (2 is not used)
 
 
 class IiqOp(C.Structure):
@@ -318,8 +319,9 @@ class IiqCorrectJob(C.Structure):
 
 def iiq_corr(ops, cfa=None, n_ops=None):
     """(rsx_iiq_corr, keep-alive objects).  ops: ("ff", payload bytes, chroma[, payload_bytes]) or
-    ("quad", curves (4, 65536) uint16, split_row, split_col, black_level) or ("kind", k) for an
-    unknown kind; a payload or curves of None leaves the pointer NULL.  cfa: (cfa_w, cfa_h,
+    ("quad", curves (4, 65536) uint16, split_row, split_col, black_level) or ("defects", payload
+    bytes[, payload_bytes]) -- the bytes of entry 0x400 -- or ("kind", k) for an unknown kind; a
+    payload or curves of None leaves the pointer NULL.  cfa: (cfa_w, cfa_h,
     colours).  n_ops overrides the count (the list itself holds at most 16)."""
     d = IiqCorr()
     keep = []
@@ -339,6 +341,17 @@ def iiq_corr(ops, cfa=None, n_ops=None):
                 o.payload = a.ctypes.data
                 o.payload_bytes = len(op[1]) if len(op) < 4 else op[3]
                 keep.append(a)
+        elif op[0] == "defects":
+            o.kind = RSX_IIQ_OP_SENSOR_DEFECTS
+            if op[1] is not None:
+                a = np.frombuffer(bytes(op[1]), dtype=np.uint8).copy()
+                if a.size == 0:
+                    a = np.zeros(1, np.uint8)
+                o.payload = a.ctypes.data
+                o.payload_bytes = len(op[1])
+                keep.append(a)
+            if len(op) > 2:
+                o.payload_bytes = op[2]
         elif op[0] == "quad":
             o.kind = RSX_IIQ_OP_QUADRANT_CURVES
             if op[1] is not None:

@@ -66,7 +66,7 @@ CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_dir
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
                 "rsx_phase_one.hip", "rsx_sony_arw2.hip", "rsx_panasonic.hip", "rsx_samsung_v0.hip",
                 "rsx_panasonic_v4.hip", "rsx_dng_deflate.hip", "rsx_nikon_snef.hip", "rsx_vc5.hip",
-                "rsx_iiq_corr.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_scale.hip",
+                "rsx_iiq_corr.hip", "rsx_iiq_defects.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_scale.hip",
                 "rsx_dng_jpeg.hip", "rsx_fuji.hip", "rsx_olympus.hip", "rsx_kodak.hip",
                 "rsx_crw.hip", "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",

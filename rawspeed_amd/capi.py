@@ -39,7 +39,7 @@ EXPORTS = [
     "rsx_nikon_snef_validate", "rsx_nikon_snef_decompress", "rsx_nikon_snef_plan_create",
     "rsx_vc5_validate", "rsx_vc5_decompress", "rsx_vc5_plan_create", "rsx_vc5_plan_bands",
     "rsx_iiq_correct_validate", "rsx_iiq_correct", "rsx_phase_one_decompress_corrected",
-    "rsx_iiq_correct_plan_create",
+    "rsx_iiq_correct_plan_create", "rsx_iiq_defect_positions", "rsx_phase_one_decompress_fixed",
     "rsx_dng_post_validate", "rsx_dng_post", "rsx_dng_decompress_ljpeg_post",
     "rsx_dng_decompress_uncompressed_post", "rsx_dng_post_plan_create",
     "rsx_dng_post_plan_result", "rsx_dng_post_plan_bad_pixels",
@@ -141,6 +141,12 @@ def lib():
         L.rsx_phase_one_decompress_corrected.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                          C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p]
+        L.rsx_iiq_defect_positions.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p,
+                                               C.c_uint32, C.c_void_p]
+        L.rsx_phase_one_decompress_fixed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_uint32,
+                                                      C.c_void_p]
         L.rsx_dng_post_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32]
         L.rsx_dng_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -296,6 +302,19 @@ def iiq_correct_validate(corr, img_view):
     """rsx_iiq_correct_validate; corr: abi.IiqCorr (abi.iiq_corr), None passes a NULL list"""
     return lib().rsx_iiq_correct_validate(None if corr is None else C.byref(corr),
                                           C.byref(img_view))
+
+
+def iiq_defect_positions(payload, dim_x, cap=1 << 16, payload_bytes=None, fn=None):
+    """rsx_iiq_defect_positions on the bytes of entry 0x400 (None: a NULL payload).  Returns
+    (status, the positions that fit `cap`, the full count).  fn: the same entry point of another
+    library (the host build of the core)."""
+    a = None if payload is None else np.frombuffer(bytes(payload) + b"\0", dtype=np.uint8)
+    n_bytes = (0 if payload is None else len(payload)) if payload_bytes is None else payload_bytes
+    buf = (C.c_uint32 * max(1, cap))()
+    n = C.c_uint32(0)
+    st = (fn or lib().rsx_iiq_defect_positions)(None if a is None else a.ctypes.data, n_bytes, dim_x,
+                                                buf, cap, C.byref(n))
+    return st, [int(v) for v in buf[:min(cap, n.value)]], n.value
 
 
 def _bad_out(result, buf, st):
@@ -555,6 +574,24 @@ class Context:
         st = lib().rsx_phase_one_decompress_corrected(self._h, a.ctypes.data, a.size, len(strips),
                                                       arr, C.byref(corr), C.byref(img_view), rows)
         return st, list(rows)[:img_view.dim_y]
+
+    def phase_one_decompress_fixed(self, data, strips, corr, img_view, want_map=True):
+        """phase_one_decompress_corrected, then the bad-pixel stage on the positions of the list's
+        defects op, one download.  Returns (status, per-row statuses, abi.BadPixelsResult, the map
+        as (dim_y, map_pitch) uint8 -- None unless made)."""
+        a = _u8(data)
+        arr = abi.phase_one_strips(strips)
+        rows = (C.c_int32 * max(1, img_view.dim_y))()
+        pitch = abi.bad_pixels_map_pitch(img_view.dim_x)
+        m = np.full((max(1, img_view.dim_y), pitch), 0xA5, np.uint8)
+        r = abi.BadPixelsResult()
+        st = lib().rsx_phase_one_decompress_fixed(
+            self._h, a.ctypes.data, a.size, len(strips), arr, C.byref(corr), C.byref(img_view), rows,
+            m.ctypes.data if want_map else None, pitch if want_map else 0, C.byref(r))
+        if want_map and not (st == abi.RSX_OK and r.map_made):
+            assert (m == 0xA5).all(), "map_out was written without a map"
+        return st, list(rows)[:img_view.dim_y], r, \
+            (m if st == abi.RSX_OK and r.map_made and want_map else None)
 
     def dng_post(self, desc, img_view, bad_cap=1 << 16):
         """desc: abi.DngPostDesc; img_view.data a host or a device pointer; in place.  Returns

@@ -3198,6 +3198,35 @@ int bad_pixels_finish(const CallPlan& call, rsx_bad_pixels_result* result, uint8
     return call.plan->dec->bad_pixels_map(0, map_out, call.plan->last_stream);
   return RSX_OK;
 }
+
+// The bad-pixel stage on a list of positions the host holds, behind a pass on the device image and
+// in front of its download (the DNG _finish calls, rsx_phase_one_decompress_fixed): the positions
+// go up and the fix runs on the same image and stream.
+struct PositionsFixStage {
+  uint8_t* map_out = nullptr;
+  CallPlan fix;
+  DeviceBuffer d_pos;
+  bool ran = false;
+  int run_positions(rsx_ctx* ctx, const uint32_t* positions, uint32_t n, int32_t is_f32,
+                    const rsx_image* img, void* dev, hipStream_t s) {
+    rsx_bad_pixels_desc d{};
+    d.positions = positions;
+    d.n_positions = n;
+    d.is_f32 = is_f32;
+    if (int e = bad_pixels_call_create(ctx, &d, img, fix))
+      return e;
+    if (int e = d_pos.ensure(size_t(n) * 4 + 16))
+      return e;
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.ptr, positions, size_t(n) * 4, hipMemcpyHostToDevice,
+                                      s ? s : ctx->stream));
+    if (int e = fix.run(d_pos.ptr, dev, s))
+      return e;
+    ran = true;
+    return RSX_OK;
+  }
+  // the map, behind the download
+  int finish() { return ran && map_out ? bad_pixels_finish(fix, nullptr, map_out) : int(RSX_OK); }
+};
 } // namespace
 
 // In place (in_place_call), the positions its side input.
@@ -3316,6 +3345,68 @@ extern "C" int rsx_panasonic_v4_decompress_fixed(rsx_ctx* ctx, const rsx_panason
   return map_out ? bad_pixels_finish(call, nullptr, map_out) : int(RSX_OK);
 }
 
+// rsx_phase_one_decompress_corrected, then the stage on the positions of the list's defects op
+// (PositionsFixStage), ONE download.
+extern "C" int rsx_iiq_defect_positions(const uint8_t* payload, uint32_t payload_bytes,
+                                        int32_t dim_x, uint32_t* out, uint32_t cap, uint32_t* n) {
+  return iiq_defect_positions(payload, payload_bytes, dim_x, out, cap, n);
+}
+
+extern "C" int rsx_phase_one_decompress_fixed(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                               int n_strips, const rsx_phase_one_strip* strips,
+                                               const rsx_iiq_corr* corr, const rsx_image* img,
+                                               int32_t* strip_status, uint8_t* map_out,
+                                               uint32_t map_pitch, rsx_bad_pixels_result* result) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !in || !strips || !corr || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = phase_one_validate(n_strips, strips, in_bytes, *img))
+    return st;
+  if (int st = iiq_correct_validate(corr, img))
+    return st;
+  if (img->pitch_bytes % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  // the positions of the (one) defects op, and the stage's own checks on them
+  std::vector<uint32_t> positions;
+  for (int o = 0; o < corr->n_ops; ++o) {
+    const rsx_iiq_op& op = corr->ops[o];
+    if (op.kind != RSX_IIQ_OP_SENSOR_DEFECTS)
+      continue;
+    uint32_t n = 0;
+    iiq_defect_positions(op.payload, op.payload_bytes, img->dim_x, nullptr, 0, &n);
+    positions.resize(n);
+    iiq_defect_positions(op.payload, op.payload_bytes, img->dim_x, positions.data(), n, &n);
+  }
+  rsx_bad_pixels_desc d{};
+  d.positions = positions.data();
+  d.n_positions = uint32_t(positions.size());
+  d.map_pitch = map_pitch;
+  d.map_out = map_out;
+  if (int st = bad_pixels_validate(&d, img))
+    return st;
+  CallPlan call;
+  PositionsFixStage fix;
+  fix.map_out = map_out;
+  SingleImageHooks hooks;
+  if (corr->n_ops != 0) {
+    if (int st = iiq_call_create(ctx, corr, img, call))
+      return st;
+    hooks.before_download = [&](uint8_t* dev, hipStream_t s) {
+      if (int e = call.run(nullptr, dev, s))
+        return e;
+      if (positions.empty())
+        return int(RSX_OK); // (the reference makes no map)
+      return fix.run_positions(ctx, positions.data(), uint32_t(positions.size()), 0, img, dev, s);
+    };
+  }
+  const int rc = phase_one_host(ctx, in, n_strips, strips, img, strip_status, hooks);
+  if (rc != RSX_OK || !fix.ran)
+    return rc;
+  return bad_pixels_finish(fix.fix, result, map_out);
+}
+
 // ---------------------------------------------------------------------------
 // DngDecoder behind the tiles: OpcodeList1 and the LinearizationTable look-up
 // ---------------------------------------------------------------------------
@@ -3376,12 +3467,8 @@ int dng_post_finish(const CallPlan& call, rsx_dng_post_result* result, uint32_t*
 // up and the fix runs on the same image and stream, in front of the download.  A list past
 // bad_cap leaves the image as the pass left it (the call then reports RSX_ERR_UNSUPPORTED, as the
 // _post call does).  `on` false: the _post calls themselves, nothing happens.
-struct DngFixStage {
+struct DngFixStage : PositionsFixStage {
   bool on = false;
-  uint8_t* map_out = nullptr;
-  CallPlan fix;
-  DeviceBuffer d_pos;
-  bool ran = false;
   // cpp > 1 with positions: refused before anything is decoded (section 5)
   static int refuse(const rsx_dng_post_desc* desc, const rsx_image* img) {
     if (img->cpp <= 1)
@@ -3404,23 +3491,8 @@ struct DngFixStage {
       return st;
     if (n == 0)
       return RSX_OK; // (the reference makes no map)
-    rsx_bad_pixels_desc d{};
-    d.positions = bad;
-    d.n_positions = uint32_t(n);
-    d.is_f32 = desc->is_f32;
-    if (int e = bad_pixels_call_create(ctx, &d, img, fix))
-      return e;
-    if (int e = d_pos.ensure(size_t(n) * 4 + 16))
-      return e;
-    RSX_HIP_CHECK(ctx, hipMemcpyAsync(d_pos.ptr, bad, size_t(n) * 4, hipMemcpyHostToDevice,
-                                      s ? s : ctx->stream));
-    if (int e = fix.run(d_pos.ptr, dev, s))
-      return e;
-    ran = true;
-    return RSX_OK;
+    return run_positions(ctx, bad, uint32_t(n), desc->is_f32, img, dev, s);
   }
-  // the map, behind the download
-  int finish() { return ran && map_out ? bad_pixels_finish(fix, nullptr, map_out) : int(RSX_OK); }
 };
 
 // In place (in_place_call): the pass, then the stage `fix`.

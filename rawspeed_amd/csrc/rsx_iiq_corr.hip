@@ -25,6 +25,10 @@
 //                        between (at most 31) and carries
 //                        on across cell boundaries.  The curves (512 KiB an op) are read from
 //                        global memory.  A lane none of whose pixels an op stood on stores nothing.
+//                        A defects op (rsx_iiq_defects.hip: it reads neighbouring columns) splits
+//                        a job's list into the run in front of it and the run behind it; `part`
+//                        says which of the two a launch applies, and the plan launches the pass,
+//                        the levels of the bad columns and the pass again on one stream.
 // No LDS, no scratch (tests/test_iiq_corr_build.py holds the numbers).
 #include <hip/hip_runtime.h>
 
@@ -81,10 +85,12 @@ __global__ void __launch_bounds__(IQ_THREADS) iiq_ff_cols_kernel(IqArgs A) {
                i % F.planes, A.tables + op.ck_off + size_t(r) * ff_ck_row_floats(F));
 }
 
-__global__ void __launch_bounds__(IQ_THREADS) iiq_correct_kernel(IqArgs A) {
+__global__ void __launch_bounds__(IQ_THREADS) iiq_correct_kernel(IqArgs A, uint32_t part) {
   const JobDev& J = A.jobs[blockIdx.y];
   const uint32_t id = blockIdx.x * IQ_THREADS + threadIdx.x;
-  if (id >= J.h * J.vpr)
+  // part 0: the ops in front of the job's defects op (all of them without one); 1: those behind it
+  const uint32_t first = part ? J.split + 1u : 0u, end = part ? J.n_ops : J.split;
+  if (first >= end || id >= J.h * J.vpr)
     return;
   const uint32_t row = id / J.vpr, v = id - row * J.vpr;
   const uint32_t col0 = 8u * v, n = min(8u, J.w - col0);
@@ -104,7 +110,7 @@ __global__ void __launch_bounds__(IQ_THREADS) iiq_correct_kernel(IqArgs A) {
     for (uint32_t i = 0; i < 8; ++i)
       px[i] = i < n ? reinterpret_cast<const uint16_t*>(p)[i] : uint16_t(0);
   }
-  const uint32_t touched = correct_pixels(J, A.ops, A.tables, A.curves, row, col0, n, px);
+  const uint32_t touched = correct_pixels(J, A.ops, A.tables, A.curves, first, end, row, col0, n, px);
   if (touched == 0u)
     return;
   if (whole) {
@@ -122,8 +128,12 @@ __global__ void __launch_bounds__(IQ_THREADS) iiq_correct_kernel(IqArgs A) {
 struct IqPlan final : DecoderPlan {
   rsx_ctx* ctx = nullptr;
   size_t n_jobs = 0, n_ops = 0;
-  DeviceBuffer d_jobs, d_ops, d_tables, d_curves, d_payloads;
-  uint32_t max_blocks = 0, max_row_blocks = 0, max_col_blocks = 0;
+  DeviceBuffer d_jobs, d_ops, d_tables, d_curves, d_payloads, d_bad_cols;
+  uint32_t max_blocks[2] = {0, 0}; // the fused pass in front of and behind the defects ops
+  uint32_t max_row_blocks = 0, max_col_blocks = 0;
+  // the bad columns of all jobs, sorted by level: level l is [level_end[l - 1], level_end[l]) of
+  // d_bad_cols, level_rows[l] the most rows one of its records walks
+  std::vector<uint32_t> level_end, level_rows;
   IqArgs args(void* out_dev) const {
     IqArgs A{};
     A.out_base = static_cast<uint8_t*>(out_dev);
@@ -151,8 +161,8 @@ struct IqPlan final : DecoderPlan {
     return RSX_OK;
   }
   int run(const void*, void* out_dev, hipStream_t s, KernelTimer* timer) override {
-    if (max_blocks == 0)
-      return RSX_OK; // (no job has an op)
+    if (max_blocks[0] == 0 && max_blocks[1] == 0 && level_end.empty())
+      return RSX_OK; // (no job has an op that writes)
     if (timer) {
       timer->begin(s);
       // (the tables stand since plan creation; a timed run writes the same values again)
@@ -165,10 +175,24 @@ struct IqPlan final : DecoderPlan {
         timer->mark("iiq_ff_cols_kernel");
       }
     }
-    hipLaunchKernelGGL(iiq_correct_kernel, dim3(max_blocks, uint32_t(n_jobs)), dim3(IQ_THREADS), 0,
-                       s, args(out_dev));
-    if (timer)
-      timer->mark("iiq_correct_kernel");
+    for (uint32_t part = 0; part < 2u; ++part) {
+      if (max_blocks[part]) {
+        hipLaunchKernelGGL(iiq_correct_kernel, dim3(max_blocks[part], uint32_t(n_jobs)),
+                           dim3(IQ_THREADS), 0, s, args(out_dev), part);
+        if (timer)
+          timer->mark("iiq_correct_kernel");
+      }
+      if (part == 1u)
+        break;
+      for (size_t l = 0; l < level_end.size(); ++l) { // (a list of columns far apart: one level)
+        const uint32_t lo = l ? level_end[l - 1] : 0u;
+        iiq_bad_columns_launch(static_cast<uint8_t*>(out_dev), d_jobs.ptr,
+                               static_cast<const IiqBadColumn*>(d_bad_cols.ptr) + lo,
+                               level_end[l] - lo, level_rows[l], s);
+        if (timer)
+          timer->mark("iiq_bad_columns_kernel");
+      }
+    }
     RSX_HIP_CHECK(ctx, hipGetLastError());
     return RSX_OK;
   }
@@ -188,6 +212,11 @@ int iiq_correct_validate(const rsx_iiq_corr* corr, const rsx_image* img) {
   return rsx_iiq::validate(corr, img);
 }
 
+int iiq_defect_positions(const uint8_t* payload, uint32_t payload_bytes, int32_t dim_x,
+                         uint32_t* out, uint32_t cap, uint32_t* n) {
+  return rsx_iiq::defect_positions(payload, payload_bytes, dim_x, out, cap, n);
+}
+
 int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job* jobs,
                             std::unique_ptr<DecoderPlan>* out) {
   auto p = std::make_unique<IqPlan>();
@@ -198,6 +227,7 @@ int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job*
   std::vector<OpDev> ops;
   std::vector<uint8_t> payloads;
   std::vector<const uint16_t*> curves;
+  std::vector<std::vector<IiqBadColumn>> levels; // [level]: the records of every job
   uint64_t table_floats = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const rsx_iiq_correct_job& j = jobs[i];
@@ -216,14 +246,20 @@ int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job*
     if (lanes >= (1ull << 31))
       return RSX_ERR_UNSUPPORTED; // (lane numbers are 32-bit on the device)
     J.op0 = uint32_t(ops.size());
-    J.n_ops = uint32_t(j.corr.n_ops);
+    J.n_ops = J.split = uint32_t(j.corr.n_ops);
     J.cfa_w = uint32_t(std::max(j.corr.cfa_w, 0));
     J.cfa_h = uint32_t(std::max(j.corr.cfa_h, 0));
     if (uint64_t(J.cfa_w) * J.cfa_h <= 64)
       for (uint32_t k = 0; k < J.cfa_w * J.cfa_h; ++k)
-        J.sel[k] = cfa_select(j.corr.cfa[k]);
-    if (J.n_ops)
-      p->max_blocks = std::max(p->max_blocks, uint32_t((lanes + IQ_THREADS - 1) / IQ_THREADS));
+        J.sel[k] = cfa_select(J.cfa[k] = j.corr.cfa[k]);
+    for (int o = 0; o < j.corr.n_ops; ++o)
+      if (j.corr.ops[o].kind == RSX_IIQ_OP_SENSOR_DEFECTS)
+        J.split = uint32_t(o);
+    const uint32_t blocks = uint32_t((lanes + IQ_THREADS - 1) / IQ_THREADS);
+    if (J.split > 0)
+      p->max_blocks[0] = std::max(p->max_blocks[0], blocks);
+    if (J.split + 1u < J.n_ops)
+      p->max_blocks[1] = std::max(p->max_blocks[1], blocks);
     for (int o = 0; o < j.corr.n_ops; ++o) {
       const rsx_iiq_op& in = j.corr.ops[o];
       OpDev op;
@@ -235,6 +271,18 @@ int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job*
         op.split_col = in.split_col;
         op.curves_off = uint64_t(curves.size()) * 4u * 65536u;
         curves.push_back(in.curves);
+      } else if (in.kind == RSX_IIQ_OP_SENSOR_DEFECTS) {
+        std::vector<uint32_t> cols, ends;
+        defects_levels(in.payload, in.payload_bytes, j.img.dim_x, j.img.dim_y, &cols, &ends);
+        if (levels.size() < ends.size()) {
+          levels.resize(ends.size());
+          p->level_rows.resize(ends.size(), 0u);
+        }
+        for (size_t l = 0, k = 0; l < ends.size(); ++l) {
+          for (; k < ends[l]; ++k)
+            levels[l].push_back(IiqBadColumn{uint32_t(i), cols[k]});
+          p->level_rows[l] = std::max(p->level_rows[l], J.h - 4u);
+        }
       } else {
         ff_parse(in.payload, in.payload_bytes, in.chroma != 0, j.img.dim_x, j.img.dim_y, &op.F);
         if (op.F.n_rows) {
@@ -259,6 +307,11 @@ int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job*
     }
   }
   p->n_ops = ops.size();
+  std::vector<IiqBadColumn> bad_cols;
+  for (const std::vector<IiqBadColumn>& l : levels) {
+    bad_cols.insert(bad_cols.end(), l.begin(), l.end());
+    p->level_end.push_back(uint32_t(bad_cols.size()));
+  }
   if (n_jobs > 65535 || ops.size() > 65535)
     return RSX_ERR_UNSUPPORTED; // (a grid's second dimension)
   RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -266,7 +319,7 @@ int iiq_correct_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_iiq_correct_job*
   if ((st = upload(ctx, p->d_jobs, jd)) || (st = upload(ctx, p->d_ops, ops)) ||
       (st = p->d_tables.ensure(size_t(table_floats) * 4 + 16)) ||
       (st = p->d_curves.ensure(curves.size() * 4 * 65536 * 2 + 16)) ||
-      (st = upload(ctx, p->d_payloads, payloads)))
+      (st = upload(ctx, p->d_payloads, payloads)) || (st = upload(ctx, p->d_bad_cols, bad_cols)))
     return st;
   for (size_t k = 0; k < curves.size(); ++k)
     RSX_HIP_CHECK(ctx, hipMemcpy(static_cast<uint16_t*>(p->d_curves.ptr) + k * 4 * 65536, curves[k],

@@ -18,9 +18,18 @@
 //                 it stands after every CK_COLS additions, so that a replay never takes more than
 //                 CK_COLS - 1 of them
 //   ff_pixel      the multiply, the truncation and the clamp
+//
+// The sensor defects of entry 0x400 (correctSensorDefects, :499-576) are no such pass: a bad column
+// is interpolated from the columns beside it.  defects_walk visits the records in file order,
+// defects_check makes the checks of the validation, bad_column_pixel computes one pixel of a bad
+// column from its neighbours (bad_column_green / bad_column_other the arithmetic), defects_levels
+// orders the columns of a list into levels of records that do not touch each other, and
+// defect_positions collects the type-129 records.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "rsx.h"
 
@@ -180,6 +189,167 @@ RSX_IIQ_FN uint16_t quad_pixel(uint16_t px, const uint16_t* curve, uint32_t blac
   return uint16_t(curve[uint16_t(px - diff)] + diff);
 }
 
+// ------------------------------------------------------------------------------------------
+// Sensor defects (entry 0x400): 8-byte records of little-endian u16 col, row, type and 2 ignored
+// bytes, in file order.
+// ------------------------------------------------------------------------------------------
+// a list may hold this many bad-column records inside the image (real lists hold a handful)
+constexpr uint32_t MAX_BAD_COLUMNS = 4096;
+
+struct DefectRecord {
+  uint32_t col, row, type;
+};
+
+RSX_IIQ_FN DefectRecord defect_record(const uint8_t* payload, uint32_t i) {
+  const uint8_t* p = payload + size_t(8) * i;
+  return DefectRecord{rd16(p), rd16(p + 2), rd16(p + 4)};
+}
+
+// a record that correctBadColumn runs for: type 131 / 137 inside the image.  With dim_y < 5 its
+// loop has no row.
+RSX_IIQ_FN bool defect_is_column(const DefectRecord& r, int32_t dim_x, int32_t dim_y) {
+  return (r.type == 131u || r.type == 137u) && int64_t(r.col) < int64_t(dim_x) && dim_y >= 5;
+}
+
+// the checks of one defects op (include/rsx.h section 3n, in its order)
+inline int defects_check(const rsx_iiq_op& op, const rsx_iiq_corr* corr, const rsx_image* img) {
+  if (!op.payload && op.payload_bytes > 0)
+    return RSX_ERR_INVALID_ARG;
+  if (op.payload_bytes % 8u != 0)
+    return RSX_ERR_IO;
+  uint32_t n_cols = 0;
+  for (uint32_t i = 0; i < op.payload_bytes / 8u; ++i) {
+    const DefectRecord r = defect_record(op.payload, i);
+    if (!defect_is_column(r, img->dim_x, img->dim_y))
+      continue;
+    if (corr->cfa_w <= 0 || corr->cfa_h <= 0 || int64_t(corr->cfa_w) * int64_t(corr->cfa_h) > 64)
+      return RSX_ERR_INVALID_ARG; // ("No CFA size set")
+    if (r.col < 2u || int64_t(r.col) > int64_t(img->dim_x) - 3)
+      return RSX_ERR_UNSUPPORTED; // (the reference reads outside the row)
+    if (++n_cols > MAX_BAD_COLUMNS)
+      return RSX_ERR_UNSUPPORTED;
+  }
+  return RSX_OK;
+}
+
+// rsx_iiq_defect_positions: the type-129 records inside the image as handleBadPixel inserts them
+inline int defect_positions(const uint8_t* payload, uint32_t payload_bytes, int32_t dim_x,
+                            uint32_t* out, uint32_t cap, uint32_t* n) {
+  if (n)
+    *n = 0;
+  if ((!payload && payload_bytes > 0) || (!out && cap > 0) || !n)
+    return RSX_ERR_INVALID_ARG;
+  if (payload_bytes % 8u != 0)
+    return RSX_ERR_IO;
+  uint32_t count = 0;
+  for (uint32_t i = 0; i < payload_bytes / 8u; ++i) {
+    const DefectRecord r = defect_record(payload, i);
+    if (int64_t(r.col) >= int64_t(dim_x) || r.type != 129u)
+      continue;
+    if (count < cap)
+      out[count] = (r.row << 16) + r.col;
+    ++count;
+  }
+  *n = count;
+  return RSX_OK;
+}
+
+// The bad columns of a checked op in an order the device can take: `cols` holds the columns of
+// the records correctBadColumn runs for, sorted by level (file order inside a level), and
+// level_end[l] the end of level l in it.  A record's level is one above the highest level of an
+// earlier record whose column lies within 2 of its own (it reads that column, or that record reads
+// or writes this one); the records of one level touch disjoint columns and read none that the
+// level writes, so a level is one launch over (record, row), and the levels run in order.
+inline void defects_levels(const uint8_t* payload, uint32_t payload_bytes, int32_t dim_x,
+                           int32_t dim_y, std::vector<uint32_t>* cols,
+                           std::vector<uint32_t>* level_end) {
+  cols->clear();
+  level_end->clear();
+  std::vector<int32_t> last(size_t(dim_x) + 4u, -1); // the highest level so far at column + 2
+  std::vector<uint32_t> col, level;
+  for (uint32_t i = 0; i < payload_bytes / 8u; ++i) {
+    const DefectRecord r = defect_record(payload, i);
+    if (!defect_is_column(r, dim_x, dim_y))
+      continue;
+    int32_t l = -1;
+    for (uint32_t c = r.col; c <= r.col + 4u; ++c)
+      l = last[c] > l ? last[c] : l;
+    last[r.col + 2u] = l + 1;
+    col.push_back(r.col);
+    level.push_back(uint32_t(l + 1));
+    if (level_end->size() < size_t(l + 2))
+      level_end->resize(size_t(l + 2), 0u);
+    ++(*level_end)[size_t(l + 1)];
+  }
+  uint32_t at = 0;
+  std::vector<uint32_t> next(level_end->size());
+  for (size_t l = 0; l < level_end->size(); ++l) {
+    next[l] = at;
+    at += (*level_end)[l];
+    (*level_end)[l] = at;
+  }
+  cols->resize(col.size());
+  for (size_t i = 0; i < col.size(); ++i)
+    (*cols)[next[level[i]]++] = col[i];
+}
+
+// binary64, every operation rounded on its own
+#if defined(__HIP_DEVICE_COMPILE__)
+RSX_IIQ_FN double d_add(double a, double b) { return __dadd_rn(a, b); }
+RSX_IIQ_FN double d_mul(double a, double b) { return __dmul_rn(a, b); }
+#else
+RSX_IIQ_FN double d_add(double a, double b) { return a + b; }
+RSX_IIQ_FN double d_mul(double a, double b) { return a * b; }
+#endif
+
+// :541-556.  v: the diagonal neighbours (row - 1, col - 1), (row + 1, col - 1), (row - 1, col + 1),
+// (row + 1, col + 1); the FIRST largest deviation from their mean is left out
+RSX_IIQ_FN uint16_t bad_column_green(const uint32_t (&v)[4]) {
+  const int32_t sum = int32_t(v[0] + v[1] + v[2] + v[3]);
+  uint32_t out = v[0];
+  int32_t worst = -1;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 4; ++i) {
+    const int32_t d = int32_t(4u * v[i]) - sum;
+    const int32_t dev = d < 0 ? -d : d;
+    if (worst < dev) {
+      worst = dev;
+      out = v[i];
+    }
+  }
+  return uint16_t((uint32_t(sum) - out + 1u) / 3u);
+}
+
+// :568-573.  lround of a value that is never negative and never above 65535.000...; x - r is exact
+RSX_IIQ_FN uint16_t bad_column_other(uint32_t diags, uint32_t horiz) {
+  const double x = d_add(d_mul(double(diags), 0.0732233), d_mul(double(horiz), 0.3535534));
+  uint32_t r = uint32_t(x);
+  if (x - double(r) >= 0.5)
+    ++r;
+  return uint16_t(r);
+}
+
+RSX_IIQ_FN uint32_t px_at(const uint8_t* img, uint32_t pitch, uint32_t row, uint32_t col) {
+  return *reinterpret_cast<const uint16_t*>(img + size_t(row) * pitch + 2u * size_t(col));
+}
+
+// the new value of (row, col) of a bad column: 2 <= row <= h - 3, 2 <= col <= w - 3; colour =
+// cfa[(col mod cfa_w) + (row mod cfa_h) cfa_w], the reference's getColorAt(col, row)
+RSX_IIQ_FN uint16_t bad_column_pixel(const uint8_t* img, uint32_t pitch, uint32_t row, uint32_t col,
+                                     uint32_t colour) {
+  if (colour == 1u) {
+    const uint32_t v[4] = {px_at(img, pitch, row - 1u, col - 1u), px_at(img, pitch, row + 1u, col - 1u),
+                           px_at(img, pitch, row - 1u, col + 1u), px_at(img, pitch, row + 1u, col + 1u)};
+    return bad_column_green(v);
+  }
+  const uint32_t diags = px_at(img, pitch, row + 2u, col - 2u) + px_at(img, pitch, row - 2u, col - 2u) +
+                         px_at(img, pitch, row + 2u, col + 2u) + px_at(img, pitch, row - 2u, col + 2u);
+  const uint32_t horiz = px_at(img, pitch, row, col - 2u) + px_at(img, pitch, row, col + 2u);
+  return bad_column_other(diags, horiz);
+}
+
 // rsx_iiq_correct_validate (include/rsx.h section 3n, in its order)
 inline int validate(const rsx_iiq_corr* corr, const rsx_image* img) {
   if (!corr || !img || img->cpp != 1 || img->dim_x <= 0 || img->dim_y <= 0 ||
@@ -189,8 +359,11 @@ inline int validate(const rsx_iiq_corr* corr, const rsx_image* img) {
     return RSX_ERR_INVALID_ARG;
   for (int i = 0; i < corr->n_ops; ++i) {
     const rsx_iiq_op& op = corr->ops[i];
-    if (op.kind != RSX_IIQ_OP_FLAT_FIELD && op.kind != RSX_IIQ_OP_QUADRANT_CURVES)
+    if (op.kind != RSX_IIQ_OP_FLAT_FIELD && op.kind != RSX_IIQ_OP_QUADRANT_CURVES &&
+        op.kind != RSX_IIQ_OP_SENSOR_DEFECTS)
       return RSX_ERR_INVALID_ARG;
+    if (op.kind == RSX_IIQ_OP_SENSOR_DEFECTS)
+      continue; // (its checks come last: defects_check)
     if (op.kind == RSX_IIQ_OP_FLAT_FIELD ? !op.payload : !op.curves)
       return RSX_ERR_INVALID_ARG;
   }
@@ -233,6 +406,14 @@ inline int validate(const rsx_iiq_corr* corr, const rsx_image* img) {
     if (ff_table_floats(F) > MAX_TABLE_FLOATS)
       return RSX_ERR_UNSUPPORTED;
   }
+  int n_defects = 0;
+  for (int i = 0; i < corr->n_ops; ++i)
+    if (corr->ops[i].kind == RSX_IIQ_OP_SENSOR_DEFECTS && ++n_defects > 1)
+      return RSX_ERR_INVALID_ARG; // ("Second sensor defects entry seen")
+  for (int i = 0; i < corr->n_ops; ++i)
+    if (corr->ops[i].kind == RSX_IIQ_OP_SENSOR_DEFECTS)
+      if (int st = defects_check(corr->ops[i], corr, img))
+        return st;
   return RSX_OK;
 }
 
@@ -254,17 +435,20 @@ struct JobDev {
   uint64_t img_offset;
   uint32_t pitch, w, h;
   uint32_t op0, n_ops; // the job's ops in the plan's list
+  uint32_t split;      // the job's defects op (n_ops: none): the fused pass stops in front of it
   uint32_t cfa_w, cfa_h;
   uint32_t vpr;        // 8-pixel vectors of a row
   uint8_t sel[64];     // cfa_select of every CFA position
+  uint8_t cfa[64];     // ... and its colour
 };
 
-// px[0 .. n) are the pixels (row, col0 ..) of job J; returns the mask of those an op stood on.
+// px[0 .. n) are the pixels (row, col0 ..) of job J, through the job's ops first .. end - 1 (none of
+// them a defects op); returns the mask of those an op stood on.
 RSX_IIQ_FN uint32_t correct_pixels(const JobDev& J, const OpDev* ops, const float* tables,
-                                   const uint16_t* curves, uint32_t row, uint32_t col0, uint32_t n,
-                                   uint16_t (&px)[8]) {
+                                   const uint16_t* curves, uint32_t first, uint32_t end, uint32_t row,
+                                   uint32_t col0, uint32_t n, uint16_t (&px)[8]) {
   uint32_t touched = 0;
-  for (uint32_t o = 0; o < J.n_ops; ++o) {
+  for (uint32_t o = first; o < end; ++o) {
     const OpDev& op = ops[J.op0 + o];
     if (op.kind == RSX_IIQ_OP_QUADRANT_CURVES) {
       const uint16_t* rowc = curves + op.curves_off + (row >= op.split_row ? 131072u : 0u);

@@ -1,12 +1,16 @@
 // rsx_iiq_corr_core.h as host C++ (librsx_iiq_corr_host.so): the same validation, row walk and
 // fused 8-pixel lane as the kernels of rsx_iiq_corr.hip, driven by loops that mirror the two
 // kernels -- every (x, plane) walks its rows into the table, every (row, cell, plane) of a wide
-// cell its start values, then every vector of every row goes through the whole list -- so that the test cases meet the code on the CPU first.  Compiled with
+// cell its start values, then every vector of every row goes through the whole list -- so that the
+// test cases meet the code on the CPU first.  A defects op ends a run of the list: its bad columns
+// are walked in file order, one after the other, as the reference does (the device sorts them into
+// levels), and the ops behind it are the next run.  Compiled with
 // -ffp-contract=off.  With -DRSX_IIQ_CORR_HOST_MAIN the file is a program (built with
 // AddressSanitizer and UBSan where g++ has them) that runs the validation cases and the
 // clipped-area cases against a pass-per-entry restatement with running sums.
 #include "rsx_iiq_corr_core.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +20,43 @@ using namespace rsx_iiq;
 
 extern "C" int rsx_iiq_corr_host_validate(const rsx_iiq_corr* corr, const rsx_image* img) {
   return validate(corr, img);
+}
+
+extern "C" int rsx_iiq_corr_host_defect_positions(const uint8_t* payload, uint32_t payload_bytes,
+                                                  int32_t dim_x, uint32_t* out, uint32_t cap,
+                                                  uint32_t* n) {
+  return defect_positions(payload, payload_bytes, dim_x, out, cap, n);
+}
+
+// the levels of a defects payload as the device plan orders them: cols[0 .. return value), the
+// end of each level in level_end[0 .. *n_levels) (both of `cap` entries)
+extern "C" uint32_t rsx_iiq_corr_host_defect_levels(const uint8_t* payload, uint32_t payload_bytes,
+                                                    int32_t dim_x, int32_t dim_y, uint32_t* cols,
+                                                    uint32_t* level_end, uint32_t cap,
+                                                    uint32_t* n_levels) {
+  std::vector<uint32_t> c, e;
+  defects_levels(payload, payload_bytes, dim_x, dim_y, &c, &e);
+  for (size_t i = 0; i < c.size() && i < cap; ++i)
+    cols[i] = c[i];
+  for (size_t i = 0; i < e.size() && i < cap; ++i)
+    level_end[i] = e[i];
+  *n_levels = uint32_t(e.size());
+  return uint32_t(c.size());
+}
+
+// the bad columns of a checked defects op, in file order, in place
+static void apply_defects(const rsx_iiq_op& op, const JobDev& J, const rsx_iiq_corr* corr,
+                          uint8_t* img) {
+  for (uint32_t i = 0; i < op.payload_bytes / 8u; ++i) {
+    const DefectRecord r = defect_record(op.payload, i);
+    if (!defect_is_column(r, int32_t(J.w), int32_t(J.h)))
+      continue;
+    for (uint32_t row = 2; row + 2u < J.h; ++row) {
+      const uint32_t colour = corr->cfa[r.col % J.cfa_w + (row % J.cfa_h) * J.cfa_w];
+      *reinterpret_cast<uint16_t*>(img + size_t(row) * J.pitch + 2u * size_t(r.col)) =
+          bad_column_pixel(img, J.pitch, row, r.col, colour);
+    }
+  }
 }
 
 // rsx_iiq_correct on the host: img->data is corrected in place (untouched unless RSX_OK)
@@ -48,6 +89,8 @@ extern "C" int rsx_iiq_corr_host_apply(const rsx_iiq_corr* corr, const rsx_image
       op.split_col = in.split_col;
       continue;
     }
+    if (in.kind == RSX_IIQ_OP_SENSOR_DEFECTS)
+      continue;
     ff_parse(in.payload, in.payload_bytes, in.chroma != 0, img->dim_x, img->dim_y, &op.F);
     op.table_off = tables.size();
     tables.resize(tables.size() + size_t(ff_table_floats(op.F)));
@@ -64,25 +107,29 @@ extern "C" int rsx_iiq_corr_host_apply(const rsx_iiq_corr* corr, const rsx_image
             ff_walk_cols(tables.data() + op.table_off + size_t(r) * op.F.tcols * op.F.planes, op.F, x, p,
                          tables.data() + op.ck_off + size_t(r) * ff_ck_row_floats(op.F));
   }
-  for (uint32_t row = 0; row < J.h; ++row) {
-    uint16_t* line = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(img->data) + size_t(row) * J.pitch);
-    for (uint32_t v = 0; v < J.vpr; ++v) {
-      const uint32_t col0 = 8u * v, n = J.w - col0 < 8u ? J.w - col0 : 8u;
-      uint16_t px[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (uint32_t i = 0; i < n; ++i)
-        px[i] = line[col0 + i];
-      uint32_t touched = 0;
-      // (one op at a time: its curves stay where the caller has them, at offset 0)
-      for (uint32_t o = 0; o < J.n_ops; ++o) {
-        JobDev one = J;
-        one.op0 = o;
-        one.n_ops = 1;
-        touched |= correct_pixels(one, ops.data(), tables.data(), corr->ops[o].curves, row, col0, n, px);
+  // the runs of the list: [first, end) holds no defects op
+  for (uint32_t first = 0, end = 0; first <= J.n_ops; first = end + 1u) {
+    for (end = first; end < J.n_ops && ops[end].kind != RSX_IIQ_OP_SENSOR_DEFECTS;)
+      ++end;
+    for (uint32_t row = 0; row < J.h && first < end; ++row) {
+      uint16_t* line = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(img->data) + size_t(row) * J.pitch);
+      for (uint32_t v = 0; v < J.vpr; ++v) {
+        const uint32_t col0 = 8u * v, n = J.w - col0 < 8u ? J.w - col0 : 8u;
+        uint16_t px[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t i = 0; i < n; ++i)
+          px[i] = line[col0 + i];
+        uint32_t touched = 0;
+        // (one op at a time: its curves stay where the caller has them, at offset 0)
+        for (uint32_t o = first; o < end; ++o)
+          touched |= correct_pixels(J, ops.data(), tables.data(), corr->ops[o].curves, o, o + 1u, row,
+                                    col0, n, px);
+        for (uint32_t i = 0; i < n; ++i)
+          if (touched >> i & 1u)
+            line[col0 + i] = px[i];
       }
-      for (uint32_t i = 0; i < n; ++i)
-        if (touched >> i & 1u)
-          line[col0 + i] = px[i];
     }
+    if (end < J.n_ops)
+      apply_defects(corr->ops[end], J, corr, static_cast<uint8_t*>(img->data));
   }
   return RSX_OK;
 }
@@ -262,6 +309,63 @@ int main() {
           narrow.pitch_bytes = uint32_t(2 * g.w - 2);
           expect(rsx_iiq_corr_host_apply(&corr, &narrow) == RSX_ERR_INVALID_ARG && a == keep, "pitch");
         }
+  // The sensor defects: random record lists -- bad columns in clusters and far apart, the same
+  // column again, bad pixels, unknown types and columns outside the image between them -- applied
+  // in file order (apply_defects) and level by level, each level from its LAST record to its first
+  // (what the device's launches are free to do).  Both must give the same image.
+  for (int round = 0; round < 300; ++round) {
+    const int w = 5 + int(rnd() % 60), h = 4 + int(rnd() % 12), pitch_px = w + int(rnd() % 3);
+    std::vector<uint8_t> pl;
+    const int n_rec = int(rnd() % 40);
+    for (int k = 0; k < n_rec; ++k) {
+      const uint32_t kind = rnd() % 8;
+      uint32_t col = kind < 5 ? 2u + rnd() % uint32_t(w - 4) : rnd() % uint32_t(w + 6);
+      if (kind < 2 && pl.size() >= 8) // (beside the record in front)
+        col = std::min(uint32_t(w - 3), std::max(2u, rd16(pl.data() + pl.size() - 8) + rnd() % 5u - 2u));
+      const uint32_t type = kind < 5 ? (rnd() & 1u ? 131u : 137u) : kind == 5 ? 129u : kind == 6 ? 7u : 131u;
+      if (kind == 7 && col < uint32_t(w))
+        col += uint32_t(w); // (a bad column outside the image: skipped, whatever it holds)
+      const uint32_t rec[4] = {col, rnd() % 65536u, type, rnd() % 65536u};
+      for (uint32_t v : rec) {
+        pl.push_back(uint8_t(v));
+        pl.push_back(uint8_t(v >> 8));
+      }
+    }
+    rsx_iiq_corr corr;
+    std::memset(&corr, 0, sizeof corr);
+    corr.cfa_w = 2;
+    corr.cfa_h = round % 3 == 0 ? 4 : 2;
+    const uint8_t cfa[8] = {1, 0, 2, 1, 0, 1, 1, 2};
+    std::memcpy(corr.cfa, cfa, 8);
+    corr.n_ops = 1;
+    corr.ops[0].kind = RSX_IIQ_OP_SENSOR_DEFECTS;
+    corr.ops[0].payload = pl.data();
+    corr.ops[0].payload_bytes = uint32_t(pl.size());
+    std::vector<uint16_t> a(size_t(pitch_px) * h), b;
+    for (uint16_t& v : a)
+      v = uint16_t(rnd());
+    b = a;
+    rsx_image img{a.data(), uint32_t(2 * pitch_px), w, h, 1, 1};
+    expect(rsx_iiq_corr_host_apply(&corr, &img) == RSX_OK, "defects: apply status");
+    std::vector<uint32_t> cols, ends;
+    defects_levels(pl.data(), uint32_t(pl.size()), w, h, &cols, &ends);
+    uint8_t* bytes = reinterpret_cast<uint8_t*>(b.data());
+    for (size_t l = 0; l < ends.size(); ++l) {
+      // (every lane of a launch may read before any of them writes, or after)
+      std::vector<uint16_t> before = b;
+      for (uint32_t k = ends[l]; k-- > (l ? ends[l - 1] : 0u);)
+        for (uint32_t row = 2; row + 2u < uint32_t(h); ++row) {
+          const uint32_t colour = corr.cfa[cols[k] % 2u + (row % uint32_t(corr.cfa_h)) * 2u];
+          const uint8_t* from = (k & 1u) ? reinterpret_cast<const uint8_t*>(before.data()) : bytes;
+          b[size_t(row) * pitch_px + cols[k]] = bad_column_pixel(from, uint32_t(2 * pitch_px), row, cols[k], colour);
+        }
+    }
+    expect(a == b, "defects: level order against file order");
+    uint32_t n = 0, two[2] = {0, 0};
+    expect(defect_positions(pl.data(), uint32_t(pl.size()), w, two, 2, &n) == RSX_OK, "defects: positions");
+    expect(defect_positions(pl.data(), uint32_t(pl.size()) - (pl.empty() ? 0u : 3u), w, two, 2, &n) ==
+               (pl.empty() ? RSX_OK : RSX_ERR_IO), "defects: a cut record");
+  }
   if (fails)
     return 1;
   std::puts("rsx_iiq_corr_host_check OK");

@@ -146,7 +146,11 @@ struct Vc5 {
 // IiqDecoder::decodeRawInternal(): the correction entries of the 0x110 block as
 // an op list, in file order, for rsx_phase_one_decompress_corrected.  The hunk parses the block
 // first (what CorrectPhaseOneC's switch does, without touching a pixel) and feeds this collector:
-// a flat-field entry is handed over as the bytes of its sub-stream; a quadrant entry as the four
+// a flat-field entry and the sensor defects (0x400) are handed over as the bytes of their
+// sub-streams -- the bad columns of the defects are corrected on the device, where the entry stands
+// in the list; its type-129 records go into mRaw->mBadPixelPositions behind a call that succeeded
+// (run), or are fixed on the device in front of the download when the caller interpolates bad
+// pixels (fixed: INTEGRATION.md 3r) --; a quadrant entry as the four
 // curves the reference's own Spline<>::calculateCurve() gave for the control points of
 // :338-373 (its checks have thrown by then, as they would have); the CFA as mRaw->cfa holds it.
 // More than RSX_IIQ_MAX_OPS entries, or a CFA of more than 64 positions: `usable` goes false and
@@ -155,6 +159,7 @@ struct IiqCorrections {
   rsx_iiq_corr d{};
   std::vector<std::vector<uint16_t>> curves; // [op]: 4 x 65536, [quadRow][quadCol]
   bool usable = true;
+  const rsx_iiq_op* defects_op = nullptr;
   IiqCorrections() { curves.reserve(RSX_IIQ_MAX_OPS); }
   rsx_iiq_op* next(int kind) {
     if (d.n_ops >= RSX_IIQ_MAX_OPS) {
@@ -171,6 +176,15 @@ struct IiqCorrections {
       op->chroma = chroma ? 1 : 0;
       op->payload = b.begin();
       op->payload_bytes = b.getSize();
+    }
+  }
+  // entry 0x400 (the hunk keeps its "Second sensor defects entry seen" throw)
+  void defects(const ByteStream& entry) {
+    if (rsx_iiq_op* op = next(RSX_IIQ_OP_SENSOR_DEFECTS)) {
+      const Buffer b = entry.peekRemainingBuffer();
+      op->payload = b.begin();
+      op->payload_bytes = b.getSize();
+      defects_op = op;
     }
   }
   // quad[quadRow][quadCol]: 65536 entries each
@@ -208,8 +222,42 @@ struct IiqCorrections {
     if (!rsx || !usable)
       return RSX_ERR_DEVICE;
     const rsx_image v = view(img);
-    return rsx_phase_one_decompress_corrected(rsx, lo, bytes, implicit_cast<int>(table.size()),
-                                              table.data(), &d, &v, nullptr);
+    const int st = rsx_phase_one_decompress_corrected(
+        rsx, lo, bytes, implicit_cast<int>(table.size()), table.data(), &d, &v, nullptr);
+    if (st == RSX_OK)
+      insert_positions(img);
+    return st;
+  }
+  // ... with fixBadPixels() on the device in front of the download (the caller interpolates bad
+  // pixels): `map` receives mBadPixelMap when one was made (result->map_made), and the positions
+  // stay out of mBadPixelPositions, as transferBadPixelsToMap() leaves them
+  int fixed(const uint8_t* lo, size_t bytes, const std::vector<rsx_phase_one_strip>& table,
+             const RawImage& img, std::vector<uint8_t>* map, uint32_t map_pitch,
+             rsx_bad_pixels_result* result) {
+    rsx_ctx* rsx = context();
+    if (!rsx || !usable)
+      return RSX_ERR_DEVICE;
+    const rsx_image v = view(img);
+    map->assign(size_t(map_pitch) * size_t(v.dim_y), 0);
+    return rsx_phase_one_decompress_fixed(rsx, lo, bytes, implicit_cast<int>(table.size()),
+                                           table.data(), &d, &v, nullptr, map->data(), map_pitch,
+                                           result);
+  }
+
+private:
+  // handleBadPixel for every type-129 record inside the image, in file order
+  void insert_positions(const RawImage& img) const {
+    if (!defects_op)
+      return;
+    uint32_t n = 0;
+    if (rsx_iiq_defect_positions(defects_op->payload, defects_op->payload_bytes, img->dim.x, nullptr,
+                                 0, &n) != RSX_OK || n == 0)
+      return;
+    std::vector<uint32_t> pos(n);
+    rsx_iiq_defect_positions(defects_op->payload, defects_op->payload_bytes, img->dim.x, pos.data(),
+                             n, &n);
+    MutexLocker guard(&img->mBadPixelMutex);
+    img->mBadPixelPositions.insert(img->mBadPixelPositions.end(), pos.begin(), pos.end());
   }
 };
 
