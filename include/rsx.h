@@ -1166,6 +1166,87 @@ int rsx_crw_decompress(rsx_ctx* ctx, const rsx_crw_desc* desc, const uint8_t* in
                        const uint8_t* low, size_t low_bytes, const rsx_image* img);
 
 /* ------------------------------------------------------------------------ */
+/* 3y. RafDecoder::applyCorrections: the 45 degree rotation of SuperCCD      */
+/*    frames (decoders/RafDecoder.cpp:228-270; the cameras with the          */
+/*    fuji_rotate hint)                                                      */
+/*    With W x H = new_size (size_x, size_y), (cx, cy) = crop_offset and     */
+/*    R = rotatedsize, sample src(cy + y, cx + x) of the uncropped uint16    */
+/*    image goes to dst(h, w):                                               */
+/*      normal  R = W + H / 2  h = W - 1 - x + (y >> 1)                      */
+/*                             w = ((y + 1) >> 1) + x                        */
+/*      alt     R = H + W / 2  h = R - (H + 1 - y + (x >> 1))                */
+/*                             w = ((x + 1) >> 1) + y                        */
+/*    dst is R wide and R - 1 tall; every sample nothing lands on is 0       */
+/*    (clearArea).  metadata.fujiRotationPos is W - 1 (normal) or W / 2 - 1  */
+/*    (alt).  Bytes of dst's pitch beyond R samples are not written.         */
+/*    rsx_raf_rotate_validate, in this order: desc, src or dst NULL; cpp    */
+/*    != 1 on either image; a dimension <= 0; a pitch below 2 dim_x, or odd; */
+/*    size_x < 1 or size_y < 1; a negative crop offset; crop + size beyond   */
+/*    src (the reference would read outside its image); R < 2 or R > 65535   */
+/*    (RawImage::createData throws); dst other than R x (R - 1); src and dst */
+/*    (both with data) overlapping; the normal layout with odd size_y (the   */
+/*    reference throws "Trying to write out of bounds": (y = H - 1, x = 0)   */
+/*    lands on row R - 1) -> RSX_ERR_INVALID_ARG.  Then alt_layout with odd  */
+/*    size_x -> RSX_ERR_UNSUPPORTED: (y = 0, x = W - 1) lands on row -1,     */
+/*    which the reference's signed `h < dim.y` does not catch.               */
+/*    rsx_raf_rotate_geometry applies the checks that need no image, in the */
+/*    same order, and gives dst's size and fujiRotationPos (outputs may be   */
+/*    NULL; untouched on a failure).                                         */
+/*    rsx_raf_rotate: src->data and dst->data are both host pointers (the   */
+/*    rows of the crop go up, the rotated image comes back) or both device   */
+/*    pointers (the call returns when the pass is done).  One launch writes  */
+/*    every sample of dst.  On any status but RSX_OK dst is untouched.       */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_raf_rotate_desc {
+  int32_t crop_x, crop_y; /* crop_offset */
+  int32_t size_x, size_y; /* new_size */
+  int32_t alt_layout;
+  int32_t reserved;
+} rsx_raf_rotate_desc;
+
+int rsx_raf_rotate_geometry(const rsx_raf_rotate_desc* desc, int32_t* out_dim_x,
+                             int32_t* out_dim_y, int32_t* rotation_pos);
+int rsx_raf_rotate_validate(const rsx_raf_rotate_desc* desc, const rsx_image* src,
+                             const rsx_image* dst);
+int rsx_raf_rotate(rsx_ctx* ctx, const rsx_raf_rotate_desc* desc, const rsx_image* src,
+                    const rsx_image* dst);
+
+/* ------------------------------------------------------------------------ */
+/* 3z. ArwDecoder::SonyDecrypt and ArwDecoder::decodeSRF (Sony SRF, DSC-F828) */
+/*    (decoders/ArwDecoder.cpp:524-560 and :70-118)                          */
+/*    The pad from `key`, uint32 wrapping: pad[p] = key = key 48828125 + 1   */
+/*    for p = 0..3; pad[3] = pad[3] << 1 | (pad[0] ^ pad[2]) >> 31; pad[p] = */
+/*    (pad[p-4] ^ pad[p-2]) << 1 | (pad[p-3] ^ pad[p-1]) >> 31 for p =       */
+/*    4..126; then every entry byte-swapped.  With w[0..126] those values,   */
+/*    w[n] = w[n - 127] ^ w[n - 63] for n >= 127, and output word i is input */
+/*    word i (4 bytes, as a little-endian uint32) ^ w[127 + i].              */
+/*    rsx_sony_decrypt runs that over n_words words: `in` and `out` are both */
+/*    host or both device pointers, of any alignment; in == out is allowed,  */
+/*    any other overlap is not; n_words == 0 is RSX_OK and does nothing;     */
+/*    ctx NULL, or in / out NULL with n_words > 0 -> RSX_ERR_INVALID_ARG;    */
+/*    n_words >= 2^32 -> RSX_ERR_UNSUPPORTED.                                */
+/*    rsx_sony_srf_decompress is decodeSRF behind its key derivation (which  */
+/*    stays with the caller: the byte at 200896, the 40-byte head at 164600  */
+/*    through the same generator, four bytes of it): `in` is the image data  */
+/*    at file offset 862144, `key` the final key.  2 dim_x dim_y bytes are   */
+/*    decrypted and read as 16-bit big-endian rows of pitch 2 dim_x, in one  */
+/*    pass over the bytes: pix(2j) = b0 << 8 | b1, pix(2j + 1) = b2 << 8 |   */
+/*    b3 of decrypted word j, pixels counted along the rows.                 */
+/*    rsx_sony_srf_validate, in this order: img NULL; cpp != 1; dimensions   */
+/*    outside 1..3360 x 1..2460; a pitch below 2 dim_x, or odd ->            */
+/*    RSX_ERR_INVALID_ARG; in_bytes < 2 dim_x dim_y (getSubView) ->          */
+/*    RSX_ERR_IO; dim_x dim_y odd -> RSX_ERR_UNSUPPORTED (len / 4 drops two  */
+/*    bytes and SonyDecrypt's size invariants do not hold).                  */
+/*    `in` and `img->data` are both host or both device pointers.  On any    */
+/*    status but RSX_OK the image is untouched; bytes of its pitch beyond    */
+/*    dim_x samples are never written.                                       */
+/* ------------------------------------------------------------------------ */
+int rsx_sony_decrypt(rsx_ctx* ctx, const uint8_t* in, uint8_t* out, size_t n_words, uint32_t key);
+int rsx_sony_srf_validate(size_t in_bytes, const rsx_image* img);
+int rsx_sony_srf_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes, uint32_t key,
+                            const rsx_image* img);
+
+/* ------------------------------------------------------------------------ */
 /* 4. AbstractDngDecompressor tile fan-out                                   */
 /*    replaces AbstractDngDecompressor::decompress()                         */
 /*    (AbstractDngDecompressor.h:141, .cpp:240-252) for compression 1        */
@@ -2183,6 +2264,38 @@ int rsx_crw_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_crw_job* jobs, rsx_p
  * leaves every window behind the first to the settling kernel; values above 32 count as 32).  The result of a run does not
  * depend on it. */
 int rsx_crw_plan_stats(rsx_plan* plan, int job, uint32_t stats[4]);
+
+/* one SuperCCD rotation (section 3y).  in_offset / img_offset address the uncropped source image
+ * in the run's input buffer and the rotated image in its output buffer (both even; any even
+ * pitches; the two buffers may be one allocation as long as the images do not overlap).  Jobs of
+ * different geometry and layout share the plan's one launch.  A job rsx_raf_rotate_validate
+ * refuses has that status in rsx_plan_results and its image is untouched. */
+typedef struct rsx_raf_rotate_job {
+  rsx_raf_rotate_desc desc;
+  uint64_t in_offset;
+  uint64_t img_offset;
+  rsx_image in;  /* .data ignored */
+  rsx_image img; /* .data ignored */
+} rsx_raf_rotate_job;
+
+int rsx_raf_rotate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_raf_rotate_job* jobs,
+                                rsx_plan** out_plan);
+
+/* one Sony SRF frame (section 3z): 2 dim_x dim_y bytes at in_offset (any), the image at an even
+ * img_offset with any even pitch_bytes >= 2 dim_x.  Jobs of different geometry and key share the
+ * plan's one launch.  A job rsx_sony_srf_validate refuses has that status in rsx_plan_results and
+ * its image is untouched.  Job results report 0 bytes consumed. */
+typedef struct rsx_sony_srf_job {
+  uint64_t in_offset;
+  uint64_t in_bytes;
+  uint64_t img_offset;
+  uint32_t key;
+  uint32_t reserved;
+  rsx_image img; /* .data ignored */
+} rsx_sony_srf_job;
+
+int rsx_sony_srf_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_srf_job* jobs,
+                             rsx_plan** out_plan);
 
 int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
                              rsx_plan** out_plan);

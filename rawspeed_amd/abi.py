@@ -806,3 +806,28 @@ def crw_desc(dec_table, has_lowbits):
     d = CrwDesc()
     d.dec_table, d.has_lowbits = dec_table, 1 if has_lowbits else 0
     return d
+
+
+class FujiRotateDesc(C.Structure):
+    """rsx_raf_rotate_desc (include/rsx.h section 3y)"""
+    _fields_ = [("crop_x", C.c_int32), ("crop_y", C.c_int32), ("size_x", C.c_int32),
+                ("size_y", C.c_int32), ("alt_layout", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FujiRotateJob(C.Structure):
+    """rsx_raf_rotate_job: the source in the run's input buffer, the rotated image in its output"""
+    _fields_ = [("desc", FujiRotateDesc), ("in_offset", C.c_uint64), ("img_offset", C.c_uint64),
+                ("in_", Image), ("img", Image)]
+
+
+def fuji_rotate_desc(crop, size, alt_layout):
+    d = FujiRotateDesc()
+    (d.crop_x, d.crop_y), (d.size_x, d.size_y) = crop, size
+    d.alt_layout = 1 if alt_layout else 0
+    return d
+
+
+class SonySrfJob(C.Structure):
+    """rsx_sony_srf_job (include/rsx.h section 3z)"""
+    _fields_ = [("in_offset", C.c_uint64), ("in_bytes", C.c_uint64), ("img_offset", C.c_uint64),
+                ("key", C.c_uint32), ("reserved", C.c_uint32), ("img", Image)]

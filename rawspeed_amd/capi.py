@@ -57,6 +57,10 @@ EXPORTS = [
     "rsx_olympus_plan_job_status",
     "rsx_kodak_validate", "rsx_kodak_decompress", "rsx_kodak_plan_create",
     "rsx_crw_validate", "rsx_crw_decompress", "rsx_crw_plan_create", "rsx_crw_plan_stats",
+    "rsx_raf_rotate_geometry", "rsx_raf_rotate_validate", "rsx_raf_rotate",
+    "rsx_raf_rotate_plan_create",
+    "rsx_sony_decrypt", "rsx_sony_srf_validate", "rsx_sony_srf_decompress",
+    "rsx_sony_srf_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -205,6 +209,13 @@ def lib():
         L.rsx_crw_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsx_crw_plan_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_raf_rotate_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_raf_rotate_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_raf_rotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_sony_decrypt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]
+        L.rsx_sony_srf_validate.argtypes = [C.c_size_t, C.c_void_p]
+        L.rsx_sony_srf_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                              C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -232,7 +243,8 @@ def lib():
                      "rsx_dng_post_plan_create", "rsx_bad_pixels_plan_create",
                      "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create",
                      "rsx_fuji_plan_create", "rsx_olympus_plan_create",
-                     "rsx_kodak_plan_create", "rsx_crw_plan_create"):
+                     "rsx_kodak_plan_create", "rsx_crw_plan_create",
+                     "rsx_raf_rotate_plan_create", "rsx_sony_srf_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -387,6 +399,31 @@ def crw_validate(dec_table, has_lowbits, img_view, in_bytes, low_bytes):
     return lib().rsx_crw_validate(None if d is None else C.byref(d),
                                   None if img_view is None else C.byref(img_view), in_bytes,
                                   low_bytes)
+
+
+def _ref(x):
+    return None if x is None else C.byref(x)
+
+
+def fuji_rotate_geometry(desc):
+    """rsx_raf_rotate_geometry -> (status, out_dim_x, out_dim_y, rotation_pos); desc None passes
+    NULL.  The three values are None on any status but RSX_OK."""
+    x, y, pos = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    st = lib().rsx_raf_rotate_geometry(_ref(desc), C.byref(x), C.byref(y), C.byref(pos))
+    if st != abi.RSX_OK:
+        assert (x.value, y.value, pos.value) == (-1, -1, -1), "outputs written on a failure"
+        return st, None, None, None
+    return st, x.value, y.value, pos.value
+
+
+def fuji_rotate_validate(desc, src_view, dst_view):
+    """rsx_raf_rotate_validate; None passes NULL"""
+    return lib().rsx_raf_rotate_validate(_ref(desc), _ref(src_view), _ref(dst_view))
+
+
+def sony_srf_validate(in_bytes, img_view):
+    """rsx_sony_srf_validate; img_view None passes a NULL image"""
+    return lib().rsx_sony_srf_validate(in_bytes, _ref(img_view))
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -774,6 +811,32 @@ class Context:
                                         C.c_void_p(low_ptr or 0), low_bytes or 0,
                                         C.byref(img_view))
 
+    def fuji_rotate(self, desc, src_view, dst_view):
+        """rsx_raf_rotate: both views hold host pointers or both device pointers.  Returns the
+        status."""
+        return lib().rsx_raf_rotate(self._h, _ref(desc), _ref(src_view), _ref(dst_view))
+
+    def sony_decrypt(self, data, key, in_ptr=None, out_ptr=None, n_words=None):
+        """rsx_sony_decrypt.  data: host bytes (a multiple of 4) -> (status, the decrypted bytes);
+        or device pointers in_ptr / out_ptr (which may be equal) and n_words -> status."""
+        if in_ptr is not None:
+            return lib().rsx_sony_decrypt(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), n_words,
+                                          key)
+        a = _u8(np.frombuffer(bytes(data) + b"\0", np.uint8))  # (a pointer for no bytes)
+        out = np.full(len(data) + 1, 0xA5, np.uint8)
+        st = lib().rsx_sony_decrypt(self._h, a.ctypes.data, out.ctypes.data, len(data) // 4, key)
+        assert out[len(data)] == 0xA5
+        return st, out[:len(data)]
+
+    def sony_srf_decompress(self, data, key, img_view, in_ptr=None, in_bytes=None):
+        """data: the encrypted image bytes (host), or the device buffer at in_ptr (then
+        img_view.data is a device pointer too).  Returns the status."""
+        if in_ptr is None:
+            a = _u8(np.frombuffer(bytes(data) + b"\0", np.uint8))  # (a pointer for no bytes)
+            in_ptr, in_bytes = a.ctypes.data, len(data)
+        return lib().rsx_sony_srf_decompress(self._h, C.c_void_p(in_ptr), in_bytes, key,
+                                             C.byref(img_view))
+
     def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
         """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
         tiles' zlib streams.  Returns (status, per-tile statuses)."""
@@ -928,6 +991,14 @@ class Context:
     def crw_plan(self, jobs):
         """jobs: abi.CrwJob, one per frame (geometries and tables may mix)"""
         return CrwPlan(self, "rsx_crw_plan_create", abi.CrwJob, jobs)
+
+    def fuji_rotate_plan(self, jobs):
+        """jobs: abi.FujiRotateJob, one per frame (geometries and layouts may mix)"""
+        return Plan(self, "rsx_raf_rotate_plan_create", abi.FujiRotateJob, jobs)
+
+    def sony_srf_plan(self, jobs):
+        """jobs: abi.SonySrfJob, one per frame (geometries and keys may mix)"""
+        return Plan(self, "rsx_sony_srf_plan_create", abi.SonySrfJob, jobs)
 
     def dng_jpeg_plan(self, jobs):
         """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""

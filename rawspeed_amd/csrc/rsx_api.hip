@@ -20,6 +20,10 @@
 #include "rsx_kodak_core.h"
 #include "rsx_crw.h"
 #include "rsx_crw_core.h"
+#include "rsx_fuji_rotate.h"
+#include "rsx_fuji_rotate_core.h"
+#include "rsx_sony_srf.h"
+#include "rsx_sony_srf_core.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
@@ -4244,6 +4248,190 @@ extern "C" int rsx_crw_decompress(rsx_ctx* ctx, const rsx_crw_desc* desc, const 
   std::memcpy(both.data() + job.low_offset, low, low_need);
   return single_image_host(ctx, key, rsx_crw_plan_create, job, both.data(), both.size(), img,
                            nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// RafDecoder::applyCorrections: the SuperCCD rotation
+// ---------------------------------------------------------------------------
+extern "C" int rsx_raf_rotate_geometry(const rsx_raf_rotate_desc* desc, int32_t* out_dim_x,
+                                        int32_t* out_dim_y, int32_t* rotation_pos) {
+  return rsx_fujirot::geometry(desc, out_dim_x, out_dim_y, rotation_pos);
+}
+
+extern "C" int rsx_raf_rotate_validate(const rsx_raf_rotate_desc* desc, const rsx_image* src,
+                                        const rsx_image* dst) {
+  return rsx_fujirot::validate(desc, src, dst);
+}
+
+extern "C" int rsx_raf_rotate_plan_create(rsx_ctx* ctx, int n_jobs,
+                                           const rsx_raf_rotate_job* jobs, rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, fuji_rotate_plan_create);
+}
+
+// Device pointers: a plan of the call's own runs on them (the two images are two ranges from the
+// lower of the two addresses), on the context's stream behind the null stream's work so far, and
+// the call returns when it is done.  Host pointers: the rows of the crop go up as one copy, the
+// pass writes a compact image (pitch roundUp(2 R, 16)) on a lane, and that comes back through
+// download_rects -- about twice the bytes that went up.
+extern "C" int rsx_raf_rotate(rsx_ctx* ctx, const rsx_raf_rotate_desc* desc,
+                               const rsx_image* src, const rsx_image* dst) {
+  if (!ctx || !desc || !src || !dst)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_fujirot::validate(desc, src, dst))
+    return st;
+  if (!src->data || !dst->data || reinterpret_cast<uintptr_t>(src->data) % 2 != 0 ||
+      reinterpret_cast<uintptr_t>(dst->data) % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool in_dev = is_device_pointer(src->data), out_dev = is_device_pointer(dst->data);
+  if (in_dev != out_dev)
+    return RSX_ERR_INVALID_ARG;
+  rsx_raf_rotate_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *desc;
+  job.in = *src;
+  job.img = *dst;
+  job.in.data = job.img.data = nullptr;
+  if (in_dev) {
+    const uint8_t* a = static_cast<const uint8_t*>(src->data);
+    uint8_t* b = static_cast<uint8_t*>(dst->data);
+    const uint8_t* base = a < b ? a : b;
+    job.in_offset = uint64_t(a - base);
+    job.img_offset = uint64_t(b - base);
+    CallPlan call;
+    if (int st = rsx_raf_rotate_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    return call.run(base, const_cast<uint8_t*>(base), nullptr);
+  }
+  // the rows [crop_y, crop_y + size_y) of the source, whole, become the job's image
+  job.desc.crop_y = 0;
+  job.in.dim_y = desc->size_y;
+  job.img.pitch_bytes = uint32_t(align_up(size_t(dst->dim_x) * 2, 16));
+  const size_t in_bytes = size_t(rsx_fujirot::image_span(&job.in));
+  const size_t out_bytes = size_t(job.img.pitch_bytes) * size_t(dst->dim_y);
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  if (int e = lane.lane->d_in.ensure(in_bytes + 64))
+    return e;
+  if (int e = lane.lane->d_out.ensure(out_bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_in.ptr,
+                                      static_cast<const uint8_t*>(src->data) +
+                                          size_t(desc->crop_y) * src->pitch_bytes,
+                                      in_bytes, hipMemcpyHostToDevice, s));
+  }
+  CallPlan call;
+  if (int st = rsx_raf_rotate_plan_create(ctx, 1, &job, &call.plan))
+    return st;
+  if (int rc = rsx_plan_run(call.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, s))
+    return rc;
+  const DownRect dr{static_cast<uint8_t*>(dst->data), dst->pitch_bytes,
+                    static_cast<uint8_t*>(lane.lane->d_out.ptr), job.img.pitch_bytes,
+                    size_t(dst->dim_x) * 2, size_t(dst->dim_y)};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  return download_rects(ctx, lane.lane, s, &dr, 1);
+}
+
+// ---------------------------------------------------------------------------
+// ArwDecoder::SonyDecrypt, ArwDecoder::decodeSRF
+// ---------------------------------------------------------------------------
+extern "C" int rsx_sony_srf_validate(size_t in_bytes, const rsx_image* img) {
+  return rsx_sony_srf::validate(in_bytes, img);
+}
+
+extern "C" int rsx_sony_srf_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_srf_job* jobs,
+                                        rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, sony_srf_plan_create);
+}
+
+// Device pointers: a plan of the call's own runs on them, on the context's stream behind the null
+// stream's work so far, and the call returns when it is done.  Host pointers: the words go up as
+// one copy, are decrypted in place on a lane and come back as one.
+extern "C" int rsx_sony_decrypt(rsx_ctx* ctx, const uint8_t* in, uint8_t* out, size_t n_words,
+                                uint32_t key) {
+  if (!ctx)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (n_words == 0)
+    return RSX_OK;
+  if (!in || !out)
+    return RSX_ERR_INVALID_ARG;
+  if (uint64_t(n_words) > 0xFFFFFFFFull)
+    return RSX_ERR_UNSUPPORTED;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool in_dev = is_device_pointer(in), out_dev = is_device_pointer(out);
+  if (in_dev != out_dev)
+    return RSX_ERR_INVALID_ARG;
+  rsx_sony_srf_job none{};
+  CallPlan call;
+  if (int st = decoder_plan_create(
+          ctx, 1, &none, &call.plan,
+          [&](rsx_ctx* c, int, const rsx_sony_srf_job*, std::unique_ptr<DecoderPlan>* o) {
+            return sony_decrypt_plan_create(c, n_words, key, o);
+          }))
+    return st;
+  if (in_dev) {
+    if (int st = rsx_plan_run(call.plan, in, out, nullptr))
+      return st;
+    return rsx_plan_results(call.plan, nullptr, nullptr);
+  }
+  const size_t bytes = n_words * 4;
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  if (int e = lane.lane->d_out.ensure(bytes + 64))
+    return e;
+  hipStream_t s = lane.lane->stream;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(lane.lane->d_out.ptr, in, bytes, hipMemcpyHostToDevice, s));
+  }
+  if (int rc = rsx_plan_run(call.plan, lane.lane->d_out.ptr, lane.lane->d_out.ptr, s))
+    return rc;
+  // (download_rects stages what is off the 16-byte grid row by row: rows of 64 KiB, then the rest)
+  const uint8_t* dev = static_cast<const uint8_t*>(lane.lane->d_out.ptr);
+  constexpr size_t ROW = size_t(64) << 10;
+  const size_t rows = bytes / ROW;
+  const DownRect body{out, ROW, dev, ROW, ROW, rows};
+  const DownRect rest{out + rows * ROW, 0, dev + rows * ROW, 0, bytes - rows * ROW, 1};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  if (int e = download_rects(ctx, lane.lane, s, &body, 1))
+    return e;
+  return download_rects(ctx, lane.lane, s, &rest, 1);
+}
+
+// Device pointers: as above.  Host pointers (single_image_host): the 2 dim_x dim_y bytes go up as
+// one copy; the plan is keyed by the geometry and the key, whose table it holds.
+extern "C" int rsx_sony_srf_decompress(rsx_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                       uint32_t key, const rsx_image* img) {
+  if (!ctx || !in || !img || !img->data)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_sony_srf::validate(in_bytes, img))
+    return st;
+  if (reinterpret_cast<uintptr_t>(img->data) % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool in_dev = is_device_pointer(in), out_dev = is_device_pointer(img->data);
+  if (in_dev != out_dev)
+    return RSX_ERR_INVALID_ARG;
+  const size_t span = 2 * size_t(img->dim_x) * size_t(img->dim_y);
+  rsx_sony_srf_job job;
+  one_job_init(job, span, img);
+  job.key = key;
+  if (in_dev) {
+    CallPlan call;
+    if (int st = rsx_sony_srf_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    return call.run(in, img->data, nullptr);
+  }
+  std::vector<uint8_t> plan_key = one_job_key(rsx_sony_srf_plan_create, job);
+  return single_image_host(ctx, plan_key, rsx_sony_srf_plan_create, job, in, span, img, nullptr);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

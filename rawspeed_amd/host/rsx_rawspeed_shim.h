@@ -362,6 +362,39 @@ inline int crw(const Array1DRef<const uint8_t>& input, const Array1DRef<const ui
                             low ? size_t(low->size()) : 0, &v);
 }
 
+// RafDecoder::applyCorrections(): the 45 degree rotation of `img` (not yet
+// cropped: the crop is the descriptor's) into a new image, which replaces *rotated on RSX_OK with
+// fujiRotationPos set; on any other status *rotated is untouched and the hunk falls through
+inline int raf_rotate(const RawImage& img, iPoint2D crop_offset, iPoint2D new_size, bool alt_layout,
+                      RawImage* rotated) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  const rsx_raf_rotate_desc d = {crop_offset.x, crop_offset.y, new_size.x,
+                                 new_size.y,    alt_layout ? 1 : 0, 0};
+  int32_t dim_x = 0, dim_y = 0, pos = 0;
+  if (int st = rsx_raf_rotate_geometry(&d, &dim_x, &dim_y, &pos))
+    return st;
+  RawImage out = RawImage::create(iPoint2D(dim_x, dim_y), RawImageType::UINT16, 1);
+  const rsx_image src = view(img), dst = view(out);
+  if (int st = rsx_raf_rotate(rsx, &d, &src, &dst))
+    return st;
+  out->metadata = img->metadata;
+  out->metadata.fujiRotationPos = implicit_cast<uint32_t>(pos);
+  *rotated = out;
+  return RSX_OK;
+}
+
+// ArwDecoder::decodeSRF(): `data` is the image buffer at its fixed offset,
+// `key` the key behind the reference's derivation; `img` has its dimensions and its data
+inline int sony_srf(const Array1DRef<const uint8_t>& data, uint32_t key, const RawImage& img) {
+  rsx_ctx* rsx = context();
+  if (!rsx)
+    return RSX_ERR_DEVICE;
+  const rsx_image v = view(img);
+  return rsx_sony_srf_decompress(rsx, data.begin(), size_t(data.size()), key, &v);
+}
+
 // DngDecoder::decodeRawInternal() / handleMetadata(): what follows the tiles --
 // OpcodeList1 and the LinearizationTable look-up -- handed to the tile fan-out so that it runs on
 // the device in front of the ONE download.  The hunk fills this BEFORE decodeData (the entries,
