@@ -1913,6 +1913,91 @@ int rsx_scale_black_white(rsx_ctx* ctx, const rsx_scale_desc* desc, const rsx_im
                           rsx_scale_result* result);
 
 /* ------------------------------------------------------------------------ */
+/* 4f. DngDecoder's branch for lossy DNGs, end to end                        */
+/*    (placed here, behind the stages it chains: it needs their types)       */
+/*    replaces, for compression 0x884c, the tiles of section 4e, then        */
+/*    DngDecoder::handleMetadata (decoders/DngDecoder.cpp:591-634) and       */
+/*    RawDecoder::decodeRaw()'s last step (decoders/RawDecoder.cpp:327-328): */
+/*    OpcodeList1 (:591-605), the LinearizationTable look-up (:607-615),     */
+/*    setBlack (:618, the caller's: it fills `scale`), scaleBlackWhite()     */
+/*    (:624), OpcodeList2 (:627-634), fixBadPixels.  Every stage is the      */
+/*    stage of section 4d, 6 and 5, bit for bit, on one staged image: ONE    */
+/*    upload of the tiles, ONE download.  The caller keeps the metadata tail */
+/*    of :635-642 (blackAreas.clear(), black 0, white 65535).                */
+/*    Without has_list2 (no OPCODELIST2 entry, or uncorrectedRawValues):     */
+/*    what rsx_dng_decompress_ljpeg_post / _finish are for LJPEG tiles, with */
+/*    JPEG tiles -- tiles, list 1, look-up, `fix`, the download.  scale,     */
+/*    opcodes2 are ignored; result->scale and ->list2 are zero.              */
+/*    With has_list2: the scale stage runs behind the look-up on the crop    */
+/*    list 1 left: scale.off_x, off_y, crop_x, crop_y must equal list1.crop_x*/
+/*    crop_y, crop_w, crop_h (the caller has them from rsx_dng_post_validate */
+/*    and needs them for setBlack), scale.is_f32 must be 0 ->                */
+/*    RSX_ERR_INVALID_ARG otherwise.  Then list 2, a DngOpcodes list without */
+/*    a table whose crop starts where list 1 left it; every rule of section  */
+/*    4d for verdicts, reasons and n_applied holds for it.  Unlike list 1,   */
+/*    an entry of 0 bytes is not "none": :628 has no `count > 0` guard, the  */
+/*    constructor's getU32 throws IOException -> RSX_ERR_IO.                 */
+/*    The positions are what mBadPixelPositions holds at the end (common/    */
+/*    DngOpcodes.cpp:180 inserts at the front, :320 appends): list 2's       */
+/*    FixBadPixelsList entries, list 1's, list 1's constant hits, list 2's   */
+/*    constant hits -- the latter taken on the SCALED image.  list1.n_bad +  */
+/*    list2.n_bad is always the exact count.                                 */
+/*    The checks that need no pixel, in this order (rsx_dng_lossy_validate   */
+/*    makes them all, fills both parses and hands out the FixBadPixelsList   */
+/*    positions; no device): desc or img NULL, stage1.is_f32 ->              */
+/*    RSX_ERR_INVALID_ARG; list 1 as rsx_dng_post_validate; list 2 likewise; */
+/*    the scale crop; rsx_scale_validate; fix with cpp > 1 and a FixBad-     */
+/*    PixelsList position in either list -> RSX_ERR_UNSUPPORTED (section 5). */
+/*    Any of them ends rsx_dng_lossy_decompress before anything is decoded.  */
+/*    Then, as the calls the stages extend:                                  */
+/*      tiles that parse and do not tile the image (section 4d) ->           */
+/*        RSX_ERR_UNSUPPORTED before anything is uploaded;                   */
+/*      a tile fails -> the plain call of section 4e: the good tiles are     */
+/*        written, RSX_ERR_TILE_ERRORS, stages = 0, the result carries the   */
+/*        parses alone;                                                      */
+/*      the scale stage refuses from the image's contents (white - black <=  */
+/*        0, the row seed) -> the image comes back as stage 1 left it,       */
+/*        stages = RSX_DNG_LOSSY_STAGE1, `bad` holds list 1's positions      */
+/*        alone and list2.n_bad is 0 (list 2's verdict stays the parse's),   */
+/*        RSX_ERR_UNSUPPORTED; the caller goes on from scaleBlackWhite();    */
+/*      more positions than bad_cap -> the image complete but UNFIXED,       */
+/*        RSX_ERR_UNSUPPORTED, `bad` unspecified (as the _finish calls).     */
+/*    RSX_DNG_LOSSY_FIXED is set when `fix` was asked for and the positions  */
+/*    fit, also when there were none (the reference then makes no map, and   */
+/*    map_out stays untouched).  tile_status is written only by a call that  */
+/*    wrote the image.  Pitch padding is never written.  img->data is a host */
+/*    pointer.  One host call in rsx_ctx_host_calls.                         */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_dng_lossy_desc {
+  rsx_dng_post_desc stage1; /* OpcodeList1 + LinearizationTable, as section 4d; is_f32 must be 0 */
+  int32_t has_list2;        /* the file has an OPCODELIST2 entry and !uncorrectedRawValues */
+  uint32_t opcodes2_bytes;
+  const uint8_t* opcodes2;  /* the entry's bytes as in the file */
+  rsx_scale_desc scale;     /* what RawImageData holds behind setBlack(); used only with has_list2 */
+  int32_t fix;              /* run fixBadPixels behind everything, in front of the download */
+  int32_t reserved;
+} rsx_dng_lossy_desc;
+
+#define RSX_DNG_LOSSY_STAGE1 1 /* list 1 + look-up applied */
+#define RSX_DNG_LOSSY_SCALED 2 /* scaleBlackWhite ran (it may have set result.scale.skipped) */
+#define RSX_DNG_LOSSY_LIST2 4
+#define RSX_DNG_LOSSY_FIXED 8
+typedef struct rsx_dng_lossy_result {
+  rsx_dng_post_result list1, list2;
+  rsx_scale_result scale;
+  rsx_bad_pixels_result fixed;
+  uint32_t stages; /* RSX_DNG_LOSSY_*: what the downloaded image has behind it */
+  uint32_t reserved;
+} rsx_dng_lossy_result;
+
+int rsx_dng_lossy_validate(const rsx_dng_lossy_desc* desc, const rsx_image* img,
+                           rsx_dng_lossy_result* result, uint32_t* bad, uint32_t bad_cap);
+int rsx_dng_lossy_decompress(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles,
+                             const rsx_dng_lossy_desc* desc, const rsx_image* img,
+                             int32_t* tile_status, rsx_dng_lossy_result* result, uint32_t* bad,
+                             uint32_t bad_cap, uint8_t* map_out);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */

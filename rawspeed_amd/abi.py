@@ -531,6 +531,43 @@ def scale_desc(crop, black_level=-1, white_point=None, black_separate=None, area
     return d, keep
 
 
+class DngLossyDesc(C.Structure):
+    """the lossy-DNG chain behind the JPEG tiles (include/rsx.h section 4f)"""
+    _fields_ = [("stage1", DngPostDesc), ("has_list2", C.c_int32), ("opcodes2_bytes", C.c_uint32),
+                ("opcodes2", C.c_void_p), ("scale", ScaleDesc), ("fix", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+DNG_LOSSY_STAGE1, DNG_LOSSY_SCALED, DNG_LOSSY_LIST2, DNG_LOSSY_FIXED = 1, 2, 4, 8
+
+
+class DngLossyResult(C.Structure):
+    _fields_ = [("list1", DngPostResult), ("list2", DngPostResult), ("scale", ScaleResult),
+                ("fixed", BadPixelsResult), ("stages", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def dng_lossy_desc(stage1, opcodes2=None, scale=None, fix=False, opcodes2_bytes=None):
+    """(rsx_dng_lossy_desc, keep-alive objects).  stage1: (DngPostDesc, keep) of dng_post_desc;
+    opcodes2: the OpcodeList2 entry's bytes (b"" is an entry of 0 bytes), None: no list 2;
+    scale: (ScaleDesc, keep) of scale_desc, needed with opcodes2."""
+    d = DngLossyDesc()
+    keep = [stage1[1]]
+    d.stage1 = stage1[0]
+    if opcodes2 is not None:
+        d.has_list2 = 1
+        if len(opcodes2):
+            a = np.frombuffer(bytes(opcodes2), dtype=np.uint8).copy()
+            d.opcodes2, d.opcodes2_bytes = a.ctypes.data, a.size
+            keep.append(a)
+    if opcodes2_bytes is not None:
+        d.opcodes2_bytes = opcodes2_bytes
+    if scale is not None:
+        d.scale = scale[0]
+        keep.append(scale[1])
+    d.fix = int(fix)
+    return d, keep
+
+
 class PanasonicV4Desc(C.Structure):
     _fields_ = [("section_split_offset", C.c_uint32), ("zero_is_bad", C.c_int32)]
 

@@ -51,6 +51,7 @@ EXPORTS = [
     "rsx_dng_deflate_validate", "rsx_dng_decompress_deflate", "rsx_dng_deflate_plan_create",
     "rsx_dng_jpeg_validate", "rsx_dng_decompress_jpeg", "rsx_dng_jpeg_plan_create",
     "rsx_dng_jpeg_plan_tile_status",
+    "rsx_dng_lossy_validate", "rsx_dng_lossy_decompress",
     "rsx_fuji_parse", "rsx_fuji_validate", "rsx_fuji_decompress", "rsx_fuji_plan_create",
     "rsx_fuji_plan_strip_status",
     "rsx_olympus_validate", "rsx_olympus_decompress", "rsx_olympus_plan_create",
@@ -194,6 +195,11 @@ def lib():
         L.rsx_dng_decompress_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
         L.rsx_dng_jpeg_plan_tile_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_dng_lossy_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_uint32]
+        L.rsx_dng_lossy_decompress.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_uint32, C.c_void_p]
         L.rsx_fuji_parse.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsx_fuji_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_fuji_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -345,6 +351,19 @@ def dng_post_validate(desc, img_view, bad_cap=1 << 16):
                                      None if img_view is None else C.byref(img_view),
                                      C.byref(r), buf, bad_cap)
     return st, r, _bad_out(r, buf, st)
+
+
+def dng_lossy_validate(desc, img_view, bad_cap=1 << 16):
+    """rsx_dng_lossy_validate; desc: abi.DngLossyDesc (abi.dng_lossy_desc), None passes NULL.
+    Returns (status, abi.DngLossyResult, the FixBadPixelsList positions of both lists or None)."""
+    r = abi.DngLossyResult()
+    buf = (C.c_uint32 * max(1, bad_cap))()
+    st = lib().rsx_dng_lossy_validate(None if desc is None else C.byref(desc),
+                                      None if img_view is None else C.byref(img_view),
+                                      C.byref(r), buf, bad_cap)
+    if st != abi.RSX_OK:
+        return st, r, None
+    return st, r, [int(v) for v in buf[:r.list1.n_bad + r.list2.n_bad]]
 
 
 def scale_validate(desc, img_view):
@@ -860,6 +879,24 @@ class Context:
         st = (C.c_int32 * n)()
         rc = lib().rsx_dng_decompress_jpeg(self._h, n, tiles, C.byref(img_view), st)
         return rc, list(st)
+
+    def dng_lossy_decompress(self, streams, offsets, desc, img_view, bad_cap=1 << 16):
+        """The lossy-DNG chain: the JPEG tiles, then list 1 and the look-up, the scaling, list 2 and
+        the fix of `desc` (abi.DngLossyDesc) on the device, one download.  Returns (status, tile
+        statuses -- -1 where the call did not write them, abi.DngLossyResult, the positions or None
+        when they did not fit or no stage ran, the map -- 0xA5 unless made)."""
+        n = len(streams)
+        tiles, keep = abi.dng_jpeg_tiles(streams, offsets)
+        st = (C.c_int32 * n)(*([-1] * n))
+        r = abi.DngLossyResult()
+        buf = (C.c_uint32 * max(1, bad_cap))()
+        m = np.full((img_view.dim_y, abi.bad_pixels_map_pitch(img_view.dim_x)), 0xA5, np.uint8)
+        rc = lib().rsx_dng_lossy_decompress(self._h, n, tiles, C.byref(desc), C.byref(img_view), st,
+                                            C.byref(r), buf, bad_cap, m.ctypes.data)
+        n_bad = r.list1.n_bad + r.list2.n_bad
+        bad = [int(v) for v in buf[:n_bad]] if r.stages and n_bad <= bad_cap else None
+        del keep
+        return rc, list(st), r, bad, m
 
     def dng_decompress_ljpeg(self, descs, datas, img_view):
         n = len(descs)

@@ -2861,13 +2861,26 @@ extern "C" int rsx_dng_jpeg_plan_tile_status(rsx_plan* plan, int job, int32_t* t
 // The host-pointer call: the tiles' bytes packed into one upload, one run of a plan made for the
 // call (its key would be the streams themselves), the windows of the tiles that decoded back
 // through download_rects -- as one rectangle where they fill their bounding box.
-extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles,
-                                       const rsx_image* img, int32_t* tile_status) {
+//
+// before_download (may be NULL; rsx_dng_lossy_decompress): what the call does to the decoded image
+// on the device in front of the download, as in ljpeg_family_host.  The tiles' windows must then
+// tile the whole image (rects_tile_image): a call whose tiles parse and do not returns
+// RSX_ERR_UNSUPPORTED before anything is uploaded or decoded.  It runs only when every tile
+// decoded, and the whole image then goes back as one rectangle; with a failing tile the call is
+// the plain call.  *wrote (may be NULL): the call reached its download (or had nothing to decode),
+// so tile_status holds the tiles' statuses.
+namespace {
+int dng_jpeg_host(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles, const rsx_image* img,
+                  int32_t* tile_status, bool count_call, const DevicePostFn* before_download,
+                  bool* wrote) {
+  if (wrote)
+    *wrote = false;
   if (!ctx || !tiles || n_tiles < 1 || !img || !img->data)
     return RSX_ERR_INVALID_ARG;
   if (img->dim_x <= 0 || img->dim_y <= 0 || img->pitch_bytes == 0)
     return RSX_ERR_INVALID_ARG;
-  ++ctx->host_calls;
+  if (count_call)
+    ++ctx->host_calls;
   std::vector<uint64_t> offs(n_tiles);
   size_t in_total = 0;
   for (int i = 0; i < n_tiles; ++i) {
@@ -2887,6 +2900,20 @@ extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_
   if (int st = rsx_dng_jpeg_plan_create(ctx, 1, &job, &cp.plan))
     return st;
   const std::vector<JpegWindow>& win = dng_jpeg_plan_windows(cp.plan->dec.get(), 0);
+  if (before_download) {
+    bool parsed = true;
+    std::vector<HostRect> all;
+    all.reserve(win.size());
+    for (const JpegWindow& w : win) {
+      parsed = parsed && w.host_status == RSX_OK;
+      all.push_back(HostRect{size_t(w.off_y), size_t(w.copy_h), size_t(w.off_x) * w.cpp * 2,
+                             size_t(w.copy_w) * w.cpp * 2});
+    }
+    // (a tile that does not parse has no window: a failing tile, the plain call)
+    if (parsed && (img->cpp < 1 || !rects_tile_image(std::move(all), size_t(img->dim_y),
+                                                     size_t(img->dim_x) * size_t(img->cpp) * 2)))
+      return RSX_ERR_UNSUPPORTED;
+  }
   // the output staging holds the image rows the windows cover
   size_t row_lo = size_t(img->dim_y), row_hi = 0;
   for (const JpegWindow& w : win)
@@ -2929,6 +2956,7 @@ extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_
         rects.push_back(HostRect{size_t(win[i].off_y), size_t(win[i].copy_h),
                                  size_t(win[i].off_x) * win[i].cpp * 2,
                                  size_t(win[i].copy_w) * win[i].cpp * 2});
+    const bool all_decoded = rects.size() == size_t(n_tiles);
     if (rects.size() > 1) {
       size_t r0 = ~size_t(0), r1 = 0, b0 = ~size_t(0), b1 = 0;
       for (const HostRect& r : rects) {
@@ -2946,6 +2974,12 @@ extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_
       if (rects_tile_image(std::move(rel), r1 - r0, b1 - b0))
         rects.assign(1, HostRect{r0, r1 - r0, b0, b1 - b0});
     }
+    if (before_download && all_decoded) {
+      if (int e = (*before_download)(out_row0, s))
+        return e;
+      // (the windows tile the image, checked on the way in: one rectangle, however many tiles)
+      rects.assign(1, HostRect{0, size_t(img->dim_y), 0, size_t(img->dim_x) * size_t(img->cpp) * 2});
+    }
     std::vector<DownRect> down;
     down.reserve(rects.size());
     for (const HostRect& r : rects) {
@@ -2960,12 +2994,20 @@ extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_
     for (int i = 0; i < n_tiles; ++i)
       st[i] = win[i].host_status;
   }
+  if (wrote)
+    *wrote = true;
   if (tile_status)
     std::copy(st.begin(), st.end(), tile_status);
   for (int i = 0; i < n_tiles; ++i)
     if (st[i] != RSX_OK)
       return RSX_ERR_TILE_ERRORS; // AbstractDngDecompressor.cpp:247-251
   return RSX_OK;
+}
+} // namespace
+
+extern "C" int rsx_dng_decompress_jpeg(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles,
+                                       const rsx_image* img, int32_t* tile_status) {
+  return dng_jpeg_host(ctx, n_tiles, tiles, img, tile_status, true, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -3762,6 +3804,224 @@ extern "C" int rsx_dng_decompress_uncompressed_finish(rsx_ctx* ctx, int n_tiles,
   fix.map_out = map_out;
   return dng_uncompressed_post_call(ctx, n_tiles, tiles, desc, img, tile_status, result, bad,
                                     bad_cap, fix);
+}
+
+// ---------------------------------------------------------------------------
+// DngDecoder's branch for lossy DNGs: JPEG tiles, OpcodeList1 and the look-up, scaleBlackWhite,
+// OpcodeList2, fixBadPixels -- every stage the plan its stand-alone call runs, on the one staged
+// image and the one stream, ONE download.
+// ---------------------------------------------------------------------------
+namespace {
+// a list's verdict and its FixBadPixelsList positions, whatever their number
+int dng_lossy_parse(const rsx_dng_post_desc* d, const rsx_image* img, rsx_dng_post_result* r,
+                    std::vector<uint32_t>* fixed) {
+  fixed->clear();
+  std::memset(r, 0, sizeof *r);
+  int st = dng_post_validate(d, img, r, nullptr, 0);
+  if (st == RSX_ERR_UNSUPPORTED && r->n_bad != 0) { // (refused for the capacity alone)
+    fixed->resize(size_t(r->n_bad));
+    st = dng_post_validate(d, img, r, fixed->data(), uint32_t(fixed->size()));
+  }
+  return st;
+}
+
+// Every check of the chain that needs no pixel, in this order: list 1, list 2, the scale stage's
+// crop and descriptor, the fix.  `r` receives both parses, *d2 list 2 as a descriptor of its own.
+int dng_lossy_check(const rsx_dng_lossy_desc* desc, const rsx_image* img, rsx_dng_lossy_result* r,
+                    std::vector<uint32_t>* fixed1, std::vector<uint32_t>* fixed2,
+                    rsx_dng_post_desc* d2) {
+  std::memset(r, 0, sizeof *r);
+  fixed1->clear();
+  fixed2->clear();
+  if (!desc || !img)
+    return RSX_ERR_INVALID_ARG;
+  if (desc->stage1.is_f32)
+    return RSX_ERR_INVALID_ARG; // (JPEG tiles decode to uint16)
+  if (int st = dng_lossy_parse(&desc->stage1, img, &r->list1, fixed1))
+    return st;
+  if (desc->has_list2) {
+    // (DngDecoder.cpp:628 has no `count > 0` guard: the constructor's getU32 throws IOException)
+    if (desc->opcodes2_bytes == 0)
+      return RSX_ERR_IO;
+    std::memset(d2, 0, sizeof *d2);
+    d2->opcodes = desc->opcodes2;
+    d2->opcodes_bytes = desc->opcodes2_bytes;
+    d2->crop_x = r->list1.crop_x;
+    d2->crop_y = r->list1.crop_y;
+    d2->crop_w = r->list1.crop_w;
+    d2->crop_h = r->list1.crop_h;
+    if (int st = dng_lossy_parse(d2, img, &r->list2, fixed2)) {
+      std::memset(&r->list2, 0, sizeof r->list2);
+      return st;
+    }
+    const rsx_scale_desc& sc = desc->scale;
+    if (sc.is_f32 || sc.off_x != r->list1.crop_x || sc.off_y != r->list1.crop_y ||
+        sc.crop_x != r->list1.crop_w || sc.crop_y != r->list1.crop_h)
+      return RSX_ERR_INVALID_ARG;
+    if (int st = scale_validate(&sc, img))
+      return st;
+  }
+  // cpp > 1 with positions: refused before anything is decoded (section 5)
+  if (desc->fix && img->cpp > 1 && (!fixed1->empty() || !fixed2->empty()))
+    return RSX_ERR_UNSUPPORTED;
+  return RSX_OK;
+}
+
+// mBadPixelPositions behind both lists: list 2's FixBadPixelsList entries went to the front, its
+// constant hits to the back (common/DngOpcodes.cpp:180, :320).  b1, b2: what each pass composed,
+// n_fixed2 of b2 list entries.
+void dng_lossy_merge(const std::vector<uint32_t>& b1, const std::vector<uint32_t>& b2,
+                     size_t n_fixed2, uint32_t* out) {
+  out = std::copy(b2.begin(), b2.begin() + n_fixed2, out);
+  out = std::copy(b1.begin(), b1.end(), out);
+  std::copy(b2.begin() + n_fixed2, b2.end(), out);
+}
+
+// the positions a pass composed; RSX_ERR_UNSUPPORTED (with *n exact) when they are more than cap
+int dng_lossy_positions(const CallPlan& call, uint64_t cap, std::vector<uint32_t>* out, uint64_t* n) {
+  out->clear();
+  const int st = call.plan->dec->bad_pixels(0, nullptr, 0, n);
+  if (st != RSX_OK && st != RSX_ERR_UNSUPPORTED)
+    return st;
+  if (*n == 0)
+    return RSX_OK;
+  if (*n > cap)
+    return RSX_ERR_UNSUPPORTED;
+  out->resize(size_t(*n));
+  return call.plan->dec->bad_pixels(0, out->data(), uint32_t(*n), n);
+}
+} // namespace
+
+extern "C" int rsx_dng_lossy_validate(const rsx_dng_lossy_desc* desc, const rsx_image* img,
+                                      rsx_dng_lossy_result* result, uint32_t* bad,
+                                      uint32_t bad_cap) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!bad && bad_cap != 0)
+    return RSX_ERR_INVALID_ARG;
+  rsx_dng_lossy_result r;
+  std::vector<uint32_t> f1, f2;
+  rsx_dng_post_desc d2;
+  const int st = dng_lossy_check(desc, img, &r, &f1, &f2, &d2);
+  if (result)
+    *result = r;
+  if (st != RSX_OK)
+    return st;
+  if (f1.size() + f2.size() > bad_cap)
+    return RSX_ERR_UNSUPPORTED;
+  if (bad)
+    dng_lossy_merge(f1, f2, f2.size(), bad);
+  return RSX_OK;
+}
+
+extern "C" int rsx_dng_lossy_decompress(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile* tiles,
+                                        const rsx_dng_lossy_desc* desc, const rsx_image* img,
+                                        int32_t* tile_status, rsx_dng_lossy_result* result,
+                                        uint32_t* bad, uint32_t bad_cap, uint8_t* map_out) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !tiles || n_tiles < 1 || !desc || !img || !img->data || (!bad && bad_cap != 0))
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  rsx_dng_lossy_result R;
+  std::vector<uint32_t> f1, f2;
+  rsx_dng_post_desc d2;
+  const int checked = dng_lossy_check(desc, img, &R, &f1, &f2, &d2);
+  if (result)
+    *result = R;
+  if (checked != RSX_OK)
+    return checked;
+  const bool two = desc->has_list2 != 0;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CallPlan list1, scale, list2;
+  if (int st = dng_post_call_create(ctx, &desc->stage1, img, bad_cap, list1))
+    return st;
+  if (two) {
+    auto job = std::make_unique<rsx_scale_job>();
+    std::memset(job.get(), 0, sizeof(rsx_scale_job));
+    job->desc = desc->scale;
+    job->img = *img;
+    job->img.data = nullptr;
+    if (int st = rsx_scale_plan_create(ctx, 1, job.get(), &scale.plan))
+      return st;
+    if (int st = dng_post_call_create(ctx, &d2, img, bad_cap, list2))
+      return st;
+  }
+  PositionsFixStage fix;
+  uint32_t stages = 0;
+  uint64_t n1 = 0, n2 = 0;
+  std::vector<uint32_t> b1, b2;
+  bool refused = false, fits = false;
+  const DevicePostFn post = [&](uint8_t* dev, hipStream_t s) {
+    if (int e = dng_post_run(list1, dev, s))
+      return e;
+    stages = RSX_DNG_LOSSY_STAGE1;
+    if (two) {
+      if (int e = rsx_plan_run(scale.plan, dev, dev, s))
+        return e;
+      const int e = rsx_plan_results(scale.plan, nullptr, nullptr);
+      if (e == RSX_ERR_UNSUPPORTED) { // (refused from the image's contents: nothing written)
+        refused = true;
+      } else if (e != RSX_OK) {
+        return e;
+      } else {
+        stages |= RSX_DNG_LOSSY_SCALED;
+        if (int e2 = dng_post_run(list2, dev, s))
+          return e2;
+        stages |= RSX_DNG_LOSSY_LIST2;
+      }
+    }
+    // the positions: the image is complete whether they fit or not
+    const int p1 = dng_lossy_positions(list1, bad_cap, &b1, &n1);
+    if (p1 != RSX_OK && p1 != RSX_ERR_UNSUPPORTED)
+      return p1;
+    int p2 = RSX_OK;
+    if (stages & RSX_DNG_LOSSY_LIST2) {
+      p2 = dng_lossy_positions(list2, bad_cap, &b2, &n2);
+      if (p2 != RSX_OK && p2 != RSX_ERR_UNSUPPORTED)
+        return p2;
+    }
+    fits = p1 == RSX_OK && p2 == RSX_OK && n1 + n2 <= bad_cap;
+    if (!fits)
+      return int(RSX_OK);
+    // (b2 is what list 2's pass composed: empty, list entries included, where it did not run)
+    if (n1 + n2 != 0)
+      dng_lossy_merge(b1, b2, std::min(f2.size(), b2.size()), bad);
+    if (!desc->fix || refused)
+      return int(RSX_OK);
+    if (n1 + n2 != 0) // (none: the reference makes no map)
+      if (int e = fix.run_positions(ctx, bad, uint32_t(n1 + n2), 0, img, dev, s))
+        return e;
+    stages |= RSX_DNG_LOSSY_FIXED;
+    return int(RSX_OK);
+  };
+  std::vector<int32_t> st(size_t(n_tiles), RSX_OK);
+  bool wrote = false;
+  const int rc = dng_jpeg_host(ctx, n_tiles, tiles, img, st.data(), false, &post, &wrote);
+  // (tile_status is written only by a call that wrote the image)
+  if (!wrote)
+    return rc != RSX_OK ? rc : int(RSX_ERR_DEVICE);
+  if (tile_status)
+    std::copy(st.begin(), st.end(), tile_status);
+  if (rc != RSX_OK)
+    return rc; // (a tile failed: the plain call; the result carries the parses alone)
+  if (stages == 0)
+    return RSX_ERR_DEVICE;
+  dng_post_finish(list1, &R.list1, nullptr, 0, false); // (n_bad: the exact count behind the run)
+  if (stages & RSX_DNG_LOSSY_SCALED)
+    if (int e = scale.plan->dec->scale_result(0, &R.scale))
+      return e;
+  if (stages & RSX_DNG_LOSSY_LIST2)
+    dng_post_finish(list2, &R.list2, nullptr, 0, false);
+  else
+    R.list2.n_bad = 0; // (the parse's verdict stays; none of its positions is in `bad`)
+  if (fix.ran)
+    if (int e = bad_pixels_finish(fix.fix, &R.fixed, map_out))
+      return e;
+  R.stages = stages;
+  if (result)
+    *result = R;
+  return refused || !fits ? int(RSX_ERR_UNSUPPORTED) : int(RSX_OK);
 }
 
 // ---------------------------------------------------------------------------

@@ -459,6 +459,116 @@ struct DngPost {
   }
 };
 
+// DngDecoder::decodeRawInternal() / handleMetadata() for compression 0x884c:
+// the whole branch for lossy DNGs -- the JPEG tiles, OpcodeList1, the look-up, scaleBlackWhite(),
+// OpcodeList2 and, for a caller that interpolates bad pixels, fixBadPixels() -- as ONE call with
+// one download (include/rsx.h section 4f).  The hunk fills `stage1` as in 3q, calls setBlack()
+// (it reads the IFD alone) and then set(); run() is the tile call; finish() does to mRaw what the
+// stages that ran would have done.  What `result.stages` does not name is left to handleMetadata
+// as it is: nothing of it after a failing tile, scaleBlackWhite() onwards after a scale stage that
+// refused from the image.
+struct DngLossy {
+  DngPost stage1;
+  rsx_dng_lossy_desc d{};
+  std::vector<rsx_scale_area> areas;
+  rsx_dng_lossy_result result{};
+  std::vector<uint32_t> bad;
+  std::vector<uint8_t> map;
+  // opcodes2: the OPCODELIST2 entry's bytes, an entry of 0 bytes included (nullptr: no entry, or
+  // uncorrectedRawValues); `img`: mRaw behind setBlack(), dim and cpp set; fix: the caller
+  // interpolates bad pixels.  False: this core refuses the file's lists or levels, or the file
+  // fails -- handleMetadata does what it always did, and throws what it always threw.
+  bool set(const Buffer* opcodes2, const RawImage& img, bool fix, bool host_sse2) {
+    d = rsx_dng_lossy_desc{};
+    d.stage1 = stage1.d;
+    d.has_list2 = opcodes2 ? 1 : 0;
+    d.opcodes2 = opcodes2 ? opcodes2->begin() : nullptr;
+    d.opcodes2_bytes = opcodes2 ? opcodes2->getSize() : 0;
+    d.fix = fix ? 1 : 0;
+    rsx_image v{};
+    v.dim_x = img->getUncroppedDim().x;
+    v.dim_y = img->getUncroppedDim().y;
+    v.cpp = implicit_cast<int32_t>(img->getCpp());
+    v.pitch_bytes = implicit_cast<uint32_t>(v.dim_x) * implicit_cast<uint32_t>(v.cpp) * 2U;
+    v.is_cfa = img->isCFA ? 1 : 0;
+    rsx_dng_post_result r1{};
+    const int st1 = rsx_dng_post_validate(&d.stage1, &v, &r1, nullptr, 0);
+    if (st1 != RSX_OK && !(st1 == RSX_ERR_UNSUPPORTED && r1.n_bad != 0))
+      return false;
+    if (d.has_list2) {
+      // the scale stage works on the crop list 1 leaves, with what setBlack() left in mRaw
+      areas.clear();
+      for (const BlackArea& a : img->blackAreas)
+        areas.push_back({a.offset, a.size, a.isVertical ? 1 : 0, 0});
+      rsx_scale_desc& s = d.scale;
+      s.off_x = r1.crop_x;
+      s.off_y = r1.crop_y;
+      s.crop_x = r1.crop_w;
+      s.crop_y = r1.crop_h;
+      s.black_level = img->blackLevel;
+      s.has_white = img->whitePoint.has_value() ? 1 : 0;
+      s.white_point = img->whitePoint.value_or(0);
+      s.has_separate = img->blackLevelSeparate.has_value() ? 1 : 0;
+      if (img->blackLevelSeparate)
+        std::copy_n(img->blackLevelSeparateStorage.begin(), 4, s.black_separate);
+      s.n_areas = implicit_cast<uint32_t>(areas.size());
+      s.areas = areas.empty() ? nullptr : areas.data();
+      s.dither = img->mDitherScale ? 1 : 0;
+      s.host_sse2 = host_sse2 ? 1 : 0;
+    }
+    const int st = rsx_dng_lossy_validate(&d, &v, &result, nullptr, 0);
+    if (st != RSX_OK && !(st == RSX_ERR_UNSUPPORTED && result.list1.n_bad + result.list2.n_bad != 0))
+      return false;
+    const bool any_list = d.stage1.opcodes_bytes != 0 || d.has_list2;
+    const uint64_t room = result.list1.n_bad + result.list2.n_bad +
+                          (any_list && v.cpp == 1 ? 2U * DngPost::MaxConstantHits : 0U);
+    bad.assign(implicit_cast<size_t>(std::min<uint64_t>(room, 1U << 26)), 0);
+    // (re-checked against the room: fix with cpp > 1 and positions is refused here)
+    return rsx_dng_lossy_validate(&d, &v, &result, bad.data(),
+                                  implicit_cast<uint32_t>(bad.size())) == RSX_OK;
+  }
+  // the tile call; `status` per tile, written only when the image was
+  int run(const std::vector<rsx_dng_jpeg_tile>& tiles, const RawImage& img, int32_t* status) {
+    rsx_ctx* rsx = context();
+    if (!rsx)
+      return RSX_ERR_DEVICE;
+    const rsx_image v = view(img);
+    const uint32_t map_pitch = roundUp((implicit_cast<uint32_t>(v.dim_x) + 7U) / 8U, 16U);
+    map.assign(d.fix ? size_t(map_pitch) * size_t(v.dim_y) : 0U, 0);
+    return rsx_dng_lossy_decompress(rsx, implicit_cast<int>(tiles.size()), tiles.data(), &d, &v, status,
+                                    &result, bad.empty() ? nullptr : bad.data(),
+                                    implicit_cast<uint32_t>(bad.size()), map.empty() ? nullptr : map.data());
+  }
+  // the stages the call ran (RSX_OK, or RSX_ERR_UNSUPPORTED with result.stages != 0), behind
+  // handleMetadata's own subFrames: the logged errors, the lists' TrimBounds as a subFrame, the
+  // levels scaleBlackWhite() leaves, the positions.  True: the branch of :621-643 is done but for
+  // its metadata tail (:635-642), which the hunk keeps.
+  bool finish(const RawImage& img) const {
+    if (!(result.stages & RSX_DNG_LOSSY_STAGE1))
+      return false;
+    const bool list2 = (result.stages & RSX_DNG_LOSSY_LIST2) != 0;
+    if (result.list1.list_status != RSX_OK || (list2 && result.list2.list_status != RSX_OK))
+      img->setError("rsx: DNG opcode list refused as the reference's parser refuses it");
+    const rsx_dng_post_result& last = list2 ? result.list2 : result.list1;
+    const iPoint2D off = img->getCropOffset();
+    const iRectangle2D trimmed(last.crop_x - off.x, last.crop_y - off.y, last.crop_w, last.crop_h);
+    if (!(trimmed.pos == iPoint2D(0, 0)) || !(trimmed.dim == img->dim))
+      img->subFrame(trimmed);
+    if (result.stages & RSX_DNG_LOSSY_SCALED) {
+      img->blackLevel = result.scale.black_level;
+      if (result.scale.estimated || img->whitePoint)
+        img->whitePoint = result.scale.white_point;
+    }
+    const uint64_t n = result.list1.n_bad + (list2 ? result.list2.n_bad : 0U);
+    if (n != 0 && n <= bad.size() && !(result.stages & RSX_DNG_LOSSY_FIXED)) {
+      MutexLocker guard(&img->mBadPixelMutex);
+      img->mBadPixelPositions.insert(img->mBadPixelPositions.begin(), bad.begin(),
+                                     bad.begin() + implicit_cast<std::ptrdiff_t>(n));
+    }
+    return list2 || !d.has_list2;
+  }
+};
+
 // status -> the exception the reference would have thrown
 [[noreturn]] inline void raise(int st) {
   switch (st) {
