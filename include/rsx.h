@@ -1998,6 +1998,52 @@ int rsx_dng_lossy_decompress(rsx_ctx* ctx, int n_tiles, const rsx_dng_jpeg_tile*
                              uint32_t bad_cap, uint8_t* map_out);
 
 /* ------------------------------------------------------------------------ */
+/* 4g. The image hash of rstest and the sums of rawspeed-identify            */
+/*    replaces imgDataHash (utilities/rstest/rstest.cpp:131-146), "md5sum of */
+/*    per-line md5sums", and the byte sum and uint16_t sum of                */
+/*    utilities/identify/rawspeed-identify.cpp:235-283, on an image that     */
+/*    stays on the device: 16 dim_y + 32 bytes come back, not the image.     */
+/*    The image is the UNCROPPED one; its samples are sample_bytes = 2       */
+/*    (UINT16) or 4 (F32) bytes each (rsx_image has no type field).  With    */
+/*    row_bytes = dim_x cpp sample_bytes:                                    */
+/*      line[j]    the 16-byte MD5 (RFC 1321) of the row_bytes bytes of row  */
+/*                 j as stored (little-endian samples); bytes of the pitch   */
+/*                 beyond row_bytes never reach a result;                    */
+/*      md5        the MD5 of the 16 dim_y bytes line[0] .. line[dim_y - 1]; */
+/*      byte_sum   the sum of all row_bytes dim_y bytes;                     */
+/*      sample_sum the sum of all samples read as uint16_t for 2-byte        */
+/*                 images, 0 for 4-byte images.                              */
+/*    A digest's bytes are the state words A, B, C, D in little-endian order */
+/*    (hashlib's digest(); the reference's md5::state_type in memory on a    */
+/*    little-endian host).  The reference accumulates both sums in double;   */
+/*    both stay below 2^53, so double(sum) is its value exactly.  identify's */
+/*    sum of F32 samples is left out: the reference's value depends on how   */
+/*    OpenMP splits the rows among threads and combines them, so there is no */
+/*    one answer to match.  Results are the same from run to run: nothing is */
+/*    added in an order that can vary.                                       */
+/*    rsx_image_hash_validate, in this order: img NULL; sample_bytes not 2   */
+/*    or 4; cpp < 1, dim_x < 1 or dim_y < 1; pitch_bytes < row_bytes or not  */
+/*    a multiple of sample_bytes -> RSX_ERR_INVALID_ARG; row_bytes >= 2^28   */
+/*    or dim_y >= 2^24 -> RSX_ERR_UNSUPPORTED (this keeps every MD5 chain    */
+/*    far below the upper word of the bit count, which is written as 64 bits */
+/*    all the same).                                                         */
+/*    rsx_image_hash: img->data is a host or a device pointer (a multiple of */
+/*    sample_bytes; ctx, data or out NULL -> RSX_ERR_INVALID_ARG); line_md5  */
+/*    (16 dim_y bytes, may be NULL) and out are host pointers.  With a       */
+/*    device pointer nothing but the 16 dim_y + 32 bytes crosses the link.   */
+/*    One host call in rsx_ctx_host_calls.  It runs a plan of one job.       */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_image_hash_result {
+  uint8_t md5[16];
+  uint64_t byte_sum;
+  uint64_t sample_sum;
+} rsx_image_hash_result;
+
+int rsx_image_hash_validate(const rsx_image* img, int32_t sample_bytes);
+int rsx_image_hash(rsx_ctx* ctx, const rsx_image* img, int32_t sample_bytes, uint8_t* line_md5,
+                   rsx_image_hash_result* out);
+
+/* ------------------------------------------------------------------------ */
 /* Device-resident plans (inputs/outputs already in HBM).                    */
 /*                                                                           */
 /* A plan is "validate + size scratch + upload tables once, launch many".   */
@@ -2381,6 +2427,28 @@ typedef struct rsx_sony_srf_job {
 
 int rsx_sony_srf_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_sony_srf_job* jobs,
                              rsx_plan** out_plan);
+
+/* one image hash (section 4g): rsx_plan_run(plan, images_base, outputs_base, stream).  The image
+ * lies at img_offset (a multiple of sample_bytes, as images_base and the pitch are) in the run's
+ * input buffer.  Into the run's output buffer (outputs_base a multiple of 16) go the 16 dim_y bytes
+ * of the line digests at lines_offset (a multiple of 16) and the 32-byte rsx_image_hash_result at
+ * result_offset (a multiple of 8).  The two buffers may be one allocation as long as nothing
+ * overlaps.  Jobs of any mix of geometry and sample size share the plan's two launches, and their
+ * number is bounded by no grid axis.  A job rsx_image_hash_validate refuses (or whose offsets are
+ * off their grids: RSX_ERR_INVALID_ARG) has that status in rsx_plan_results and its outputs are
+ * untouched.  Job results report 0 bytes consumed.  The plan is stream-ordered: it can run right
+ * behind a decode plan on the same stream and buffer without a host wait. */
+typedef struct rsx_image_hash_job {
+  uint64_t img_offset;
+  uint64_t lines_offset;
+  uint64_t result_offset;
+  int32_t sample_bytes;
+  int32_t reserved;
+  rsx_image img; /* .data ignored */
+} rsx_image_hash_job;
+
+int rsx_image_hash_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_image_hash_job* jobs,
+                               rsx_plan** out_plan);
 
 int rsx_dng_jpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dng_jpeg_job* jobs,
                              rsx_plan** out_plan);

@@ -868,3 +868,36 @@ class SonySrfJob(C.Structure):
     """rsx_sony_srf_job (include/rsx.h section 3z)"""
     _fields_ = [("in_offset", C.c_uint64), ("in_bytes", C.c_uint64), ("img_offset", C.c_uint64),
                 ("key", C.c_uint32), ("reserved", C.c_uint32), ("img", Image)]
+
+
+class ImageHashResult(C.Structure):
+    """rsx_image_hash_result (include/rsx.h section 4g)"""
+    _fields_ = [("md5", C.c_uint8 * 16), ("byte_sum", C.c_uint64), ("sample_sum", C.c_uint64)]
+
+    def digest(self):
+        return bytes(self.md5)
+
+
+class ImageHashJob(C.Structure):
+    """rsx_image_hash_job: the image in the run's input buffer, the line digests and the result in
+    its output buffer"""
+    _fields_ = [("img_offset", C.c_uint64), ("lines_offset", C.c_uint64),
+                ("result_offset", C.c_uint64), ("sample_bytes", C.c_int32),
+                ("reserved", C.c_int32), ("img", Image)]
+
+
+def image_hash_job(img_offset, lines_offset, result_offset, sample_bytes, dim_x, dim_y, cpp,
+                   pitch_bytes):
+    j = ImageHashJob()
+    j.img_offset, j.lines_offset, j.result_offset = img_offset, lines_offset, result_offset
+    j.sample_bytes = sample_bytes
+    j.img = Image(None, pitch_bytes, dim_x, dim_y, cpp, 0)
+    return j
+
+
+def hex_joined_hash(line_md5):
+    """tests/golden_cases.image_hash's form of the image hash, from the 16 dim_y bytes of the line
+    digests: the MD5 of the concatenated hex digests"""
+    import hashlib
+    raw = bytes(line_md5)
+    return hashlib.md5(raw.hex().encode()).hexdigest()

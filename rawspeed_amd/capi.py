@@ -62,6 +62,7 @@ EXPORTS = [
     "rsx_raf_rotate_plan_create",
     "rsx_sony_decrypt", "rsx_sony_srf_validate", "rsx_sony_srf_decompress",
     "rsx_sony_srf_plan_create",
+    "rsx_image_hash_validate", "rsx_image_hash", "rsx_image_hash_plan_create",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -222,6 +223,8 @@ def lib():
         L.rsx_sony_srf_validate.argtypes = [C.c_size_t, C.c_void_p]
         L.rsx_sony_srf_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                               C.c_void_p]
+        L.rsx_image_hash_validate.argtypes = [C.c_void_p, C.c_int32]
+        L.rsx_image_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -250,7 +253,8 @@ def lib():
                      "rsx_scale_plan_create", "rsx_dng_jpeg_plan_create",
                      "rsx_fuji_plan_create", "rsx_olympus_plan_create",
                      "rsx_kodak_plan_create", "rsx_crw_plan_create",
-                     "rsx_raf_rotate_plan_create", "rsx_sony_srf_plan_create"):
+                     "rsx_raf_rotate_plan_create", "rsx_sony_srf_plan_create",
+                     "rsx_image_hash_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -443,6 +447,11 @@ def fuji_rotate_validate(desc, src_view, dst_view):
 def sony_srf_validate(in_bytes, img_view):
     """rsx_sony_srf_validate; img_view None passes a NULL image"""
     return lib().rsx_sony_srf_validate(in_bytes, _ref(img_view))
+
+
+def image_hash_validate(img_view, sample_bytes):
+    """rsx_image_hash_validate; img_view None passes a NULL image"""
+    return lib().rsx_image_hash_validate(_ref(img_view), sample_bytes)
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -856,6 +865,17 @@ class Context:
         return lib().rsx_sony_srf_decompress(self._h, C.c_void_p(in_ptr), in_bytes, key,
                                              C.byref(img_view))
 
+    def image_hash(self, img_view, sample_bytes, lines=True):
+        """rsx_image_hash: img_view.data is a host or a device pointer.  Returns (status,
+        abi.ImageHashResult, the 16 dim_y bytes of the line digests or None without `lines`).
+        Both outputs start as 0xA5 bytes, so a call that fails shows that it wrote nothing."""
+        r = abi.ImageHashResult()
+        C.memset(C.byref(r), 0xA5, C.sizeof(r))
+        buf = np.full(16 * max(1, img_view.dim_y), 0xA5, np.uint8) if lines else None
+        st = lib().rsx_image_hash(self._h, C.byref(img_view), sample_bytes,
+                                  buf.ctypes.data if lines else None, C.byref(r))
+        return st, r, (buf.tobytes() if lines else None)
+
     def dng_decompress_deflate(self, bps, predictor, geoms, datas, img_view):
         """geoms: (tile_w, tile_h, off_x, off_y, width, height) per tile, samples; datas: the
         tiles' zlib streams.  Returns (status, per-tile statuses)."""
@@ -1036,6 +1056,11 @@ class Context:
     def sony_srf_plan(self, jobs):
         """jobs: abi.SonySrfJob, one per frame (geometries and keys may mix)"""
         return Plan(self, "rsx_sony_srf_plan_create", abi.SonySrfJob, jobs)
+
+    def image_hash_plan(self, jobs):
+        """jobs: abi.ImageHashJob, one per image (geometries and sample sizes may mix);
+        run(images_base, outputs_base)"""
+        return Plan(self, "rsx_image_hash_plan_create", abi.ImageHashJob, jobs)
 
     def dng_jpeg_plan(self, jobs):
         """jobs: abi.DngJpegJob (abi.dng_jpeg_job), one per image"""

@@ -24,6 +24,8 @@
 #include "rsx_fuji_rotate_core.h"
 #include "rsx_sony_srf.h"
 #include "rsx_sony_srf_core.h"
+#include "rsx_image_hash.h"
+#include "rsx_image_hash_core.h"
 #include "rsx_samsung_v2.h"
 #include "rsx_sony_arw2.h"
 #include "rsx_nikon_snef.h"
@@ -4692,6 +4694,84 @@ extern "C" int rsx_sony_srf_decompress(rsx_ctx* ctx, const uint8_t* in, size_t i
   }
   std::vector<uint8_t> plan_key = one_job_key(rsx_sony_srf_plan_create, job);
   return single_image_host(ctx, plan_key, rsx_sony_srf_plan_create, job, in, span, img, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// rstest's imgDataHash, rawspeed-identify's sums
+// ---------------------------------------------------------------------------
+extern "C" int rsx_image_hash_validate(const rsx_image* img, int32_t sample_bytes) {
+  return rsx_imghash::validate(img, sample_bytes);
+}
+
+extern "C" int rsx_image_hash_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_image_hash_job* jobs,
+                                          rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, image_hash_plan_create);
+}
+
+// A plan of one job whose outputs are one block of 16 dim_y + 32 bytes: the digests, the result
+// behind them.  A device pointer: the plan runs on the image where it lies, on the context's
+// stream behind the null stream's work so far, and the block alone comes back.  A host pointer:
+// the rows go up as one copy into a lane.
+extern "C" int rsx_image_hash(rsx_ctx* ctx, const rsx_image* img, int32_t sample_bytes,
+                              uint8_t* line_md5, rsx_image_hash_result* out) {
+  if (!ctx || !img || !img->data || !out)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_imghash::validate(img, sample_bytes))
+    return st;
+  if (reinterpret_cast<uintptr_t>(img->data) % uintptr_t(sample_bytes) != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t lines_bytes = size_t(img->dim_y) * 16;
+  const size_t back_bytes = lines_bytes + sizeof(rsx_image_hash_result);
+  rsx_image_hash_job job;
+  std::memset(&job, 0, sizeof job);
+  job.result_offset = lines_bytes;
+  job.sample_bytes = sample_bytes;
+  job.img = *img;
+  job.img.data = nullptr;
+  CallPlan call;
+  if (int st = rsx_image_hash_plan_create(ctx, 1, &job, &call.plan))
+    return st;
+  std::vector<uint8_t> back(back_bytes);
+  if (is_device_pointer(img->data)) {
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    DeviceBuffer d_back;
+    if (int e = d_back.ensure(back_bytes + 16))
+      return e;
+    if (int st = rsx_plan_run(call.plan, img->data, d_back.ptr, nullptr))
+      return st;
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(back.data(), d_back.ptr, back_bytes, hipMemcpyDeviceToHost,
+                                      ctx->stream));
+    if (int st = rsx_plan_results(call.plan, nullptr, nullptr)) // (waits for the stream)
+      return st;
+  } else {
+    LaneGuard lane(ctx);
+    if (!lane.lane)
+      return RSX_ERR_DEVICE;
+    rsx_ctx::HostLane* L = lane.lane;
+    const size_t row_bytes = size_t(img->dim_x) * size_t(img->cpp) * size_t(sample_bytes);
+    const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) + row_bytes;
+    if (int e = L->d_in.ensure(bytes + 64))
+      return e;
+    if (int e = L->d_out.ensure(back_bytes + 64))
+      return e;
+    {
+      std::lock_guard<std::mutex> up(ctx->upload_mu);
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr, img->data, bytes, hipMemcpyHostToDevice,
+                                        L->stream));
+    }
+    if (int st = rsx_plan_run(call.plan, L->d_in.ptr, L->d_out.ptr, L->stream))
+      return st;
+    const DownRect dr{back.data(), 0, static_cast<const uint8_t*>(L->d_out.ptr), 0, back_bytes, 1};
+    std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+    if (int e = download_rects(ctx, L, L->stream, &dr, 1))
+      return e;
+  }
+  if (line_md5)
+    std::memcpy(line_md5, back.data(), lines_bytes);
+  std::memcpy(out, back.data() + lines_bytes, sizeof *out);
+  return RSX_OK;
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,
