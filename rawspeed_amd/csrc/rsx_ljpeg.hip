@@ -245,12 +245,8 @@ __device__ __forceinline__ void lj_stage_slots(const Lds& L, const LjArgs& a,
   // streams were assembled byte by byte, eighty loads a lane: K0 took 0.18 ms instead of
   // 0.07 on the four tiles of a cfg-4 frame with restart intervals.
   const uint32_t delta = uint32_t(reinterpret_cast<uintptr_t>(in) & 15u);
-#ifdef RSX_NO_FUNNEL // (A/B builds)
-  const bool funnel = false;
-#else
   const bool funnel = !aligned16 && S.in_offset >= 16u && start >= 0 &&
                       start - int64_t(delta) + 96 <= in_bytes;
-#endif
   if (__any(funnel)) {
     uint32_t w[25];
 #pragma unroll
@@ -442,9 +438,6 @@ __device__ __forceinline__ void lj_decode_span_single(const Lds& L, const Decode
     *sums = make_uint2(NS == 1 ? (a0 & 0xFFFFu) : a0, NS == 4 ? a1 : 0u);
 }
 
-#ifndef RSX_SPAN_GENERIC
-#define RSX_SPAN_GENERIC 0 // (experiments: 1 = the generic loop everywhere)
-#endif
 template <bool MULTI, int NS, bool PAIR, int REVBW, typename TB = TabLds>
 __device__ __forceinline__ void lj_decode_span(const Lds& L, const DecodeParams& dp,
                                                int col, uint32_t start,
@@ -452,7 +445,7 @@ __device__ __forceinline__ void lj_decode_span(const Lds& L, const DecodeParams&
                                                uint32_t& count, uint2* sums,
                                                bool enabled = true,
                                                uint32_t pos_override = 0xFFFFFFFFu) {
-  if (!MULTI && !PAIR && REVBW != 0 && !RSX_SPAN_GENERIC) {
+  if (!MULTI && !PAIR && REVBW != 0) {
     lj_decode_span_single<NS, REVBW ? REVBW : 1, TB>(L, dp, col, start, end_bits, exit, count,
                                                      sums, enabled, pos_override);
     return;
@@ -541,44 +534,10 @@ __device__ __forceinline__ uint32_t lj_guess_parse(uint32_t bcol, uint32_t lut, 
     *count = n | ((spec & 0x80u) << 24);
   return pos - end_bits;
 }
-// The same loop instruction by instruction, for the layout the kernel really has (the
-// image at LDS address 0, the length table behind the layout): the position is kept as
-// 32 * pos, so the window's row is one v_and_or, its two dwords come with one
-// ds_read2st64_b32 in the order v_lshlrev_b64 wants them, the advance is one v_lshl_add --
-// 6 vector instructions and 2 LDS reads per symbol where the compiler's version has 11 and 2
-// (K0 parses three slots per slot: 0.20 of its 0.33 ms on cfg 3 are this loop).
+// K0's LDS layout: the image at address 0, the 10-bit length table in its dword row 17, ob[] behind it.
 constexpr uint32_t LJ_GUESS_LUT_OFF = uint32_t(LJ_PW + 1) * LJ_T * 4; // dword row 17 of the image
 constexpr uint32_t LJ_K0_OFF_OB = uint32_t(LJ_BW) * LJ_T * 4;
 constexpr uint32_t LJ_K0_LDS = LJ_K0_OFF_OB + 3 * LJ_T * 2 + 16 * 4 + 16 * 4 + 16;
-template <bool COUNT>
-__device__ __forceinline__ uint32_t lj_guess_parse_asm(uint32_t col4, uint32_t end_bits,
-                                                       uint32_t from, uint32_t* count = nullptr) {
-  uint32_t q = from << 5, n = 0, spec = 0;
-  const uint32_t qend = end_bits << 5;
-  while (q < qend) {
-    uint32_t ad, len;
-    uint64_t pr;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(ad) : "v"(q), "s"(0xFFFFFC00u), "v"(col4));
-    // (two reads: 56 cycles where ds_read2st64_b32 takes 73, scripts/ubench/valu_rates.hip)
-    uint32_t d0, d1;
-    asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&v"(d0), "=&v"(d1)
-                 : "v"(ad));
-    pr = (uint64_t(d0) << 32) | d1;
-    const uint32_t w = uint32_t((pr << ((q >> 5) & 31u)) >> 32);
-    asm volatile("ds_read_u8 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)"
-                 : "=v"(len)
-                 : "v"(w >> 22), "n"(LJ_GUESS_LUT_OFF));
-    spec |= len;
-    q += (len & 0x7Fu) << 5;
-    if (COUNT)
-      ++n;
-  }
-  if (COUNT)
-    *count = n | ((spec & 0x80u) << 24);
-  return (q - qend) >> 5;
-}
-
 // Total bits of the symbol a window starts with, the general way (any code length, SSSS = 16;
 // 0: no such code): what the guess parses fall back to where the 10-bit length table only
 // says "special".  Rare -- the codes of 11 bits and more are the rarest categories -- but a
@@ -603,7 +562,7 @@ __device__ __forceinline__ uint32_t lj_exact_symbol_bits(uint32_t w, const TabLd
   return r >> 10;
 }
 
-// Two symbols per window read (round 4).  The loop above spends, per symbol, two LDS reads
+// Two symbols per window read (round 4).  A one-symbol loop spends, per symbol, two LDS reads
 // for the window, one random byte read in a 1 KB table (four dwords per bank: conflicts)
 // and ~7 vector instructions.  Here a second, 256-byte table -- 64 dwords, one per LDS bank:
 // conflict-free -- holds the symbol's total length for the codes of up to 8 bits (0x80:
@@ -612,12 +571,10 @@ __device__ __forceinline__ uint32_t lj_exact_symbol_bits(uint32_t w, const TabLd
 // code of at most 8 bits + at most 16 difference bits), so the 8 index bits are the stream's.
 // Pairs are taken while the first symbol cannot reach the end of the slot (q + 26 symbols'
 // bits < end), so the second one always starts inside it; the last two or three symbols go
-// through the one-symbol loop.  A miss in either look-up (0x80 + anything >= 128) takes ONE
-// symbol by the 10-bit table, as the loop above would.
-// 10 vector instructions and 4 LDS reads per PAIR where the loop above takes 14-16 and 6.
-#ifndef RSX_K0_FINAL_POLLS
-#define RSX_K0_FINAL_POLLS 64 // polls for the predecessor's FINAL hand-over word (two-table plans)
-#endif
+// through a one-symbol loop.  A miss in either look-up (0x80 + anything >= 128) takes ONE
+// symbol by the 10-bit table.
+// 10 vector instructions and 4 LDS reads per PAIR where one-symbol loops take 14-16 and 6.
+constexpr uint32_t LJ_K0_FINAL_POLLS = 64; // polls for the predecessor's FINAL hand-over word (two-table plans)
 constexpr uint32_t LJ_GUESS_ROUNDS = 6; // rounds of the chain's fixed-point iteration, at most
 // dword rows 17..19 of the image (3 KB, free once the image is written out): the 10-bit
 // length table | the 8-bit one, or the SECOND 10-bit table of a two-table stream | the chain's
@@ -957,11 +914,7 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
   // kernel -1 %, a single cfg-4 frame -2.8 %).  K0's workgroups are independent of one another.
   // (K0_CHAIN, plans with two-table streams: workgroups in block order, because each one asks
   // its predecessor for its true entry state, see "hand-over" below)
-#ifdef RSX_K0_FORWARD
-  uint32_t b = blockIdx.x;
-#else
   uint32_t b = a.blk0 + (a.blk_n - 1u - blockIdx.x);
-#endif
   // (no tickets: the dispatcher starts a 1-D grid's workgroups in order, and if it ever did
   // not, the bounded wait below gives up and the workgroup keeps its own estimate -- a ticket
   // and its barrier in front of the first load cost every workgroup 1.5 us of its 25)
@@ -1074,7 +1027,8 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
   if (j == 0)
     a.block_drops[b] = L.misc[9];
   // state of the single-pass kernel that follows (rsx_ljpeg_fast.hip): its look-back
-  // granules and workgroup tickets start from zero in every run
+  // granules start from zero in every run (and the vestigial ticket words, LjArgs::tickets,
+  // which nothing reads)
   if (a.lb && j < LF_LB_WORDS)
     a.lb[size_t(b) * LF_LB_WORDS + j] = 0ull;
   if (a.tickets && b == 0 && j < 25) {
@@ -1197,14 +1151,9 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
       if (KM == 1 && mt)
         return count ? lj_guess_parse_mt<true, true>(uint32_t(col) * 4u, bits, from, tb_even, tb_odd, count)
                      : lj_guess_parse_mt<false, true>(uint32_t(col) * 4u, bits, from, tb_even, tb_odd);
-#ifndef RSX_K0_SINGLE_SYMBOL
       if (hand)
         return count ? lj_guess_parse_pairs<true>(uint32_t(col) * 4u, bits, from, count)
                      : lj_guess_parse_pairs<false>(uint32_t(col) * 4u, bits, from);
-#endif
-      if (hand)
-        return count ? lj_guess_parse_asm<true>(uint32_t(col) * 4u, bits, from, count)
-                     : lj_guess_parse_asm<false>(uint32_t(col) * 4u, bits, from);
       return count ? lj_guess_parse<true>(lds_addr(&L.B[col]), lds_addr(lut8), bits, from, count)
                    : lj_guess_parse<false>(lds_addr(&L.B[col]), lds_addr(lut8), bits, from);
     };
@@ -1225,15 +1174,10 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
     K0_STAMP(5);
     const uint32_t xa = j >= 1 ? uint32_t(EA[j - 1]) : 0u;
     uint32_t ebv = ea;
-#ifdef RSX_K0_X1 // (diagnostic build: the B parse without its count -- wrong counts, K0's time only)
-    if (!constant && exists && xa != 0u && gs >= 2u)
-      ebv = parse(j, eb, xa, nullptr) & smask;
-#else
     // (two tables: the parse from bit 0 stands for the B parse where the predecessor ends on
     // bit 0 -- unless it met a special length: then once more, looking them up)
     if (!constant && exists && gs >= 2u && (xa != 0u || ((mt || pt) && (cnt >> 31) != 0u)))
       ebv = parse(j, eb, xa, &cnt) & smask;
-#endif
     EB[j] = uint16_t(ebv);
     uint32_t handed = 0;
     // Hand-over (K0_CHAIN): the state this workgroup's chain leaves its last slot in IS the
@@ -1471,13 +1415,11 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
       }
     }
     K0_STAMP(7);
-#ifndef RSX_K0_NO_FINAL_HANDOVER
     // (the hand-over once more, now that the rounds have run: marked final)
     if (K0_CHAIN && j == LJ_T - 1 && lb + 1 < S.n_blocks)
       __hip_atomic_store(&a.k0e[b + 1],
                          0xA000u | (a.run_parity << 14) | (uint32_t(EB[LJ_T - 1]) & smask),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     if (K0_CHAIN) {
       // the hand-over: the predecessor's word (asked for before the rounds; once more if it
       // was not out yet -- it is by now as a rule: the predecessor started earlier)
@@ -1490,11 +1432,10 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
             __builtin_amdgcn_s_sleep(1);
             v = __hip_atomic_load(&a.k0e[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
-#ifndef RSX_K0_NO_FINAL_HANDOVER
           // (the predecessor's word from behind ITS rounds, if it comes within a few polls:
           // in 1.3 % of the workgroups the rounds move the last slot's exit, and a workgroup
           // that started from the older state is a slow one in the single-pass kernel)
-          for (uint32_t spins = 0; spins < uint32_t(RSX_K0_FINAL_POLLS) &&
+          for (uint32_t spins = 0; spins < LJ_K0_FINAL_POLLS &&
                                    (v & 0xE000u) != (tag | 0x2000u);
                ++spins) {
             const uint32_t w = __hip_atomic_load(&a.k0e[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1503,7 +1444,6 @@ __global__ __launch_bounds__(LJ_T) void lj_unstuff_kernel(LjArgs a) {
             if ((v & 0xE000u) != (tag | 0x2000u))
               __builtin_amdgcn_s_sleep(1);
           }
-#endif
           // (a table per phase: the phase of EB[0] is the look-back's, absolute; a predecessor's
           // word from BEFORE its own phase pass -- not marked final -- only has an offset to give)
           uint32_t vs = v & smask;
@@ -2618,10 +2558,7 @@ __global__ __launch_bounds__(LJ_T) void lj_scan_kernel(LjArgs a) {
 // ---------------------------------------------------------------------------
 // LAS: the stream's table holds Nikon "lossy after split" values (its own
 // instantiation so that the JPEG hot loop carries no extra branch)
-#ifndef RSX_K4_BURST
-#define RSX_K4_BURST 4
-#endif
-constexpr int K4_BURST = RSX_K4_BURST; // groups of 8 differences per store burst
+constexpr int K4_BURST = 4; // groups of 8 differences per store burst
 
 template <bool MULTI, bool LAS = false>
 __global__ __launch_bounds__(LJ_T) void lj_decode_kernel(LjArgs a) {
@@ -3773,11 +3710,7 @@ LjArgs make_args(LJpegPlan* p, const void* in_dev, void* out_dev) {
   a.k0e = static_cast<uint32_t*>(p->d_k0e.ptr);
   a.k0p = static_cast<uint32_t*>(p->d_k0p.ptr);
   a.pt_np = p->pt_np;
-#ifdef RSX_NO_K0_CHAIN // (experiments)
-  a.k0_chain = 0u;
-#else
   a.k0_chain = ((p->any_fast_mt || p->any_fast_pt) && p->d_k0e.ptr) ? 1u : 0u;
-#endif
   a.block_base0 = static_cast<uint32_t*>(p->d_block_base0.ptr);
   a.fast_uniform_nb = p->fast_uniform_nb;
   a.dev_layout = p->dev_layout ? 1u : 0u;
@@ -3809,7 +3742,7 @@ LjArgs make_args(LJpegPlan* p, const void* in_dev, void* out_dev) {
   // batches of 32 streams and more -- a wrong guess delays only the workgroups of ITS stream
   // -- but every re-decode round still costs its workgroup 6 us and the ones behind it their
   // wait: 256 cfg-5 frames 348 GPix/s with three slots, 318 with two.)
-  a.guess_slots = 3u;
+  a.guess_slots = uint32_t(LJ_GUESS_SLOTS);
 #ifdef RSX_EXPERIMENT
   if (const char* e = getenv("RSX_GUESS_SLOTS"))
     a.guess_slots = uint32_t(atoi(e));
@@ -3826,16 +3759,13 @@ void mark(LJpegPlan* p, const char* name) {
     p->timer->mark(name);
 }
 
-#ifndef RSX_K1_LDS_PAD
-#define RSX_K1_LDS_PAD 0 // (experiments: unused LDS that limits K1's workgroups per CU)
-#endif
 template <bool STITCH, bool MULTI, int NS>
 void launch_sync_one(LJpegPlan* p, const LjArgs& a, hipStream_t s) {
   if (!p->sync_present[MULTI ? 1 : 0][NS])
     return;
   using TB = SyncTable<MULTI, false>;
   const size_t lds = lj_sync_lds_bytes<TB>(MULTI ? p->max_tables : 1, LJ_BW_SYNC, NS) +
-                     (STITCH ? lj_periodic_bytes() : RSX_K1_LDS_PAD);
+                     (STITCH ? lj_periodic_bytes() : 0);
   hipLaunchKernelGGL((lj_sync_kernel<STITCH, MULTI, false, NS>), dim3(p->total_blocks),
                      dim3(LJ_T), lds, s, a);
   mark(p, STITCH ? "lj_sync_kernel<stitch>" : "lj_sync_kernel");
@@ -3945,12 +3875,10 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
     // decode + reconstruction; everything else (sRaw groups, 3 components, the
     // Nikon-type kinds, Hasselblad pairs) the legacy route through differences
     uint8_t direct_n = 0;
-#ifndef RSX_NO_DIRECT
     if ((g.kind == 0 || g.kind == 1) && !g.raw && !g.las && !g.pair && !g.no_vertical &&
         g.period == g.n_comp && (g.n_comp == 1 || g.n_comp == 2 || g.n_comp == 4) &&
         J.explicit_n == 0)
       direct_n = uint8_t(g.n_comp);
-#endif
     // The legacy route keeps a 2-byte difference per symbol, sized by the frame the
     // header declares, not by the input: a small tile that claims a huge frame is
     // refused (the forwarding hunks then leave it to the original CPU loop) instead of
@@ -3996,7 +3924,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
     S.diff_offset = direct_n ? LJ_NO_DIFFS : 0; // (legacy streams: assigned below)
     // the single-pass kernel: fused-path streams with one table whose MCU is a row of
     // its components (or CR2 strips)
-#ifndef RSX_NO_FAST
     // (round 4: also TWO tables that alternate symbol by symbol -- one per component of a
     // two-component scan, the usual DNG; A B A B of four --: S.fast = 2, the kernel's
     // two-table instantiation, the table being part of every parse state)
@@ -4004,9 +3931,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
                            g.comp_of_phase[0] != g.comp_of_phase[1];
     for (uint32_t ph = 0; ph < g.n_comp && two_alternating; ++ph)
       two_alternating = g.comp_of_phase[ph] == g.comp_of_phase[ph & 1u];
-#ifdef RSX_NO_FAST_MT
-    two_alternating = false;
-#endif
     // (round 6: ANY assignment of up to four tables to the components -- a table per
     // component of a three-component scan, what DNG writers emit for linear images; A B C D,
     // A B B, ... --: S.fast = 3, the kernel's table-per-phase instantiation, the phase
@@ -4036,9 +3960,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
             per_phase = false;
         }
     }
-#ifdef RSX_NO_FAST_PT
-    per_phase = false;
-#endif
     S.fast = (direct_n && (J.n_tables == 1 || two_alternating || per_phase) &&
               (g.kind == 1 || (g.mcu_h == 1 && g.mcu_w == g.n_comp)) &&
               g.row_samples >= g.n_comp && tables.size() < 0xFFFFu)
@@ -4050,7 +3971,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
     // the fused multi-kernel path (direct stays 0: that path's kernels are for 1, 2 and 4
     // components), so a stream the kernel gives up on is redone by the legacy route, whose
     // difference scratch it keeps.
-#ifndef RSX_NO_FAST3
     const bool fast3 = !direct_n && g.kind == 0 && !g.raw && !g.las && !g.pair &&
                        !g.no_vertical && g.n_comp == 3 && g.period == 3 && g.mcu_h == 1 &&
                        g.mcu_w == 3 && (J.n_tables == 1 || per_phase) && J.explicit_n == 0 &&
@@ -4073,7 +3993,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
     const bool env_no_nk = getenv("RSX_NO_FAST_NK") != nullptr;
     const bool env_no_diffs = getenv("RSX_NO_FAST_DIFFS") != nullptr;
     S.fast_nk = 0;
-#ifndef RSX_NO_FAST_NK
     // (a table given as the reference's own (encLen, diffLen) pairs -- SamsungV1 -- is as good as a
     // canonical one while its codes fit the kernel's 10-bit LUT: every entry is a whole symbol)
     const bool lut10 = J.explicit_n == 0 || J.explicit_bits <= 10;
@@ -4097,16 +4016,13 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
             S.init_pred[2 * h + c] = uint16_t(N.p_up[2 * ((g.out_y + h) & 1u) + c]);
       }
     }
-#endif
     S.fast_diffs = 0;
-#ifndef RSX_NO_FAST_DIFFS
     if (!env_no_diffs && !S.fast && !direct_n && J.n_tables == 1 && lut10 && !g.las && !g.pair &&
         (g.kind == 2 || g.kind == 1 || g.kind == 0) && !(g.kind == 2 && J.nikon.sony) &&
         tables.size() < 0xFFFFu && needed >= 1) {
       S.fast = 1;
       S.fast_diffs = 1;
     }
-#endif
     S.tab_period = 0;
     if (S.fast == 3) {
       // (the period of the assignment: A B A B over four components is two phases, not four --
@@ -4123,7 +4039,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
       }
       S.tab_period = uint8_t(tp);
     }
-#endif
     if (S.fast) {
       // its workgroups stage all their samples in LDS at once: the allocation follows the
       // stream's symbols per workgroup (+ 15 % for local variation; a workgroup that
@@ -4135,7 +4050,6 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
       else
         p->fast_lds = std::max(p->fast_lds, lds);
     }
-#endif
     S.sync_lut11 = (J.explicit_n > 0 && J.explicit_bits > 10) ? 1 : 0;
     S.raw_limit = g.raw_limit;
     S.rows = g.rows;
@@ -4314,24 +4228,8 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
       o.fix16 = dt.fix16;
       o.zero_sym_bits = dt.zero_sym_bits;
       o.las = dt.las;
-      for (uint32_t i = 0; i < uint32_t(LUT_SIZE); ++i) {
-        const uint32_t e = dt.lut[i];
-        uint32_t hi = 0;
-#if RSX_LUT_DIFF
-        // the symbol's difference, if code and difference bits lie inside the index
-        const uint32_t cl = e & 31u, ssss = (e >> 5) & 31u, total = e >> 10;
-        if (e != 0 && !dt.las && total <= uint32_t(LUT_BITS)) {
-          if (ssss == 16u) {
-            hi = 0x8000u;
-          } else if (ssss != 0u) {
-            const uint32_t v = (i >> (uint32_t(LUT_BITS) - total)) & ((1u << ssss) - 1u);
-            hi = (v >= (1u << (ssss - 1)) ? v : v + 1u - (1u << ssss)) & 0xFFFFu;
-          }
-          (void)cl;
-        }
-#endif
-        o.lut[i] = LutEntry(e | (hi << 16));
-      }
+      for (uint32_t i = 0; i < uint32_t(LUT_SIZE); ++i)
+        o.lut[i] = LutEntry(dt.lut[i]);
     }
     auto up = [&](DeviceBuffer& b, const void* src, size_t n) -> int {
       if (int st = b.ensure(n ? n : 16))
@@ -4390,20 +4288,11 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
       // (measured on cfg 3: the kernel +4-10 %) -- so the streams' turn rotates from group to
       // group then; other counts spread a stream over 8 / gcd(streams, 8) XCDs by themselves.
       const size_t ns = p->streams.size();
-#if defined(RSX_LF_ROTATE) && RSX_LF_ROTATE == 0
-      p->fast_rotate = 0;
-#elif defined(RSX_LF_ROTATE) && RSX_LF_ROTATE == 2
-      p->fast_rotate = 1;
-#else
       p->fast_rotate = (ns % 8 == 0) ? 1u : 0u;
-#endif
       p->fast_uniform_nb = max_blocks;
       for (const LjStreamDev& S : p->streams)
         if (S.n_blocks != max_blocks)
           p->fast_uniform_nb = 0;
-#ifdef RSX_LF_NO_UNIFORM
-      p->fast_uniform_nb = 0;
-#endif
       for (uint32_t k = 0; k < max_blocks; ++k)
         for (size_t i0 = 0; i0 < ns; ++i0) {
           const size_t si = p->fast_rotate ? (i0 + k) % ns : i0;
@@ -4431,7 +4320,7 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
           (st = p->d_k0w.ensure(size_t(p->total_blocks + 1) * 8)) ||
           (st = p->d_k0e.ensure(size_t(p->total_blocks + 1) * 4)) ||
           (st = p->d_block_base0.ensure(size_t(p->total_blocks) * 4)) ||
-          (st = p->d_tickets.ensure(LF_TICKET_WORDS * 4)))
+          (st = p->d_tickets.ensure(LF_TICKET_WORDS * 4))) // (vestigial: LjArgs::tickets)
         return st;
       if ((st = p->d_fast_level.ensure(256)))
         return st;
@@ -4452,9 +4341,7 @@ int ljpeg_plan_create(rsx_ctx* ctx, const std::vector<LJpegJobIn>& jobs,
       // whenever other host threads kept the null stream busy -- K0's words, the hand-over words or
       // the LDS level zeroed under the kernels' feet; once in ~17 000 calls from six threads a whole
       // small tile came back wrong with status OK (profiles/r06/host_path_defect/README.md).
-#ifndef RSX_NO_CREATE_SYNC // (experiment: the behaviour until round 6, for scripts/exp_null_stream_stress.py)
       RSX_HIP_CHECK(ctx, hipStreamSynchronize(nullptr));
-#endif
 #ifdef RSX_EXPERIMENT
       if (getenv("RSX_DEBUG")) {
         if ((st = p->d_dbg.ensure(size_t(p->total_blocks) * 32 * 8)))
@@ -4829,7 +4716,6 @@ int run_dri_device(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t 
 
 int run_dri(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t s) {
   p->dri_ran_dev = false;
-#ifndef RSX_DRI_HOST_ONLY
   if (!p->child_dev_failed) {
     const int st = run_dri_device(p, in_dev, out_dev, s);
     if (st == RSX_OK) {
@@ -4840,7 +4726,6 @@ int run_dri(LJpegPlan* p, const void* in_dev, void* out_dev, hipStream_t s) {
       return st;
     p->child_dev_failed = true;
   }
-#endif
   return run_dri_host(p, in_dev, out_dev, s);
 }
 
@@ -4964,7 +4849,6 @@ static int ljpeg_plan_run_begin_(LJpegPlan* p, const void* in_dev, void* out_dev
   }
   LjArgs a = make_args(p, in_dev, out_dev);
   a.fuse_consumed = (p->any_fast && !p->any_pipeline && !p->any_legacy) ? 1u : 0u;
-#ifndef RSX_NO_FIRST_RUN_INV
   // A plan's FIRST run: its kernels read the stream records, the block map and the ticket
   // order through the scalar cache, nothing invalidates a CU's scalar cache between two
   // kernels of a stream, and the arrays of a new plan tend to lie where those of the plan
@@ -4972,7 +4856,6 @@ static int ljpeg_plan_run_begin_(LJpegPlan* p, const void* in_dev, void* out_dev
   // plan is replaced).  5 us once per plan.
   if (p->run_count == 1 && !p->dev_layout)
     hipLaunchKernelGGL(lj_dcache_inv_kernel, dim3(4096), dim3(64), 0, s);
-#endif
   // results: marker_pos = 0xFFFFFFFF, everything else 0
   for (auto& r : p->h_results) {
     std::memset(&r, 0, sizeof r);
@@ -4981,11 +4864,6 @@ static int ljpeg_plan_run_begin_(LJpegPlan* p, const void* in_dev, void* out_dev
   // (on the device: a copy of a few hundred bytes from pageable memory in front of every run
   // costs the stream more than a kernel of one wavefront)
   const uint32_t n_streams = uint32_t(p->streams.size());
-#ifdef RSX_RESULTS_BY_COPY
-  RSX_HIP_CHECK(ctx, hipMemcpyAsync(results_of_run(p), p->h_results.data(),
-                                    p->h_results.size() * sizeof(LjResult),
-                                    hipMemcpyHostToDevice, s));
-#else
   // (unless the run before this one has cleared them: K0 does that for its successor, on the
   // same stream)
   if (p->results_clean_for != p->run_count || p->results_clean_stream != s) {
@@ -4993,7 +4871,6 @@ static int ljpeg_plan_run_begin_(LJpegPlan* p, const void* in_dev, void* out_dev
                        dim3(256), 0, s, results_of_run(p), n_streams);
     mark(p, "lj_init_results_kernel");
   }
-#endif
   p->results_clean_for = p->run_count + 1;
   p->results_clean_stream = s;
   p->run_args = a;
@@ -5328,10 +5205,7 @@ int converge(LJpegPlan* p, hipStream_t s) {
   uint32_t rounds = 0;
   // (a stitch launch settles at least LJ_STITCH_MAX_ROUNDS slots of a workgroup that
   // is still chaining, and at least one more workgroup of a chain of workgroups)
-#ifndef RSX_STITCH_BOUND_X
-#define RSX_STITCH_BOUND_X 1
-#endif
-  while (unconverged() && rounds <= RSX_STITCH_BOUND_X * (9 * p->total_blocks + 16)) {
+  while (unconverged() && rounds <= 9 * p->total_blocks + 16) {
     for (int k = 0; k < 4; ++k)
       launch_sync<true>(p, a, s);
     rounds += 4;

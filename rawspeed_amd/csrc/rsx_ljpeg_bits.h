@@ -137,13 +137,9 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 // its next barrier although nobody in the workgroup will ever read those bytes.  Use where
 // the lanes of a workgroup talk to one another through LDS alone.  (The compiler still waits
 // for a loaded value in front of its first use: it counts the loads itself.)
-#ifdef RSX_PLAIN_BARRIERS
-__device__ __forceinline__ void lds_barrier() { __syncthreads(); }
-#else
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-#endif
 // the difference sums of slot j (N components)
 template <int NS>
 __device__ __forceinline__ uint2 sm_get(const Lds& L, int j) {
@@ -186,8 +182,7 @@ __device__ __forceinline__ void lj_stage_tables10(const Lds& L, const LjArgs& a,
   TabLds10* dst = reinterpret_cast<TabLds10*>(L.tabs);
   for (uint32_t t = 0; t < S.n_tables; ++t) {
     for (int i = threadIdx.x; i < 1024; i += int(blockDim.x)) {
-      const uint32_t e =
-          reinterpret_cast<const uint16_t*>(src[t].lut)[2 * i * (sizeof(LutEntry) / 2)];
+      const uint32_t e = src[t].lut[2 * i];
       dst[t].lut[i] = uint16_t((e & 31u) > 10u ? 0u : e);
     }
     // (max_code .. las: the same bytes in both structs)
@@ -303,7 +298,7 @@ __device__ __forceinline__ uint32_t lj_extend(uint32_t w, uint32_t e) {
 
 // the 16-bit entry (code length | SSSS << 5 | bits consumed << 10) at LUT index i
 __device__ __forceinline__ uint32_t lj_lut16(const TabLds& tb, uint32_t i) {
-  return reinterpret_cast<const uint16_t*>(tb.lut)[i * (sizeof(LutEntry) / 2)];
+  return tb.lut[i];
 }
 __device__ __forceinline__ uint32_t lj_lut16(const TabLds10& tb, uint32_t i) {
   return tb.lut[i];
@@ -321,35 +316,13 @@ __device__ __forceinline__ uint32_t lj_entry(uint32_t w, const TB& tb, bool live
 }
 
 // Entry AND difference of the symbol whose first 32 bits are w (the loops that need
-// both): *diff = the 16-bit difference.  With RSX_LUT_DIFF it comes out of the LUT's
-// high half when the symbol lies inside the index bits; otherwise (wave-uniform branch:
-// only when some live lane has a longer symbol) it is computed.
-__device__ __forceinline__ uint32_t lj_entry_diff(uint32_t w, const TabLds10& tb, bool live,
+// both): *diff = the 16-bit difference, computed from the entry (JPEG "EXTEND").
+template <typename TB>
+__device__ __forceinline__ uint32_t lj_entry_diff(uint32_t w, const TB& tb, bool live,
                                                   bool long_codes, uint32_t* diff) {
   const uint32_t e = lj_entry(w, tb, live, long_codes);
   *diff = lj_extend(w, e);
   return e;
-}
-__device__ __forceinline__ uint32_t lj_entry_diff(uint32_t w, const TabLds& tb, bool live,
-                                                  bool long_codes, uint32_t* diff) {
-#if RSX_LUT_DIFF
-  const uint32_t e32 = tb.lut[w >> (32 - LUT_BITS)];
-  uint32_t e = e32 & 0xFFFFu;
-  uint32_t d = e32 >> 16;
-  const bool computed = live && ((e >> 10) > uint32_t(LUT_BITS) || e == 0u);
-  if (__builtin_expect(__any(computed), 0)) {
-    if (long_codes && live && (e & 31u) == 0u)
-      e = lj_slow_entry(w, &tb);
-    if (computed)
-      d = lj_extend(w, e);
-  }
-  *diff = d;
-  return e;
-#else
-  const uint32_t e = lj_entry(w, tb, live, long_codes);
-  *diff = lj_extend(w, e);
-  return e;
-#endif
 }
 
 // the same for a single lane reading the table from global memory

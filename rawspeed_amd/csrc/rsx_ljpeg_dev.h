@@ -22,19 +22,13 @@ namespace rsx {
 // Geometry constants
 // ---------------------------------------------------------------------------
 constexpr int LJ_T = 256;             // lanes per workgroup = slots per workgroup
-#ifndef RSX_LJ_P
-#define RSX_LJ_P 64
-#endif
-constexpr int LJ_P = RSX_LJ_P;        // physical bytes per subsequence
+constexpr int LJ_P = 64;              // physical bytes per subsequence
 constexpr int LJ_PW = LJ_P / 4;       // dwords per subsequence
 constexpr int LJ_OWN = LJ_T - 1;      // owned slots (slot 0 = warm-up)
 constexpr int LJ_R = LJ_OWN * LJ_P;   // bytes of stream owned by one workgroup
 constexpr int LJ_BW = LJ_PW + 4;      // compacted slot capacity (dwords)
 constexpr int LJ_IMG_U4 = (LJ_BW + 1) * LJ_T / 4; // per-workgroup un-stuffed image: B + ob[], in uint4
-#ifndef RSX_LJ_WARM
-#define RSX_LJ_WARM 512
-#endif
-constexpr uint32_t LJ_WARM = RSX_LJ_WARM;     // warm-up bits decoded ahead of a slot for its start guess
+constexpr uint32_t LJ_WARM = 512;     // warm-up bits decoded ahead of a slot for its start guess
 
 // Ablation switches of the experiment builds (rawspeed_amd/build.py build_variant with
 // -DRSX_EXPERIMENT -DRSX_ABLATE=<bits>; compile-time constants, 0 in the shipped
@@ -76,24 +70,14 @@ constexpr uint32_t FL_SLOW = 8u;
 // differences over a healthy stream's region.
 constexpr uint64_t LJ_NO_DIFFS = ~uint64_t(0);
 
-// The code table as the kernels keep it in LDS.  RSX_LUT_DIFF: a LUT entry also
-// carries, in its high half, the DIFFERENCE the symbol stands for whenever the whole
-// symbol -- code and difference bits -- lies inside the LUT_BITS index bits (total <=
-// LUT_BITS; sensor data: nearly always), so that the loops which need differences (the
-// recorded synchronisation pass, the final decode) read them instead of computing the
-// JPEG "EXTEND"; longer symbols take the computed path, wave-uniformly.
-// OFF: the 8 KB table costs the synchronisation kernel its sixth workgroup per CU, which
-// is worth more than the instructions saved (production builds side by side, one GPU
-// session: cfg 3 1.274 -> 1.232 ms, uniform-random 14-bit 1.09 -> 0.96, clipped
-// highlights 2.48 -> 2.25 with the table off).  Kept for experiments.
-#ifndef RSX_LUT_DIFF
-#define RSX_LUT_DIFF 0
-#endif
-#if RSX_LUT_DIFF
-typedef uint32_t LutEntry;
-#else
+// The code table as the kernels keep it in LDS.  A LUT entry is 16 bits: code length and
+// difference category only.  A 32-bit entry that also carried the DIFFERENCE of every symbol
+// lying wholly inside the LUT_BITS index bits was tried and dropped: its 8 KB table costs the
+// synchronisation kernel its sixth workgroup per CU, which is worth more than the JPEG
+// "EXTEND" instructions it saves (production builds side by side, one GPU session: cfg 3
+// 1.274 -> 1.232 ms, uniform-random 14-bit 1.09 -> 0.96, clipped highlights 2.48 -> 2.25
+// with the 16-bit entry).
 typedef uint16_t LutEntry;
-#endif
 
 struct alignas(16) TabLds {
   LutEntry lut[LUT_SIZE];
@@ -252,10 +236,11 @@ struct LjArgs {
   const uint2* fast_tabs;    // [table][1024]: the 10-bit LUT of the single-pass loops
   const uint16_t* fast_tabs16; // [table][1024]: its 2-byte form (streams with a table per phase)
   unsigned long long* lb;    // [workgroup][LF_LB_WORDS]: look-back records (zeroed by K0)
-  uint32_t* tickets;         // [3][4]: workgroup tickets of the single-pass launches by
-                             // LDS level and components (zeroed by K0)
+  uint32_t* tickets;         // VESTIGIAL: the atomic workgroup tickets of the single-pass launches
+                             // until round 5.  No kernel reads them any more (the block index is
+                             // the ticket); K0 still zeroes them.  To be removed with that code.
   uint32_t* fast_level;      // [2]: the LDS level K0 chose for this run (see fast_lds_lv), by
-                             // run parity; [2 + parity]: the level it would have needed.  (Not next to the tickets: 15 000 workgroups'
+                             // run parity; [2 + parity]: the level it would have needed.  (On a cache line of its own: 15 000 workgroups'
                              // atomics and loads on one cache line take 7 ns each, in turn.)
   uint32_t fast_lds;         // LDS bytes of the single-pass launches (staging capacity)
   // The single-pass kernel stages all samples of a workgroup in LDS.  How many that are
@@ -308,11 +293,7 @@ struct LjArgs {
 // words of a workgroup's look-back record (8-byte granules, each self-validating):
 // [0] entry / exit state, symbols, inclusive symbol base; [1..4] LOCAL transfer of the
 // predictor state (a, v; two words each for 4 components); [5..8] the inclusive state
-#ifdef RSX_LF_LB16 // (experiment: LOCAL / inclusive pairs of a record as 16-byte loads)
-constexpr int LF_LB_WORDS = 10;
-#else
 constexpr int LF_LB_WORDS = 9;
-#endif
 
 // Nothing invalidates a CU's scalar data cache between two kernels that follow one another on
 // a stream without the host in between (measured in round 3 on the LDS-level word): a kernel
@@ -438,6 +419,6 @@ __host__ __device__ __forceinline__ uint32_t lf_table_word(uint32_t base, uint32
 }
 uint32_t ljpeg_fast_lds_for(uint64_t samples_per_workgroup);
 uint32_t ljpeg_fast_stage_cap(uint32_t lds_bytes);
-constexpr int LF_TICKET_WORDS = 32; // [2][3][4] tickets: [two tables][LDS level][components]
+constexpr int LF_TICKET_WORDS = 32; // size of the vestigial LjArgs::tickets array
 
 } // namespace rsx

@@ -433,24 +433,14 @@ __device__ __forceinline__ OutCursor lj_store_general(const StoreCtx& x, OutCurs
   return oc;
 }
 
-#ifndef RSX_K4D_BURST
-#define RSX_K4D_BURST 4
-#endif
-constexpr int K4D_BURST = RSX_K4D_BURST; // groups of 8 samples decoded before their stores
+constexpr int K4D_BURST = 4; // groups of 8 samples decoded before their stores
 
-#ifndef RSX_K4D_LDS_PAD
-#define RSX_K4D_LDS_PAD 0 // (experiments: unused LDS that limits the workgroups per CU)
-#endif
 constexpr size_t k4d_lds_bytes(int n_tables) {
-  return size_t(LJ_BW_DEC) * LJ_T * 4 + 16 * 4 + size_t(n_tables) * sizeof(TabLds) +
-         RSX_K4D_LDS_PAD;
+  return size_t(LJ_BW_DEC) * LJ_T * 4 + 16 * 4 + size_t(n_tables) * sizeof(TabLds);
 }
 
-#ifndef RSX_K4D_MIN_WAVES
-#define RSX_K4D_MIN_WAVES 1
-#endif
 template <bool MULTI, int N>
-__global__ __launch_bounds__(LJ_T, RSX_K4D_MIN_WAVES) void lj_decode_direct_kernel(LjArgs a) {
+__global__ __launch_bounds__(LJ_T, 1) void lj_decode_direct_kernel(LjArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t b = blockIdx.x;
   const uint32_t s = a.block_stream[b];
@@ -491,15 +481,8 @@ __global__ __launch_bounds__(LJ_T, RSX_K4D_MIN_WAVES) void lj_decode_direct_kern
     for (int h = 0; h < n_it; ++h) {
       const int i = h * LJ_T + j;
       t[h] = make_uint4(0, 0, 0, 0);
-      if (i < n4) {
-#ifdef RSX_K4D_NT_LOADS
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + i));
-        t[h] = make_uint4(q.x, q.y, q.z, q.w);
-#else
+      if (i < n4)
         t[h] = src[i];
-#endif
-      }
     }
 #pragma unroll
     for (int h = 0; h < n_it; ++h) {
@@ -583,7 +566,7 @@ __global__ __launch_bounds__(LJ_T, RSX_K4D_MIN_WAVES) void lj_decode_direct_kern
       const uint32_t d1 = *(lds_u32p)(ad), d0 = *(lds_u32p)(ad + 4u * LJ_T);
       const uint32_t w = uint32_t((((uint64_t(d0) << 32) | d1) << (pos & 31u)) >> 32);
       uint32_t d, e;
-      if (MULTI || RSX_LUT_DIFF) {
+      if (MULTI) {
         e = lj_entry_diff(w, lj_table<MULTI>(L, dp, phase), live, dp.long_codes, &d);
       } else {
         e = *(lds_u16p)(lut0 | ((w >> (31 - LUT_BITS)) & ((2u << LUT_BITS) - 2u)));

@@ -11,8 +11,8 @@
 // FL_SLOW and redone by it (LjArgs::pass == 1).
 //
 // Per workgroup (256 lanes = 255 own 64-byte subsequences + a copy of the predecessor's
-// last one; workgroups take TICKETS -- the streams' blocks interleaved -- so that every
-// predecessor is resident or finished):
+// last one; a workgroup's block index is its TICKET -- the streams' blocks interleaved -- so
+// that every predecessor is resident or finished):
 //  1. start guesses: made by lj_unstuff_kernel (rsx_ljpeg.hip: a parse of the three
 //     subsequences before each one from bit 0 -- Huffman streams self-synchronise --, the
 //     symbol grid of constant runs from their bits, and the LDS level of the launch:
@@ -66,14 +66,10 @@ namespace rsx {
 
 namespace {
 
-// (experiment, round 6: -DRSX_LF_WG_PER_CU=5 makes the compiler fit the kernel into the 96 vector
-// registers five workgroups a CU would leave it -- the LDS still holds four: what the registers
-// alone would cost, profiles/r06/ab/five_workgroups_register_cap.txt)
-#ifdef RSX_LF_WG_PER_CU
-constexpr int LF_WG_PER_CU = RSX_LF_WG_PER_CU;
-#else
+// Four workgroups a CU: what the LDS holds.  (Round 6 built the kernel for five, to see what the
+// 96 vector registers that would leave it cost by themselves:
+// profiles/r06/ab/five_workgroups_register_cap.txt.)
 constexpr int LF_WG_PER_CU = 4;
-#endif
 constexpr int LF_BW = LJ_PW + 1;        // dword rows of a subsequence the loops can touch
 constexpr int LF_MAXSYM = 128;          // symbols a lane keeps (64 VGPRs)
 constexpr int LF_NR = LF_MAXSYM / 2;
@@ -134,7 +130,7 @@ enum : int {
   M_WCNT = 0,   // [4] symbols per wavefront
   M_WSUM = 4,   // [8] difference sums per wavefront (uint2 x 4)
   M_LIST = 12,  // re-decode list length
-  M_TICKET = 13,
+  // (13: free -- the workgroup's ticket until round 5)
   M_UNRESB = 14, // symbols in front of slot misc[M_UNRES]
   M_PRED = 15,  // predecessor's exit state
   M_SLOW = 16,  // != 0: give the stream to the slow path
@@ -258,20 +254,14 @@ __device__ __forceinline__ u64 lb_load(const u64* p) {
 // words 1..8: bit 63 valid | flags (8 bits at 32) | payload (two 16-bit fields)
 constexpr u64 LB_VALID = 1ull << 63;
 // where the words of component pair k sit in a record: LOCAL transfer (a, v), inclusive state (t, c)
-#ifdef RSX_LF_LB16
-// (experiment: a record of 80 bytes, every (a, v) and (t, c) pair on a 16-byte boundary -- one
-// 16-byte load a pair; every 8-byte word carries its own valid bit, so a pair whose halves
-// were written apart is seen as what it is)
-__device__ __forceinline__ constexpr int lb_wa(int k) { return 2 + 4 * k; }
-__device__ __forceinline__ constexpr int lb_wv(int k) { return 3 + 4 * k; }
-__device__ __forceinline__ constexpr int lb_wt(int k) { return 4 + 4 * k; }
-__device__ __forceinline__ constexpr int lb_wc(int k) { return 5 + 4 * k; }
-#else
+// (Round 5 tried 80-byte records with every pair on a 16-byte boundary, read as 16-byte loads:
+// K1f -1 to -2.5 %, not shipped -- that an aligned 16-byte load never tears an 8-byte half is how
+// the hardware behaves, not what the ISA promises;
+// profiles/r05/ab_k0_head_and_lookback_16byte_loads.txt.)
 __device__ __forceinline__ constexpr int lb_wa(int k) { return 1 + k; }
 __device__ __forceinline__ constexpr int lb_wv(int k) { return 3 + k; }
 __device__ __forceinline__ constexpr int lb_wt(int k) { return 5 + k; }
 __device__ __forceinline__ constexpr int lb_wc(int k) { return 7 + k; }
-#endif
 // word 0 since round 4: bit 63 valid | (symbols the workgroup decoded - symbols K0 counted
 // for it), 32 bits: what a successor adds to K0's count of a FLAGGED workgroup.
 // K0's word of a workgroup (LjArgs::k0w, lj_unstuff_kernel): symbols (32) | own estimate of
@@ -294,9 +284,6 @@ struct FastState {
   uint32_t acc[4];
   uint32_t ev;   // running sum after the last even-numbered symbol
   uint32_t spec; // (per-phase tables) OR of the entries read: bit 15 = a special one among them
-#ifdef RSX_LF_PAIRWIN
-  uint32_t w, wb, sh; // (experiment: the even step's 64-bit window and its entry's shift, for the odd step)
-#endif
 };
 
 // (DIFF -- round 6, streams whose reconstruction stays with the legacy kernels: the lane keeps
@@ -304,16 +291,7 @@ struct FastState {
 template <int N, int K, bool DIFF = false>
 __device__ __forceinline__ void lf_step(FastState& s, uint32_t vbase) {
   const uint32_t ad = vbase + (s.Pn & ~1023u);
-#ifdef RSX_LF_SPLIT_READS
-  // (two ds_read_b32: 56 cycles where the ds_read2st64_b32 the compiler makes of them takes
-  // 73, scripts/ubench/valu_rates.hip)
-  uint32_t d0, d1;
-  asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(d1), "=&v"(d0)
-               : "v"(ad));
-#else
   const uint32_t d1 = *(lds_u32p)(ad), d0 = *(lds_u32p)(ad + 4u * LJ_T);
-#endif
   const uint32_t w = __builtin_amdgcn_alignbit(d0, d1, s.Pn >> 5);
   const lf_u32x2 e = *(lds_u2p)((w >> 19) & 0x1FF8u);
   const uint32_t v = (w >> (e.x & 31u)) & e.y;
@@ -329,41 +307,10 @@ __device__ __forceinline__ void lf_step(FastState& s, uint32_t vbase) {
   s.n += 1;
 }
 
-#ifdef RSX_LF_PAIRWIN
-// Experiment (round 6): ONE window read for two symbols.  The even step reads three dwords of the
-// lane's column -- bits [pos, pos + 64) -- and the odd step takes its window out of those: the
-// second symbol starts total1 <= 26 bits further and needs at most 26 bits, 52 <= 64.  The odd
-// step loses its address, its two LDS reads and one of the two LDS round trips of a symbol;
-// the even step pays one more read and one more funnel shift.
-template <int N, int K>
-__device__ __forceinline__ void lf_step_even(FastState& s, uint32_t vbase) {
-  const uint32_t ad = vbase + (s.Pn & ~1023u);
-  const uint32_t d1 = *(lds_u32p)(ad), d0 = *(lds_u32p)(ad + 4u * LJ_T), d2 = *(lds_u32p)(ad - 4u * LJ_T);
-  const uint32_t sh = s.Pn >> 5;
-  const uint32_t w = __builtin_amdgcn_alignbit(d0, d1, sh);
-  s.wb = __builtin_amdgcn_alignbit(d1, d2, sh);
-  s.w = w;
-  const lf_u32x2 e = *(lds_u2p)((w >> 19) & 0x1FF8u);
-  const uint32_t v = (w >> (e.x & 31u)) & e.y;
-  const uint32_t u = e.y - v;
-  const uint32_t m = uint32_t(int32_t(u - v) >> 31);
-  s.acc[K % N] += (e.y & m) - u;
-  s.Pn -= (e.x & 0x800007E0u);
-  s.sh = e.x;
-  s.n += 1;
-}
-template <int N, int K>
-__device__ __forceinline__ void lf_step_odd(FastState& s) {
-  const uint32_t w = __builtin_amdgcn_alignbit(s.w, s.wb, s.sh); // (w : wb) << total1, by 32 - total1 = sh & 31
-  const lf_u32x2 e = *(lds_u2p)((w >> 19) & 0x1FF8u);
-  const uint32_t v = (w >> (e.x & 31u)) & e.y;
-  const uint32_t u = e.y - v;
-  const uint32_t m = uint32_t(int32_t(u - v) >> 31);
-  s.acc[K % N] += (e.y & m) - u;
-  s.Pn -= (e.x & 0x800007E0u);
-  s.n += 1;
-}
-#endif
+// (Round 6 tried ONE window read for a pair of symbols -- three dwords in the even step, the odd
+// step's window taken out of those: one LDS round trip less a pair, bit-exact, and 0.385 against
+// 0.386 ms, as two window reads as separate LDS loads had been before it: the decode phase is not
+// what the kernel waits for.  profiles/r06/ab/pair_window_decode_*.txt)
 
 // Two tables that alternate symbol by symbol (round 4; the kernel's MT instantiations): both
 // 10-bit LUTs in the 8 KB the one table takes otherwise, as 4-byte entries
@@ -441,14 +388,7 @@ struct LfChain {
       else if constexpr (TM == 2)
         lf_step_pt<N, C>(s, vbase, C == 0 ? lut0 : (C == 1 ? lut1 : (C == 2 ? lut2 : lut3)));
       else {
-#ifdef RSX_LF_PAIRWIN
-        if constexpr ((K & 1) == 0)
-          lf_step_even<N, C>(s, vbase);
-        else
-          lf_step_odd<N, C>(s);
-#else
         lf_step<N, C, DIFF>(s, vbase);
-#endif
       }
       if ((K & 1) == 0)
         s.ev = s.acc[C];
@@ -638,12 +578,8 @@ __device__ __forceinline__ uint32_t fld_mask1(uint32_t flags2) { // two flag bit
 // (4 frames of noise; 3 components) faster, and a stream alone on the chip (1024 workgroups
 // in flight) still gains 6 % (profiles/r05/ab_lookback_window.txt).  The first pass looks at
 // the LF_LB1_WIN0 nearest only: 16 or 32 are another 2-5 % over 64, 8 and 4 no better.
-#ifndef LF_LB1_WAVES
-#define LF_LB1_WAVES 1
-#endif
-#ifndef LF_LB1_WIN0
-#define LF_LB1_WIN0 16
-#endif
+constexpr int LF_LB1_WAVES = 1;
+constexpr int LF_LB1_WIN0 = 16;
 // Look-back 1 (the whole workgroup, one record per lane and pass): the predictor state
 // (T, Vc) before the workgroup = the nearest inclusive state, carried through the LOCAL
 // transfers of the workgroups in between.  The transfers compose associatively: a
@@ -675,33 +611,6 @@ __device__ __forceinline__ bool lb1_walk(const LjArgs& a, const FastLds& F, uint
       wa[k] = wv_[k] = wt[k] = wc[k] = 0;
     if (real && inwin) {
       const u64* p = A + size_t(idx) * LF_LB_WORDS;
-#ifdef RSX_LF_LB16
-      // (coherent 16-byte loads: agent scope is `sc1`, as the compiler emits it for lb_load)
-      lf_u32x4 q[2 * NW];
-      if constexpr (NW == 1)
-        asm volatile("global_load_dwordx4 %0, %2, off offset:16 sc1\n\t"
-                     "global_load_dwordx4 %1, %2, off offset:32 sc1\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(q[0]), "=&v"(q[1])
-                     : "v"(p)
-                     : "memory");
-      else
-        asm volatile("global_load_dwordx4 %0, %4, off offset:16 sc1\n\t"
-                     "global_load_dwordx4 %1, %4, off offset:32 sc1\n\t"
-                     "global_load_dwordx4 %2, %4, off offset:48 sc1\n\t"
-                     "global_load_dwordx4 %3, %4, off offset:64 sc1\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2 * NW - 2]), "=&v"(q[2 * NW - 1])
-                     : "v"(p)
-                     : "memory");
-#pragma unroll
-      for (int k = 0; k < NW; ++k) {
-        wa[k] = u64(q[2 * k][0]) | (u64(q[2 * k][1]) << 32);
-        wv_[k] = u64(q[2 * k][2]) | (u64(q[2 * k][3]) << 32);
-        wt[k] = u64(q[2 * k + 1][0]) | (u64(q[2 * k + 1][1]) << 32);
-        wc[k] = u64(q[2 * k + 1][2]) | (u64(q[2 * k + 1][3]) << 32);
-      }
-#else
 #pragma unroll
       for (int k = 0; k < NW; ++k) {
         wa[k] = lb_load(p + lb_wa(k));
@@ -709,7 +618,6 @@ __device__ __forceinline__ bool lb1_walk(const LjArgs& a, const FastLds& F, uint
         wt[k] = lb_load(p + lb_wt(k));
         wc[k] = lb_load(p + lb_wc(k));
       }
-#endif
     }
     bool loc = true, pre = true;
 #pragma unroll
@@ -1047,11 +955,7 @@ __device__ __forceinline__ void lf_copy_out2(const FastLds& F, const LjArgs& a,
         if (LF_ABLATE & 256u) { // (experiment: everything but the stores)
           asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(p));
         } else if (sf >= 0 && uint32_t(sf) + 8u <= n) {
-#ifndef RSX_LF_PLAIN_MEM
           __builtin_nontemporal_store(lf_u32x4{o[0], o[1], o[2], o[3]}, reinterpret_cast<lf_u32x4*>(p));
-#else
-          *reinterpret_cast<uint4*>(p) = make_uint4(o[0], o[1], o[2], o[3]);
-#endif
         } else {
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
@@ -1263,7 +1167,6 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
   static_assert(!DIFF || (N == 1 && TM == 0), "differences: one table, symbols in stream order");
   static_assert(!NK || (N == 2 && TM == 0 && !DIFF), "Nikon-type pixels: one table, two column parities");
   constexpr bool MT = TM == 1, PT = TM == 2; // two alternating tables / a table per phase
-  constexpr uint32_t TICKET0 = (MT ? 12u : 0u) + (N == 4 ? 2u : (N == 3 ? 3u : uint32_t(N) - 1u));
   // offset (| table bit of the next symbol | its phase, two bits)
   constexpr uint32_t SMASK = MT ? 0x7Fu : (PT ? 0xFFu : ST_OFF_MASK);
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1274,11 +1177,8 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
 #endif
   // Is this launch the one that works (LjArgs::fast_lds_lv)?  An L2 load: the word changes
   // from run to run, and nothing invalidates a CU's scalar cache between two kernels of a
-  // stream (measured: stale level words).  At level 0, the usual one, the ticket is taken
-  // in the same round trip (every level has tickets of its own, on another cache line --
-  // 15 000 atomics on one address take 0.17 ms, so the other levels ask first).
-#ifndef RSX_LF_TICKETS
-  // Round 5: the block index IS the ticket.  The dispatcher starts a 1-D grid's workgroups
+  // stream (measured: stale level words).
+  // The block index IS the ticket (since round 5).  The dispatcher starts a 1-D grid's workgroups
   // in order (lj_unstuff_kernel's hand-over relies on the same), so a predecessor in
   // fast_order's sequence has started when its successor runs; an atomic ticket + its LDS
   // broadcast + barrier stood in front of everything else a workgroup asks for, a dependent
@@ -1290,7 +1190,6 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
   // Plans whose streams all have the same number of workgroups (frames of a batch, the tiles
   // of a DNG) work (stream, block) out arithmetically: nothing stands in front of the image
   // loads; the others read fast_order's entry first.
-  (void)TICKET0;
   lj_fresh_scalars<INV>();
   const uint32_t t_blk = a.blk0 + blockIdx.x;
   const uint32_t chosen_now = __hip_atomic_load(&a.fast_level[a.run_parity], __ATOMIC_RELAXED,
@@ -1323,32 +1222,6 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
     if (s == 0xFFFFFFFFu)
       return; // (a block no stream owns: plans laid out on the device, lj_dri_layout_kernel)
   }
-#else
-  if (j == 0) {
-    uint32_t chosen, t = 0;
-    if (level == 0) {
-      chosen = __hip_atomic_load(&a.fast_level[a.run_parity], __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-      t = atomicAdd(&a.tickets[TICKET0], 1u);
-    } else {
-      chosen = __hip_atomic_load(&a.fast_level[a.run_parity], __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-      if (chosen == level)
-        t = atomicAdd(&a.tickets[4 * level + TICKET0], 1u);
-    }
-    F.misc[M_TICKET] = chosen == level ? t : 0xFFFFFFFFu;
-  }
-  __syncthreads();
-  if (uni(F.misc[M_TICKET]) == 0xFFFFFFFFu)
-    return; // this run's workgroups need another LDS level: that launch does the work
-  // ticket -> block: the blocks of the launch's streams interleaved (each stream's in
-  // order, so every predecessor holds an earlier ticket).  A workgroup waits for ALL its
-  // stream's workgroups in flight; with one stream after the other that is everything on
-  // the chip, and it pays the slowest of ~1000 -- interleaved, 1000 / streams.
-  const uint4 bs = a.fast_order[uni(F.misc[M_TICKET])];
-  const uint32_t b = uni(bs.x), s = uni(bs.y), fb_now = uni(bs.w);
-  uint32_t tz_now = uni(bs.z);
-#endif
   // The workgroup's image and the stream's flags are asked for NOW, next to the stream's
   // record: the head of a workgroup is a chain of dependent loads (ticket -> block ->
   // stream -> flags -> table and image, 0.7-1.5 us each); the ticket's entry names the
@@ -1365,21 +1238,14 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
   uint4 im[5];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-#ifndef RSX_LF_PLAIN_MEM // (the un-stuffed image is read once: non-temporal, like the pixel stores --
-                         // together 1.5-2 % on cfg 3, cfg 4 and the Nikon legs, profiles/r06/ab/nontemporal.txt)
+    // (the un-stuffed image is read once: non-temporal, like the pixel stores -- together 1.5-2 % on
+    // cfg 3, cfg 4 and the Nikon legs, profiles/r06/ab/nontemporal.txt)
     const lf_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const lf_u32x4*>(img_src + k * LJ_T + j));
     im[k] = make_uint4(q[0], q[1], q[2], q[3]);
-#else
-    im[k] = img_src[k * LJ_T + j];
-#endif
   }
   // (the fifth: row 16 for the first 64 lanes; the others ask for their first chunk again --
   // a line they hold -- instead of rows 17..19, which nobody reads: 47 MB of HBM reads on cfg 3)
-#ifdef RSX_LF_FIFTH_PLAIN // (experiment: rows 17..19 read as well)
-  im[4] = img_src[4 * LJ_T + j];
-#else
   im[4] = img_src[j < LF_BW * LJ_T / 4 - 4 * LJ_T ? 4 * LJ_T + j : j];
-#endif
   const uint32_t ob_now = reinterpret_cast<const uint32_t*>(img_src + (LJ_BW / 4) * LJ_T)[j];
   // (a stream's subsequences are numbered from first_block * LJ_OWN: the guesses too; lane 0
   // reads lane 1's and ignores it)
@@ -1406,12 +1272,10 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
       kwv[it] = kw[k < lb_now ? k : lb_now];
     }
   }
-#ifndef RSX_LF_TICKETS
   if (uniform_plan) {
     const uint32_t tb = uni(tbv), tp = uni(tpv);
     tz_now = lf_table_word(tb, tp & 15u, (tp >> 8) & 15u, (tp >> 16) & 15u, (tp >> 24) & 15u);
   }
-#endif
   const uint32_t table_base = tz_now & 0xFFFFu;
   uint4 lut_now[MT ? 4 : 2];
   {
@@ -1463,10 +1327,8 @@ __global__ __launch_bounds__(LJ_T, LF_WG_PER_CU) void lj_fast_kernel(LjArgs a, u
                "v"(kwv[6]), "v"(kwv[7]), "v"(kwv[8]), "v"(kwv[9]), "v"(kwv[10]), "v"(kwv[11]),
                "v"(kwv[12]), "v"(kwv[13]), "v"(kwv[14]), "v"(kwv[15]));
   static_assert(LF_K0_IT == 16, "the pin lists the K0 words one by one");
-#ifndef RSX_LF_TICKETS
   if (uni(chosen_now) != level)
     return; // this run's workgroups need another LDS level: that launch does the work
-#endif
   if (int(S.fast_n) != N || int(S.tm) != TM || (S.diffs != 0u) != DIFF || (S.nk != 0u) != NK)
     return; // (workgroup-uniform)
   NkOut nko{};
@@ -2326,10 +2188,6 @@ uint32_t ljpeg_fast_lds_for(uint64_t samples) {
   need = (need + 1279) / 1280 * 1280;
   if (need < 40960)
     need = 40960; // (four workgroups per CU take 40 KB each anyway)
-#ifdef RSX_LF_MIN_LDS // (experiment: fewer resident workgroups, for the residency slope)
-  if (need < RSX_LF_MIN_LDS)
-    need = RSX_LF_MIN_LDS;
-#endif
   return need <= 64 * 1024 ? uint32_t(need) : 0u; // (more needs hipFuncSetAttribute)
 }
 
@@ -2399,9 +2257,8 @@ void ljpeg_launch_fast(const LjArgs& a, const FastLaunch& f, hipStream_t s, Kern
 void ljpeg_build_fast_table(const TabLds& t, uint2* out, uint32_t* zinfo) {
   *zinfo = 0;
   for (uint32_t i = 0; i < 1024; ++i) {
-    const uint32_t ea = reinterpret_cast<const uint16_t*>(t.lut)[2 * i * (sizeof(LutEntry) / 2)];
-    const uint32_t eb =
-        reinterpret_cast<const uint16_t*>(t.lut)[(2 * i + 1) * (sizeof(LutEntry) / 2)];
+    const uint32_t ea = t.lut[2 * i];
+    const uint32_t eb = t.lut[2 * i + 1];
     const uint32_t cl = ea & 31u, ssss = (ea >> 5) & 31u, total = ea >> 10;
     const bool plain = ea != 0 && cl <= 10u && ssss < 16u && total == cl + ssss && total >= 1u &&
                        total <= 26u;

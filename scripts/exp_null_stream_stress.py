@@ -4,7 +4,11 @@ arrays with it and the plan's kernels, on a hipStreamNonBlocking stream, could r
 host thread keeps the null stream busy on purpose (torch's default stream IS the null stream:
 torch.cuda._sleep; never more than BURST kernels of US microseconds queued), while LJPEG host calls of
 small tiles are made one after the other and compared with the oracle.
-   RSX_LIB=.../librsx_nosync.so BURST=4 US=10 python scripts/exp_null_stream_stress.py    (the old behaviour)"""
+   BURST=4 US=10 python scripts/exp_null_stream_stress.py
+(Round 6 also ran it against a library built WITHOUT the wait for the null stream at the end of plan
+creation -- the behaviour until then: wrong tiles with status OK, profiles/r06/host_path_defect/
+null_stream_stress_first_run.txt, memset_async_and_the_wrong_tiles.txt.  That comparison is done and
+its compile-time switch is gone from the source; the library always waits.)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
