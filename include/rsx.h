@@ -2560,6 +2560,149 @@ int rsx_plan_kernel_table(rsx_plan* plan, int cap, const char** names, double* a
                           int* n_kernels, int* n_runs);
 void rsx_plan_destroy(rsx_plan* plan);
 
+/* ------------------------------------------------------------------------ */
+/* 7. Writers: BitVacuumer* and PrefixCodeVectorEncoder                      */
+/*    The write direction of src/librawspeed: bitstreams/BitVacuumer.h with  */
+/*    BitVacuumerLSB.h, BitVacuumerMSB.h, BitVacuumerMSB16.h,                */
+/*    BitVacuumerMSB32.h and BitVacuumerJPEG.h, and codes/                   */
+/*    PrefixCodeVectorEncoder.h over codes/AbstractPrefixCodeEncoder.h.  The */
+/*    reference has no call site for them in its decoders (its benchmarks    */
+/*    and fuzzers use them): what binds these calls is a writer, a caller    */
+/*    who holds a decoded image on the device and wants it back as a packed  */
+/*    strip or as lossless-JPEG tiles (the raw-to-DNG direction).            */
+/*                                                                           */
+/*    7a. Packed integers: the inverse of decodePackedInt.  The descriptor   */
+/*    is rsx_unpack_desc with the reader's meaning: rows crop_y .. crop_y +  */
+/*    crop_h - 1 of the image become one continuous stream; each row gives   */
+/*    crop_w cpp samples of bits_per_pixel bits read from column 0 (the      */
+/*    reader ignores crop_x, and so does the writer) followed by             */
+/*    input_pitch_bytes - row_bytes zero bytes; the order is LSB, MSB, MSB16 */
+/*    or MSB32 with the word addressing of SURVEY.md A.1.  A sample's bits   */
+/*    above bits_per_pixel are dropped: BitStreamCache::push does not mask,  */
+/*    so this is the one deliberate difference from handing put an oversized */
+/*    value.  Tail: BitVacuumer::flush pads with zero bits to a whole 32-bit */
+/*    chunk, so roundUp(crop_h pitch, 4) bytes are written (bytes_written)   */
+/*    of which crop_h pitch are the stream (stream_bytes).  Validation: the  */
+/*    geometry checks of rsx_unpack_validate in its order; then crop_y +     */
+/*    crop_h > dim_y, an odd image pitch or one shorter than its samples,    */
+/*    and out_cap < roundUp(crop_h pitch, 4) -> RSX_ERR_INVALID_ARG.         */
+/*    Integer images only: at the reader's check of bits_per_pixel, 17..32   */
+/*    (the widths only an F32 image has) get RSX_ERR_UNSUPPORTED; anything   */
+/*    else outside 1..16 RSX_ERR_INVALID_ARG as the reader's does.           */
+/*    Image and output are both host pointers or both device pointers.       */
+/* ------------------------------------------------------------------------ */
+typedef struct rsx_encode_pack_result {
+  uint64_t bytes_written; /* roundUp(crop_h pitch, 4) */
+  uint64_t stream_bytes;  /* crop_h pitch */
+} rsx_encode_pack_result;
+
+int rsx_encode_pack_validate(const rsx_unpack_desc* d, const rsx_image* img, size_t out_cap);
+int rsx_encode_pack_u16(rsx_ctx* ctx, const rsx_unpack_desc* d, const rsx_image* img, uint8_t* out,
+                        size_t out_cap, rsx_encode_pack_result* bytes);
+
+/* A plan's input buffer holds images and its output buffer holds streams: the image of a job lies
+ * at img_offset (even) of the input, its stream goes to out_offset (any) of the output, at most
+ * out_cap bytes of it.  Nothing outside [out_offset, out_offset + bytes_written) is touched.  Jobs
+ * of any geometry and order share the plan's one launch.  Results report bytes_written as the
+ * bytes consumed. */
+typedef struct rsx_encode_pack_job {
+  rsx_unpack_desc desc;
+  uint32_t reserved;
+  uint64_t img_offset;
+  uint64_t out_offset;
+  uint64_t out_cap;
+  rsx_image img; /* .data ignored */
+} rsx_encode_pack_job;
+
+int rsx_encode_pack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_encode_pack_job* jobs,
+                                rsx_plan** out_plan);
+
+/* 7b. Lossless JPEG scan: the inverse of LJpegDecompressor::decode.  The descriptor is
+ * rsx_ljpeg_desc as it stands: a stream written for a descriptor decodes under that descriptor.
+ * Accepted is the subset in which every decoded pixel exists in the image: mcu_h == 1, mcu_w ==
+ * n_comp in 1..4, frame_w mcu_w == cpp tile_w, frame_h == tile_h, the tile inside the image,
+ * rows_per_restart_interval >= 1 (a value >= tile_h means no markers).  rsx_encode_ljpeg_validate
+ * returns, in this order, what rsx_ljpeg_validate returns for the descriptor, then
+ * RSX_ERR_UNSUPPORTED for MCU 2x2, a frame wider or taller than the tile or a trailing partial
+ * MCU, then RSX_ERR_INVALID_ARG for an odd image pitch or one shorter than its row.
+ * Per sample: predictor 1 as LJpegDecompressor reconstructs it (the left sample of the component;
+ * for the first MCU of a row the first MCU of the row above; in the first row of the tile or of a
+ * restart interval init_pred[c]); d = int16(uint16(x - pred)); (diff, ssss) = reduce(d) of
+ * AbstractPrefixCodeEncoder.h:48-58, -32768 giving ssss 16; the symbol word is the code followed
+ * by the ssss low bits, for ssss 16 the code alone, or with fix_dng_bug16 the code and 16 zero
+ * bits.  Every data byte FF is followed by 00 (BitVacuumerJPEG.h:84-91); between restart intervals
+ * the bit stream is closed and FF D0+((i-1)%8) follows (LJpegDecompressor.cpp:288-298).
+ * Tail, chosen by `flags`:
+ *   RSX_ENCODE_TAIL_JPEG      pad with 1-bits to a byte boundary, a final FF stuffed like any other
+ *                             (T.81 F.1.2.3; byte for byte the test writer's stream).  Intervals in
+ *                             front of a marker are closed like this in either mode: the
+ *                             reference's reader needs the marker at the next byte.
+ *   RSX_ENCODE_TAIL_VACUUMER  the last interval ends as BitVacuumerJPEG::flush ends it: zero bits
+ *                             up to a whole 32-bit chunk, the stuffing applied to its bytes.
+ * Results per job: status, entropy bytes written, symbol bits.  Data-dependent statuses: a
+ * category the component's table lacks -> RSX_ERR_BAD_HUFFMAN_CODE; a stream that would pass
+ * out_cap -> RSX_ERR_INPUT_OVERFLOW; in both cases 0 bytes are reported and the job's output range
+ * may hold anything up to out_cap but nothing past it.  out_cap below the bound is no error at
+ * validation.  rsx_encode_ljpeg_bound is the host closed form: 4 bytes a sample, doubled for
+ * stuffing, plus 2 a marker, plus 8 (0 for a descriptor the validation refuses). */
+#define RSX_ENCODE_TAIL_JPEG 0
+#define RSX_ENCODE_TAIL_VACUUMER 1
+
+typedef struct rsx_encode_result {
+  int32_t status;
+  int32_t reserved;
+  uint64_t bytes;       /* entropy bytes written (0 unless status is RSX_OK) */
+  uint64_t symbol_bits; /* code and difference bits, without padding, stuffing and markers */
+} rsx_encode_result;
+
+int rsx_encode_ljpeg_validate(const rsx_ljpeg_desc* d, const rsx_image* img);
+uint64_t rsx_encode_ljpeg_bound(const rsx_ljpeg_desc* d, const rsx_image* img);
+/* img->data and out: both host pointers or both device pointers; result: host.  Returns the
+ * job's status. */
+int rsx_encode_ljpeg(rsx_ctx* ctx, const rsx_ljpeg_desc* d, const rsx_image* img, uint32_t flags,
+                     uint8_t* out, size_t out_cap, rsx_encode_result* result);
+
+/* Jobs of different geometry and tables share a plan: the tiles of a DNG are the jobs of one
+ * plan.  rsx_plan_results reports per-job status and the bytes written as bytes consumed;
+ * rsx_encode_ljpeg_plan_result, after it, the whole result of job `job` of the last run.
+ * Nothing beyond the written bytes of a job is touched. */
+typedef struct rsx_encode_ljpeg_job {
+  rsx_ljpeg_desc desc;
+  uint32_t flags; /* RSX_ENCODE_TAIL_* */
+  uint32_t reserved;
+  uint64_t img_offset;
+  uint64_t out_offset;
+  uint64_t out_cap;
+  rsx_image img; /* .data ignored */
+} rsx_encode_ljpeg_job;
+
+int rsx_encode_ljpeg_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_encode_ljpeg_job* jobs,
+                                 rsx_plan** out_plan);
+int rsx_encode_ljpeg_plan_result(rsx_plan* plan, int job, rsx_encode_result* out);
+
+/* Host only: SOI, SOF3, DHT(s), optional DRI and SOS in front of a scan of `entropy_bytes` bytes
+ * into hdr_out (*hdr_bytes of them), in the layout of SURVEY.md Appendix C; EOI (FF D9) goes
+ * behind the scan and is the caller's to append.  With it a job's bytes become a tile that
+ * LJpegDecoder takes.  RSX_ERR_INVALID_ARG: a descriptor the validation refuses, a frame or a
+ * restart interval past 65535, hdr_cap too small. */
+int rsx_encode_ljpeg_container(const rsx_ljpeg_desc* d, const rsx_image* img, int32_t precision,
+                               uint64_t entropy_bytes, uint8_t* hdr_out, size_t hdr_cap,
+                               size_t* hdr_bytes);
+
+/* 7c. The difference histogram of a tile and the table made from it.  The histogram is the
+ * category of every sample's difference, counted per component: counts[17 c + ssss], 4 x 17
+ * 64-bit counts (host memory).  The call takes the descriptor of the encode and ignores its
+ * tables (they must still pass the validation).  img->data is a host or a device pointer.
+ * rsx_encode_huff_from_histogram (host only) turns 17 counts into a table by T.81 Annex K.2
+ * (Figures K.1 - K.4): the all-ones code point reserved, lengths limited to 16.  A category with
+ * count 0 is left out; RSX_ENCODE_TABLE_ALL_CATEGORIES gives every absent category of 0..16 a
+ * count of 1 first, so that the table also serves other tiles.  RSX_ERR_INVALID_ARG for a
+ * histogram without counts. */
+#define RSX_ENCODE_TABLE_ALL_CATEGORIES 1
+int rsx_encode_ljpeg_histogram(rsx_ctx* ctx, const rsx_ljpeg_desc* d, const rsx_image* img,
+                               uint64_t* counts);
+int rsx_encode_huff_from_histogram(const uint64_t* counts, uint32_t flags, rsx_huff_table* out);
+
 /* Measurement aid, not part of the decode path: runs a plain streaming kernel
  * (16-byte loads of in_bytes, 16-byte stores of out_bytes, device pointers) `reps`
  * times on `stream` and returns the average duration in ms, measured with

@@ -901,3 +901,43 @@ def hex_joined_hash(line_md5):
     import hashlib
     raw = bytes(line_md5)
     return hashlib.md5(raw.hex().encode()).hexdigest()
+
+
+# include/rsx.h section 7: the writers
+ENCODE_TAIL_JPEG, ENCODE_TAIL_VACUUMER = 0, 1
+ENCODE_TABLE_ALL_CATEGORIES = 1
+ENCODE_CATEGORIES = 17
+
+
+class EncodePackResult(C.Structure):
+    """rsx_encode_pack_result"""
+    _fields_ = [("bytes_written", C.c_uint64), ("stream_bytes", C.c_uint64)]
+
+
+class EncodeResult(C.Structure):
+    """rsx_encode_result"""
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_int32), ("bytes", C.c_uint64),
+                ("symbol_bits", C.c_uint64)]
+
+
+class EncodePackJob(C.Structure):
+    """rsx_encode_pack_job: the image in the run's input buffer, the stream in its output buffer"""
+    _fields_ = [("desc", UnpackDesc), ("reserved", C.c_uint32), ("img_offset", C.c_uint64),
+                ("out_offset", C.c_uint64), ("out_cap", C.c_uint64), ("img", Image)]
+
+
+class EncodeLJpegJob(C.Structure):
+    """rsx_encode_ljpeg_job"""
+    _fields_ = [("desc", LJpegDesc), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("img_offset", C.c_uint64), ("out_offset", C.c_uint64), ("out_cap", C.c_uint64),
+                ("img", Image)]
+
+
+def encode_pack_job(desc, img_offset, out_offset, out_cap, dim_x, dim_y, cpp, pitch_bytes):
+    return EncodePackJob(desc, 0, img_offset, out_offset, out_cap,
+                         Image(None, pitch_bytes, dim_x, dim_y, cpp, 1))
+
+
+def encode_ljpeg_job(desc, flags, img_offset, out_offset, out_cap, dim_x, dim_y, cpp, pitch_bytes):
+    return EncodeLJpegJob(desc, flags, 0, img_offset, out_offset, out_cap,
+                          Image(None, pitch_bytes, dim_x, dim_y, cpp, 1))

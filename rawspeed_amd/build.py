@@ -30,6 +30,8 @@
                                 the Sony SRF core (rsx_sony_srf_core.h) as host C++ (g++)
   rawspeed_amd/librsx_image_hash_host.so, rawspeed_amd/rsx_image_hash_host_check
                                 the image hash core (rsx_image_hash_core.h) as host C++ (g++)
+  rawspeed_amd/librsx_encode_host.so, rawspeed_amd/rsx_encode_host_check
+                                the writers' core (rsx_encode_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -73,6 +75,8 @@ LIB_SONY_SRF_HOST = os.path.join(PKG, "librsx_sony_srf_host.so")
 BIN_SONY_SRF_CHECK = os.path.join(PKG, "rsx_sony_srf_host_check")
 LIB_IMAGE_HASH_HOST = os.path.join(PKG, "librsx_image_hash_host.so")
 BIN_IMAGE_HASH_CHECK = os.path.join(PKG, "rsx_image_hash_host_check")
+LIB_ENCODE_HOST = os.path.join(PKG, "librsx_encode_host.so")
+BIN_ENCODE_CHECK = os.path.join(PKG, "rsx_encode_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
@@ -81,7 +85,7 @@ CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_dir
                 "rsx_iiq_corr.hip", "rsx_iiq_defects.hip", "rsx_dng_post.hip", "rsx_bad_pixels.hip", "rsx_scale.hip",
                 "rsx_dng_jpeg.hip", "rsx_fuji.hip", "rsx_olympus.hip", "rsx_kodak.hip",
                 "rsx_crw.hip", "rsx_fuji_rotate.hip", "rsx_sony_srf.hip",
-                "rsx_image_hash.hip", "rsx_host.cpp"]
+                "rsx_image_hash.hip", "rsx_encode_pack.hip", "rsx_encode_ljpeg.hip", "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
@@ -94,7 +98,7 @@ CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.
                 "rsx_olympus.h", "rsx_olympus_core.h", "rsx_kodak.h", "rsx_kodak_core.h",
                 "rsx_crw.h", "rsx_crw_core.h", "rsx_crw_tables.h", "rsx_fuji_rotate.h",
                 "rsx_fuji_rotate_core.h", "rsx_sony_srf.h", "rsx_sony_srf_core.h",
-                "rsx_image_hash.h", "rsx_image_hash_core.h"]
+                "rsx_image_hash.h", "rsx_image_hash_core.h", "rsx_encode.h", "rsx_encode_core.h"]
 
 
 def _hipcc():
@@ -262,6 +266,13 @@ def build_image_hash_host(force=False):
                             ["-pthread", "-I" + INCLUDE], force)
 
 
+def build_encode_host(force=False):
+    """rsx_encode_core.h: integers only, one thread a job"""
+    return _build_host_core(LIB_ENCODE_HOST, BIN_ENCODE_CHECK, "rsx_encode_host.cpp",
+                            ["rsx_encode_core.h", _RSX_H], "RSX_ENCODE_HOST_MAIN",
+                            ["-I" + INCLUDE], force)
+
+
 def _compile_objects(objdir, extra_flags, force=False):
     """One object per source under `objdir`, rebuilt when the source or any header is newer;
     the stale ones in parallel (the sources are independent translation units: one hipcc run
@@ -320,7 +331,7 @@ def build_all(force=False):
             build_bad_pixels_host(force), build_scale_host(force), build_jpeg_host(force),
             build_fuji_host(force), build_olympus_host(force), build_kodak_host(force),
             build_crw_host(force), build_fuji_rotate_host(force), build_sony_srf_host(force),
-            build_image_hash_host(force))
+            build_image_hash_host(force), build_encode_host(force))
 
 
 if __name__ == "__main__":

@@ -63,6 +63,10 @@ EXPORTS = [
     "rsx_sony_decrypt", "rsx_sony_srf_validate", "rsx_sony_srf_decompress",
     "rsx_sony_srf_plan_create",
     "rsx_image_hash_validate", "rsx_image_hash", "rsx_image_hash_plan_create",
+    "rsx_encode_pack_validate", "rsx_encode_pack_u16", "rsx_encode_pack_plan_create",
+    "rsx_encode_ljpeg_validate", "rsx_encode_ljpeg_bound", "rsx_encode_ljpeg",
+    "rsx_encode_ljpeg_plan_create", "rsx_encode_ljpeg_plan_result", "rsx_encode_ljpeg_container",
+    "rsx_encode_ljpeg_histogram", "rsx_encode_huff_from_histogram",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -225,6 +229,19 @@ def lib():
                                               C.c_void_p]
         L.rsx_image_hash_validate.argtypes = [C.c_void_p, C.c_int32]
         L.rsx_image_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.rsx_encode_pack_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_encode_pack_u16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]
+        L.rsx_encode_ljpeg_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_encode_ljpeg_bound.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_encode_ljpeg_bound.restype = C.c_uint64
+        L.rsx_encode_ljpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
+        L.rsx_encode_ljpeg_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_encode_ljpeg_container.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsx_encode_ljpeg_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_encode_huff_from_histogram.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -254,7 +271,8 @@ def lib():
                      "rsx_fuji_plan_create", "rsx_olympus_plan_create",
                      "rsx_kodak_plan_create", "rsx_crw_plan_create",
                      "rsx_raf_rotate_plan_create", "rsx_sony_srf_plan_create",
-                     "rsx_image_hash_plan_create"):
+                     "rsx_image_hash_plan_create", "rsx_encode_pack_plan_create",
+                     "rsx_encode_ljpeg_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -452,6 +470,38 @@ def sony_srf_validate(in_bytes, img_view):
 def image_hash_validate(img_view, sample_bytes):
     """rsx_image_hash_validate; img_view None passes a NULL image"""
     return lib().rsx_image_hash_validate(_ref(img_view), sample_bytes)
+
+
+def encode_pack_validate(desc, img_view, out_cap):
+    """rsx_encode_pack_validate; None passes NULL"""
+    return lib().rsx_encode_pack_validate(_ref(desc), _ref(img_view), out_cap)
+
+
+def encode_ljpeg_validate(desc, img_view):
+    """rsx_encode_ljpeg_validate; None passes NULL"""
+    return lib().rsx_encode_ljpeg_validate(_ref(desc), _ref(img_view))
+
+
+def encode_ljpeg_bound(desc, img_view):
+    return int(lib().rsx_encode_ljpeg_bound(_ref(desc), _ref(img_view)))
+
+
+def encode_ljpeg_container(desc, img_view, precision, entropy_bytes=0, cap=1024):
+    """rsx_encode_ljpeg_container -> (status, the header's bytes or None)"""
+    hdr = np.empty(max(cap, 1), dtype=np.uint8)
+    n = C.c_size_t(0)
+    st = lib().rsx_encode_ljpeg_container(_ref(desc), _ref(img_view), precision, entropy_bytes,
+                                          hdr.ctypes.data, cap, C.byref(n))
+    return st, (hdr[:n.value].copy() if st == abi.RSX_OK else None)
+
+
+def encode_huff_from_histogram(counts, flags=0):
+    """rsx_encode_huff_from_histogram: 17 counts -> (status, abi.HuffTable)"""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    assert c.size == abi.ENCODE_CATEGORIES
+    t = abi.HuffTable()
+    st = lib().rsx_encode_huff_from_histogram(c.ctypes.data, flags, C.byref(t))
+    return st, t
 
 
 def dng_deflate_tile(geom, in_bytes=0, in_ptr=None):
@@ -1057,6 +1107,36 @@ class Context:
         """jobs: abi.SonySrfJob, one per frame (geometries and keys may mix)"""
         return Plan(self, "rsx_sony_srf_plan_create", abi.SonySrfJob, jobs)
 
+    def encode_pack_u16(self, desc, img_view, out_ptr, out_cap):
+        """rsx_encode_pack_u16: img_view.data and out_ptr are both host or both device pointers.
+        Returns (status, bytes written, stream bytes)."""
+        r = abi.EncodePackResult()
+        st = lib().rsx_encode_pack_u16(self._h, C.byref(desc), C.byref(img_view), C.c_void_p(out_ptr),
+                                       out_cap, C.byref(r))
+        return st, int(r.bytes_written), int(r.stream_bytes)
+
+    def encode_ljpeg(self, desc, img_view, flags, out_ptr, out_cap):
+        """rsx_encode_ljpeg -> (status, abi.EncodeResult)"""
+        r = abi.EncodeResult()
+        st = lib().rsx_encode_ljpeg(self._h, C.byref(desc), C.byref(img_view), flags,
+                                    C.c_void_p(out_ptr), out_cap, C.byref(r))
+        return st, r
+
+    def encode_ljpeg_histogram(self, desc, img_view):
+        """rsx_encode_ljpeg_histogram -> (status, counts[4][17] as np.uint64)"""
+        counts = np.zeros((4, abi.ENCODE_CATEGORIES), dtype=np.uint64)
+        st = lib().rsx_encode_ljpeg_histogram(self._h, C.byref(desc), C.byref(img_view),
+                                              counts.ctypes.data)
+        return st, counts
+
+    def encode_pack_plan(self, jobs):
+        """jobs: abi.EncodePackJob; run(images_base, streams_base)"""
+        return Plan(self, "rsx_encode_pack_plan_create", abi.EncodePackJob, jobs)
+
+    def encode_ljpeg_plan(self, jobs):
+        """jobs: abi.EncodeLJpegJob (the tiles of a DNG are the jobs of one plan)"""
+        return EncodeLJpegPlan(self, "rsx_encode_ljpeg_plan_create", abi.EncodeLJpegJob, jobs)
+
     def image_hash_plan(self, jobs):
         """jobs: abi.ImageHashJob, one per image (geometries and sample sizes may mix);
         run(images_base, outputs_base)"""
@@ -1154,6 +1234,14 @@ class BadPixelsPlan(Plan):
         """after results(): (status, abi.BadPixelsResult) of job `job`"""
         r = abi.BadPixelsResult()
         st = lib().rsx_bad_pixels_plan_result(self._h, job, C.byref(r))
+        return st, r
+
+
+class EncodeLJpegPlan(Plan):
+    def result(self, job):
+        """after results(): (status, abi.EncodeResult) of job `job`"""
+        r = abi.EncodeResult()
+        st = lib().rsx_encode_ljpeg_plan_result(self._h, job, C.byref(r))
         return st, r
 
 

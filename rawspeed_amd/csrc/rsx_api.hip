@@ -36,6 +36,8 @@
 #include "rsx_scale.h"
 #include "rsx_dng_jpeg.h"
 #include "rsx_jpeg_core.h"
+#include "rsx_encode.h"
+#include "rsx_encode_core.h"
 
 #include <algorithm>
 #include <map>
@@ -4772,6 +4774,276 @@ extern "C" int rsx_image_hash(rsx_ctx* ctx, const rsx_image* img, int32_t sample
     std::memcpy(line_md5, back.data(), lines_bytes);
   std::memcpy(out, back.data() + lines_bytes, sizeof *out);
   return RSX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Writers: BitVacuumer{LSB,MSB,MSB16,MSB32,JPEG}, PrefixCodeVectorEncoder (rsx.h section 7)
+// ---------------------------------------------------------------------------
+extern "C" int rsx_encode_pack_validate(const rsx_unpack_desc* d, const rsx_image* img,
+                                        size_t out_cap) {
+  return rsx_encode::validate_pack(d, img, out_cap);
+}
+
+extern "C" int rsx_encode_pack_plan_create(rsx_ctx* ctx, int n_jobs,
+                                           const rsx_encode_pack_job* jobs, rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, encode_pack_plan_create);
+}
+
+namespace {
+// Both device pointers or both host pointers (`*dev` says which); RSX_ERR_INVALID_ARG for a mix.
+int same_side(const void* a, const void* b, bool* dev) {
+  const bool da = is_device_pointer(a), db = is_device_pointer(b);
+  *dev = da;
+  return da == db ? RSX_OK : RSX_ERR_INVALID_ARG;
+}
+
+// The base a plan of one job runs on when its image and its output are two device pointers: the
+// lower of the two on the samples' grid, and the offsets of both from it.
+const uint8_t* device_base(const void* img, const void* out, uint64_t* img_off, uint64_t* out_off) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(img), b = reinterpret_cast<uintptr_t>(out);
+  const uintptr_t base = (a < b ? a : b) & ~uintptr_t(1);
+  *img_off = a - base;
+  *out_off = b - base;
+  return reinterpret_cast<const uint8_t*>(base);
+}
+
+// Rows [y0, y0 + rows) of the caller's image, whole, into the lane's input buffer as one copy.
+int upload_rows(rsx_ctx* ctx, rsx_ctx::HostLane* L, const rsx_image* img, int32_t y0, int32_t rows) {
+  const size_t bytes = size_t(img->pitch_bytes) * size_t(rows - 1) +
+                       size_t(img->dim_x) * size_t(img->cpp) * 2;
+  if (int e = L->d_in.ensure(bytes + 64))
+    return e;
+  std::lock_guard<std::mutex> up(ctx->upload_mu);
+  RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr,
+                                    static_cast<const uint8_t*>(img->data) +
+                                        size_t(y0) * img->pitch_bytes,
+                                    bytes, hipMemcpyHostToDevice, L->stream));
+  return RSX_OK;
+}
+
+int download_bytes(rsx_ctx* ctx, rsx_ctx::HostLane* L, uint8_t* out, size_t bytes) {
+  if (bytes == 0)
+    return RSX_OK;
+  const DownRect dr{out, 0, static_cast<const uint8_t*>(L->d_out.ptr), 0, bytes, 1};
+  std::lock_guard<std::mutex> down_lock(ctx->download_mu);
+  return download_rects(ctx, L, L->stream, &dr, 1);
+}
+} // namespace
+
+// Device pointers: a plan of one job runs on them where they lie, on the context's stream behind
+// the null stream's work so far, and the call returns when it is done.  Host pointers: the rows
+// crop_y .. go up as one copy into a lane and the stream comes back as one.
+extern "C" int rsx_encode_pack_u16(rsx_ctx* ctx, const rsx_unpack_desc* d, const rsx_image* img,
+                                   uint8_t* out, size_t out_cap, rsx_encode_pack_result* bytes) {
+  if (bytes)
+    std::memset(bytes, 0, sizeof *bytes);
+  if (!ctx || !d || !img || !img->data || !out || !bytes)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_encode::validate_pack(d, img, out_cap))
+    return st;
+  if (reinterpret_cast<uintptr_t>(img->data) % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  bool dev = false;
+  if (int st = same_side(img->data, out, &dev))
+    return st;
+  rsx_encode_pack_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *d;
+  job.img = *img;
+  job.img.data = nullptr;
+  job.out_cap = out_cap;
+  const uint64_t stream_bytes = uint64_t(d->crop_h) * uint64_t(d->input_pitch_bytes);
+  const uint64_t written = rsx_encode::round_up4(stream_bytes);
+  CallPlan call;
+  if (dev) {
+    const uint8_t* base = device_base(img->data, out, &job.img_offset, &job.out_offset);
+    if (int st = rsx_encode_pack_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    if (int st = call.run(base, const_cast<uint8_t*>(base), nullptr))
+      return st;
+  } else {
+    job.desc.crop_y = 0;
+    job.img.dim_y = d->crop_h;
+    if (int st = rsx_encode_pack_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    LaneGuard lane(ctx);
+    if (!lane.lane)
+      return RSX_ERR_DEVICE;
+    if (int e = upload_rows(ctx, lane.lane, img, d->crop_y, d->crop_h))
+      return e;
+    if (int e = lane.lane->d_out.ensure(size_t(written) + 64))
+      return e;
+    if (int st = rsx_plan_run(call.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, lane.lane->stream))
+      return st;
+    if (int e = download_bytes(ctx, lane.lane, out, size_t(written)))
+      return e;
+  }
+  bytes->bytes_written = written;
+  bytes->stream_bytes = stream_bytes;
+  return RSX_OK;
+}
+
+extern "C" int rsx_encode_ljpeg_validate(const rsx_ljpeg_desc* d, const rsx_image* img) {
+  if (!d || !img)
+    return RSX_ERR_INVALID_ARG;
+  if (int st = validate_ljpeg(*d, *img))
+    return st;
+  return rsx_encode::validate_ljpeg_subset(*d, *img);
+}
+
+extern "C" uint64_t rsx_encode_ljpeg_bound(const rsx_ljpeg_desc* d, const rsx_image* img) {
+  if (rsx_encode_ljpeg_validate(d, img) != RSX_OK)
+    return 0;
+  rsx_encode::LJpegGeom g;
+  rsx_encode::ljpeg_geom(*d, *img, 0, 0, 0, 0, &g);
+  return rsx_encode::ljpeg_bound(g);
+}
+
+extern "C" int rsx_encode_ljpeg_plan_create(rsx_ctx* ctx, int n_jobs,
+                                            const rsx_encode_ljpeg_job* jobs, rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, encode_ljpeg_plan_create);
+}
+
+extern "C" int rsx_encode_ljpeg_plan_result(rsx_plan* plan, int job, rsx_encode_result* out) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->encode_result(job, out); });
+}
+
+// Device pointers: as above, and only the result comes back.  Host pointers: the tile's rows go up
+// as one copy into a lane; the stream is written there (into at most the bound's bytes) and the
+// bytes the result counts come back.
+extern "C" int rsx_encode_ljpeg(rsx_ctx* ctx, const rsx_ljpeg_desc* d, const rsx_image* img,
+                                uint32_t flags, uint8_t* out, size_t out_cap,
+                                rsx_encode_result* result) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !d || !img || !img->data || !out || !result || flags > RSX_ENCODE_TAIL_VACUUMER)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_encode_ljpeg_validate(d, img))
+    return result->status = st;
+  if (reinterpret_cast<uintptr_t>(img->data) % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  bool dev = false;
+  if (int st = same_side(img->data, out, &dev))
+    return st;
+  rsx_encode_ljpeg_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *d;
+  job.flags = flags;
+  job.img = *img;
+  job.img.data = nullptr;
+  job.out_cap = out_cap;
+  CallPlan call;
+  if (dev) {
+    const uint8_t* base = device_base(img->data, out, &job.img_offset, &job.out_offset);
+    if (int st = rsx_encode_ljpeg_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    if (int st = rsx_plan_run(call.plan, base, const_cast<uint8_t*>(base), nullptr))
+      return st;
+    rsx_plan_results(call.plan, nullptr, nullptr);
+    if (int st = rsx_encode_ljpeg_plan_result(call.plan, 0, result))
+      return st;
+    return result->status;
+  }
+  job.desc.tile_y = 0;
+  job.img.dim_y = d->tile_h;
+  const uint64_t bound = rsx_encode_ljpeg_bound(d, img);
+  const size_t room = size_t(uint64_t(out_cap) < bound ? uint64_t(out_cap) : bound);
+  job.out_cap = room;
+  if (int st = rsx_encode_ljpeg_plan_create(ctx, 1, &job, &call.plan))
+    return st;
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  if (int e = upload_rows(ctx, lane.lane, img, d->tile_y, d->tile_h))
+    return e;
+  if (int e = lane.lane->d_out.ensure(room + 64))
+    return e;
+  if (int st = rsx_plan_run(call.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, lane.lane->stream))
+    return st;
+  rsx_plan_results(call.plan, nullptr, nullptr);
+  if (int st = rsx_encode_ljpeg_plan_result(call.plan, 0, result))
+    return st;
+  if (result->status == RSX_OK)
+    if (int e = download_bytes(ctx, lane.lane, out, size_t(result->bytes)))
+      return e;
+  return result->status;
+}
+
+extern "C" int rsx_encode_ljpeg_container(const rsx_ljpeg_desc* d, const rsx_image* img,
+                                          int32_t precision, uint64_t entropy_bytes,
+                                          uint8_t* hdr_out, size_t hdr_cap, size_t* hdr_bytes) {
+  (void)entropy_bytes; // (no field of the layout holds the scan's length)
+  if (!hdr_out || !hdr_bytes || precision < 2 || precision > 16)
+    return RSX_ERR_INVALID_ARG;
+  if (int st = rsx_encode_ljpeg_validate(d, img))
+    return st;
+  const bool markers = d->rows_per_restart_interval < d->tile_h;
+  if (d->frame_w > 0xFFFF || d->frame_h > 0xFFFF ||
+      (markers && int64_t(d->rows_per_restart_interval) * d->frame_w > 0xFFFF))
+    return RSX_ERR_INVALID_ARG;
+  *hdr_bytes = rsx_encode::ljpeg_container(*d, precision, hdr_out, hdr_cap);
+  return *hdr_bytes ? RSX_OK : RSX_ERR_INVALID_ARG;
+}
+
+extern "C" int rsx_encode_huff_from_histogram(const uint64_t* counts, uint32_t flags,
+                                              rsx_huff_table* out) {
+  if (!counts || !out || (flags & ~uint32_t(RSX_ENCODE_TABLE_ALL_CATEGORIES)))
+    return RSX_ERR_INVALID_ARG;
+  return rsx_encode::huff_from_histogram(counts, (flags & RSX_ENCODE_TABLE_ALL_CATEGORIES) != 0, out);
+}
+
+// A histogram plan of one job whose output is the 4 x 17 counts.  A device pointer: the plan runs
+// on the image where it lies and the counts alone come back.  A host pointer: the tile's rows go
+// up as one copy into a lane.
+extern "C" int rsx_encode_ljpeg_histogram(rsx_ctx* ctx, const rsx_ljpeg_desc* d,
+                                          const rsx_image* img, uint64_t* counts) {
+  if (!ctx || !d || !img || !img->data || !counts)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_encode_ljpeg_validate(d, img))
+    return st;
+  if (reinterpret_cast<uintptr_t>(img->data) % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  constexpr size_t BYTES = 4 * rsx_encode::N_CATEGORIES * sizeof(uint64_t);
+  rsx_encode_ljpeg_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *d;
+  job.img = *img;
+  job.img.data = nullptr;
+  job.out_cap = BYTES;
+  const bool dev = is_device_pointer(img->data);
+  if (!dev) {
+    job.desc.tile_y = 0;
+    job.img.dim_y = d->tile_h;
+  }
+  CallPlan call;
+  if (int st = decoder_plan_create(ctx, 1, &job, &call.plan, encode_histogram_plan_create))
+    return st;
+  if (dev) {
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    DeviceBuffer d_back;
+    if (int e = d_back.ensure(BYTES + 16))
+      return e;
+    if (int st = rsx_plan_run(call.plan, img->data, d_back.ptr, nullptr))
+      return st;
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(counts, d_back.ptr, BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    return rsx_plan_results(call.plan, nullptr, nullptr); // (waits for the stream)
+  }
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  if (int e = upload_rows(ctx, lane.lane, img, d->tile_y, d->tile_h))
+    return e;
+  if (int e = lane.lane->d_out.ensure(BYTES + 64))
+    return e;
+  if (int st = rsx_plan_run(call.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, lane.lane->stream))
+    return st;
+  return download_bytes(ctx, lane.lane, reinterpret_cast<uint8_t*>(counts), BYTES);
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

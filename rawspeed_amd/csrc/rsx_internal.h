@@ -203,6 +203,8 @@ struct DecoderPlan {
   }
   // the levels and the verdict of job `job` of the last run, after results (scaling plans)
   virtual int scale_result(int /*job*/, rsx_scale_result* /*out*/) { return RSX_ERR_INVALID_ARG; }
+  // status, bytes and symbol bits of job `job` of the last run, after results (LJPEG writer plans)
+  virtual int encode_result(int /*job*/, rsx_encode_result* /*out*/) { return RSX_ERR_INVALID_ARG; }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };
