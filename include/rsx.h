@@ -2703,6 +2703,131 @@ int rsx_encode_ljpeg_histogram(rsx_ctx* ctx, const rsx_ljpeg_desc* d, const rsx_
                                uint64_t* counts);
 int rsx_encode_huff_from_histogram(const uint64_t* counts, uint32_t flags, rsx_huff_table* out);
 
+/* 7d. Floating-point images (RawImageType::F32): the inverse of rsx_unpack_f32 (section 1a) and
+ * the width an image needs.  All names begin with rsx_fpwrite_.
+ *
+ * Narrowing.  binary32 -> binary16 (16 bits) or binary24 (24 bits) is the inverse of
+ * extendBinaryFloatingPoint (common/FloatingPoint.h:109-145) and is defined only where widening
+ * the result gives the sample back as a 32-bit pattern: no rounding, no clamping.  The rule is
+ * bitwise: -0, the infinities and NaNs whose low 23 - FRAC fraction bits are zero have a narrow
+ * pattern; a binary32 normal in the narrow format's subnormal range has one iff the bits shifted
+ * out are zero; a binary32 subnormal other than +-0 has none.  A sample without one is inexact.
+ *
+ * rsx_fpwrite_fit reports for each window of an F32 image the least of 16 / 24 / 32 under which
+ * every sample of the window narrows exactly: what a DNG writer sets BitsPerSample from.  A window
+ * counts samples (cpp folded in: x in [0, dim_x cpp)).  img->data is a host or a device pointer;
+ * all windows share one launch.  RSX_ERR_INVALID_ARG: no window, a window empty or outside the
+ * image, dim_x or dim_y < 1, cpp outside 1..4, a pitch that is no multiple of 4 or shorter than a
+ * row, data off the 4-byte grid.
+ *
+ * rsx_fpwrite_pack.  The descriptor is rsx_unpack_desc with the meaning rsx_unpack_f32 gives it:
+ * 32 bits is copyPixels (crop_x counts pixels), 16 and 24 bits are MSB or LSB order (whole bytes:
+ * big- or little-endian samples) and crop_x is a SAMPLE offset as decodePackedFP has it; each row
+ * gives crop_w cpp samples followed by input_pitch_bytes - row_bytes zero bytes; the tail follows
+ * 7a: roundUp(crop_h pitch, 4) bytes are written.  A stream written for a descriptor unpacks under
+ * that descriptor to the same image.  Validation: rsx_unpack_f32_validate's verdicts in its order
+ * (of its size checks, the 32-bit one), then dim_x or dim_y < 1, a crop outside the image, an image pitch that is no
+ * multiple of 4 or shorter than the samples read, and out_cap < roundUp(crop_h pitch, 4) ->
+ * RSX_ERR_INVALID_ARG.  An inexact sample gives the job RSX_ERR_VALUE_RANGE: bytes_written is 0,
+ * `inexact` counts such samples, and the job's output range may hold anything up to
+ * roundUp(crop_h pitch, 4) bytes but nothing past it.  Image and output are both host pointers or
+ * both device pointers. */
+typedef struct rsx_fpwrite_window {
+  int32_t x, y, w, h; /* samples */
+} rsx_fpwrite_window;
+
+int rsx_fpwrite_fit(rsx_ctx* ctx, const rsx_image* img, int n_windows,
+                    const rsx_fpwrite_window* windows, int32_t* min_bps_out);
+
+typedef struct rsx_fpwrite_pack_result {
+  uint64_t bytes_written; /* roundUp(crop_h pitch, 4); 0 unless the status is RSX_OK */
+  uint64_t stream_bytes;  /* crop_h pitch */
+  uint64_t inexact;       /* samples without a narrow pattern */
+} rsx_fpwrite_pack_result;
+
+int rsx_fpwrite_pack_validate(const rsx_unpack_desc* d, const rsx_image* img, size_t out_cap);
+int rsx_fpwrite_pack(rsx_ctx* ctx, const rsx_unpack_desc* d, const rsx_image* img, uint8_t* out,
+                     size_t out_cap, rsx_fpwrite_pack_result* result);
+
+/* Jobs as in 7a: the image of a job lies at img_offset (a multiple of 4) of the plan's input
+ * buffer, its stream goes to out_offset (any) of the output buffer.  rsx_plan_results reports
+ * per-job status and the bytes written as bytes consumed; rsx_fpwrite_pack_plan_result, after it,
+ * the whole result of job `job` of the last run. */
+typedef struct rsx_fpwrite_pack_job {
+  rsx_unpack_desc desc;
+  uint32_t reserved;
+  uint64_t img_offset;
+  uint64_t out_offset;
+  uint64_t out_cap;
+  rsx_image img; /* .data ignored */
+} rsx_fpwrite_pack_job;
+
+int rsx_fpwrite_pack_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fpwrite_pack_job* jobs,
+                                 rsx_plan** out_plan);
+int rsx_fpwrite_pack_plan_result(rsx_plan* plan, int job, rsx_fpwrite_pack_result* out);
+
+/* Deflate tiles (compression 8): the inverse of rsx_dng_decompress_deflate (section 4b).  The
+ * descriptor is rsx_dng_deflate_desc as it stands; a tile carries the geometry of
+ * rsx_dng_deflate_tile, in samples with cpp folded in (predFactor = {1, 2, 4} cpp), and where its
+ * stream goes.  The bytes a tile compresses: per row bytesps byte planes of tile_w bytes, most significant
+ * first, of the narrow samples (0 outside the window), then b[col] -= b[col - predFactor] from the
+ * end of the row down where the row is longer than predFactor.  The stream: CMF 0x78, FLG 0x01 (no
+ * FDICT), deflate blocks of RSX_FPWRITE_BLOCK input bytes each (the last one shorter), the
+ * big-endian Adler-32 of the bytes.  A block is dynamic-Huffman, or stored when the stored form
+ * (padding included) is not longer.  Matches: length 3..258, distance 1..32768, across block
+ * boundaries but never before the tile's first byte nor past the block's end.  The stream is a
+ * function of the tile's bytes alone: the same from run to run, and byte for byte what the host
+ * build of rsx_deflate_core.h writes.
+ * Validation: rsx_dng_deflate_validate's verdicts in its order, then a NULL or mixed-side pointer,
+ * a tile of 2^28 bytes or more -> RSX_ERR_UNSUPPORTED.  Per tile: an inexact sample ->
+ * RSX_ERR_VALUE_RANGE; a stream that would pass out_cap -> RSX_ERR_INPUT_OVERFLOW; in both cases 0
+ * bytes are reported and nothing at or past out_cap is touched (nothing is written at all).  The
+ * call returns RSX_ERR_TILE_ERRORS if any tile failed.  rsx_fpwrite_deflate_bound is the host
+ * closed form: the tile's bytes + 6 a block (3 header bits, up to 7 bits of padding, LEN, NLEN) +
+ * 2 + 4; the emit writes single bytes and needs no word padding (0 for a refused tile). */
+#define RSX_FPWRITE_BLOCK 16384
+
+typedef struct rsx_fpwrite_deflate_tile {
+  uint8_t* out;
+  size_t out_cap;
+  uint32_t tile_w, tile_h;              /* samples */
+  uint32_t off_x, off_y, width, height; /* samples */
+} rsx_fpwrite_deflate_tile;
+
+typedef struct rsx_fpwrite_deflate_result {
+  int32_t status;
+  uint32_t adler;         /* Adler-32 of the tile's bytes */
+  uint64_t bytes;         /* of the stream (0 unless status is RSX_OK) */
+  uint32_t blocks;        /* deflate blocks */
+  uint32_t stored_blocks; /* ... of which stored */
+} rsx_fpwrite_deflate_result;
+
+int rsx_fpwrite_deflate_validate(const rsx_dng_deflate_desc* desc,
+                                 const rsx_fpwrite_deflate_tile* tile, const rsx_image* img);
+uint64_t rsx_fpwrite_deflate_bound(const rsx_dng_deflate_desc* desc,
+                                   const rsx_fpwrite_deflate_tile* tile, const rsx_image* img);
+/* img->data and every tile's out: all host pointers or all device pointers; results: host */
+int rsx_fpwrite_deflate(rsx_ctx* ctx, const rsx_dng_deflate_desc* desc, int n_tiles,
+                        const rsx_fpwrite_deflate_tile* tiles, const rsx_image* img,
+                        rsx_fpwrite_deflate_result* results);
+
+/* a tile of a plan: the image at img_offset (a multiple of 4) of the run's input buffer, the
+ * stream at out_offset of its output buffer.  rsx_plan_results reports per-job status and the
+ * stream's bytes as bytes consumed; rsx_fpwrite_deflate_plan_result the whole result. */
+typedef struct rsx_fpwrite_deflate_job {
+  rsx_dng_deflate_desc desc;
+  uint32_t tile_w, tile_h;
+  uint32_t off_x, off_y, width, height;
+  uint64_t img_offset;
+  uint64_t out_offset;
+  uint64_t out_cap;
+  rsx_image img; /* .data ignored */
+} rsx_fpwrite_deflate_job;
+
+int rsx_fpwrite_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fpwrite_deflate_job* jobs,
+                                    rsx_plan** out_plan);
+int rsx_fpwrite_deflate_plan_result(rsx_plan* plan, int job, rsx_fpwrite_deflate_result* out);
+
 /* Measurement aid, not part of the decode path: runs a plain streaming kernel
  * (16-byte loads of in_bytes, 16-byte stores of out_bytes, device pointers) `reps`
  * times on `stream` and returns the average duration in ms, measured with

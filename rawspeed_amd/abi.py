@@ -941,3 +941,52 @@ def encode_pack_job(desc, img_offset, out_offset, out_cap, dim_x, dim_y, cpp, pi
 def encode_ljpeg_job(desc, flags, img_offset, out_offset, out_cap, dim_x, dim_y, cpp, pitch_bytes):
     return EncodeLJpegJob(desc, flags, 0, img_offset, out_offset, out_cap,
                           Image(None, pitch_bytes, dim_x, dim_y, cpp, 1))
+
+
+# include/rsx.h section 7d: the writers of F32 images
+class FpWriteWindow(C.Structure):
+    """rsx_fpwrite_window: samples, cpp folded in"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class FpWritePackResult(C.Structure):
+    """rsx_fpwrite_pack_result"""
+    _fields_ = [("bytes_written", C.c_uint64), ("stream_bytes", C.c_uint64),
+                ("inexact", C.c_uint64)]
+
+
+class FpWritePackJob(C.Structure):
+    """rsx_fpwrite_pack_job: the image in the run's input buffer, the stream in its output buffer"""
+    _fields_ = [("desc", UnpackDesc), ("reserved", C.c_uint32), ("img_offset", C.c_uint64),
+                ("out_offset", C.c_uint64), ("out_cap", C.c_uint64), ("img", Image)]
+
+
+def fpwrite_pack_job(desc, img_offset, out_offset, out_cap, dim_x, dim_y, cpp, pitch_bytes):
+    return FpWritePackJob(desc, 0, img_offset, out_offset, out_cap,
+                          Image(None, pitch_bytes, dim_x, dim_y, cpp, 1))
+
+
+FPWRITE_BLOCK = 16384
+
+
+class FpWriteDeflateTile(C.Structure):
+    """rsx_fpwrite_deflate_tile: geometry in samples, as DngDeflateTile"""
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_size_t),
+                ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("off_x", C.c_uint32), ("off_y", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class FpWriteDeflateResult(C.Structure):
+    """rsx_fpwrite_deflate_result"""
+    _fields_ = [("status", C.c_int32), ("adler", C.c_uint32), ("bytes", C.c_uint64),
+                ("blocks", C.c_uint32), ("stored_blocks", C.c_uint32)]
+
+
+class FpWriteDeflateJob(C.Structure):
+    """rsx_fpwrite_deflate_job"""
+    _fields_ = [("desc", DngDeflateDesc), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("off_x", C.c_uint32), ("off_y", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32),
+                ("img_offset", C.c_uint64), ("out_offset", C.c_uint64), ("out_cap", C.c_uint64),
+                ("img", Image)]

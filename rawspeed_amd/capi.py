@@ -67,6 +67,10 @@ EXPORTS = [
     "rsx_encode_ljpeg_validate", "rsx_encode_ljpeg_bound", "rsx_encode_ljpeg",
     "rsx_encode_ljpeg_plan_create", "rsx_encode_ljpeg_plan_result", "rsx_encode_ljpeg_container",
     "rsx_encode_ljpeg_histogram", "rsx_encode_huff_from_histogram",
+    "rsx_fpwrite_fit", "rsx_fpwrite_pack_validate", "rsx_fpwrite_pack",
+    "rsx_fpwrite_pack_plan_create", "rsx_fpwrite_pack_plan_result",
+    "rsx_fpwrite_deflate_validate", "rsx_fpwrite_deflate_bound", "rsx_fpwrite_deflate",
+    "rsx_fpwrite_deflate_plan_create", "rsx_fpwrite_deflate_plan_result",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -242,6 +246,17 @@ def lib():
                                                  C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsx_encode_ljpeg_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsx_encode_huff_from_histogram.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rsx_fpwrite_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rsx_fpwrite_pack_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsx_fpwrite_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]
+        L.rsx_fpwrite_pack_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_fpwrite_deflate_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_fpwrite_deflate_bound.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_fpwrite_deflate_bound.restype = C.c_uint64
+        L.rsx_fpwrite_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        L.rsx_fpwrite_deflate_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -272,7 +287,8 @@ def lib():
                      "rsx_kodak_plan_create", "rsx_crw_plan_create",
                      "rsx_raf_rotate_plan_create", "rsx_sony_srf_plan_create",
                      "rsx_image_hash_plan_create", "rsx_encode_pack_plan_create",
-                     "rsx_encode_ljpeg_plan_create"):
+                     "rsx_encode_ljpeg_plan_create", "rsx_fpwrite_pack_plan_create",
+                     "rsx_fpwrite_deflate_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -475,6 +491,20 @@ def image_hash_validate(img_view, sample_bytes):
 def encode_pack_validate(desc, img_view, out_cap):
     """rsx_encode_pack_validate; None passes NULL"""
     return lib().rsx_encode_pack_validate(_ref(desc), _ref(img_view), out_cap)
+
+
+def fpwrite_deflate_validate(desc, tile, img_view):
+    """rsx_fpwrite_deflate_validate; None passes NULL"""
+    return lib().rsx_fpwrite_deflate_validate(_ref(desc), _ref(tile), _ref(img_view))
+
+
+def fpwrite_deflate_bound(desc, tile, img_view):
+    return int(lib().rsx_fpwrite_deflate_bound(_ref(desc), _ref(tile), _ref(img_view)))
+
+
+def fpwrite_pack_validate(desc, img_view, out_cap):
+    """rsx_fpwrite_pack_validate; None passes NULL"""
+    return lib().rsx_fpwrite_pack_validate(_ref(desc), _ref(img_view), out_cap)
 
 
 def encode_ljpeg_validate(desc, img_view):
@@ -1129,6 +1159,41 @@ class Context:
                                               counts.ctypes.data)
         return st, counts
 
+    def fpwrite_fit(self, img_view, windows):
+        """rsx_fpwrite_fit: windows are (x, y, w, h) in samples; img_view.data is a host or a
+        device pointer.  Returns (status, [16 | 24 | 32 per window])."""
+        n = len(windows)
+        arr = (abi.FpWriteWindow * max(n, 1))(*[abi.FpWriteWindow(*w) for w in windows])
+        out = (C.c_int32 * max(n, 1))()
+        st = lib().rsx_fpwrite_fit(self._h, C.byref(img_view), n, arr, out)
+        return st, list(out)[:n]
+
+    def fpwrite_pack(self, desc, img_view, out_ptr, out_cap):
+        """rsx_fpwrite_pack: img_view.data and out_ptr are both host or both device pointers.
+        Returns (status, abi.FpWritePackResult)."""
+        r = abi.FpWritePackResult()
+        st = lib().rsx_fpwrite_pack(self._h, C.byref(desc), C.byref(img_view), C.c_void_p(out_ptr),
+                                    out_cap, C.byref(r))
+        return st, r
+
+    def fpwrite_deflate(self, desc, tiles, img_view):
+        """rsx_fpwrite_deflate: tiles are abi.FpWriteDeflateTile (out pointers on the image's side).
+        Returns (status, [abi.FpWriteDeflateResult])."""
+        n = len(tiles)
+        arr = (abi.FpWriteDeflateTile * n)(*tiles)
+        res = (abi.FpWriteDeflateResult * n)()
+        st = lib().rsx_fpwrite_deflate(self._h, C.byref(desc), n, arr, C.byref(img_view), res)
+        return st, list(res)
+
+    def fpwrite_deflate_plan(self, jobs):
+        """jobs: abi.FpWriteDeflateJob, the tiles of one or more images; run(images_base,
+        streams_base)"""
+        return FpWriteDeflatePlan(self, "rsx_fpwrite_deflate_plan_create", abi.FpWriteDeflateJob, jobs)
+
+    def fpwrite_pack_plan(self, jobs):
+        """jobs: abi.FpWritePackJob; run(images_base, streams_base)"""
+        return FpWritePackPlan(self, "rsx_fpwrite_pack_plan_create", abi.FpWritePackJob, jobs)
+
     def encode_pack_plan(self, jobs):
         """jobs: abi.EncodePackJob; run(images_base, streams_base)"""
         return Plan(self, "rsx_encode_pack_plan_create", abi.EncodePackJob, jobs)
@@ -1234,6 +1299,22 @@ class BadPixelsPlan(Plan):
         """after results(): (status, abi.BadPixelsResult) of job `job`"""
         r = abi.BadPixelsResult()
         st = lib().rsx_bad_pixels_plan_result(self._h, job, C.byref(r))
+        return st, r
+
+
+class FpWriteDeflatePlan(Plan):
+    def result(self, job):
+        """after results(): (status, abi.FpWriteDeflateResult) of job `job`"""
+        r = abi.FpWriteDeflateResult()
+        st = lib().rsx_fpwrite_deflate_plan_result(self._h, job, C.byref(r))
+        return st, r
+
+
+class FpWritePackPlan(Plan):
+    def result(self, job):
+        """after results(): (status, abi.FpWritePackResult) of job `job`"""
+        r = abi.FpWritePackResult()
+        st = lib().rsx_fpwrite_pack_plan_result(self._h, job, C.byref(r))
         return st, r
 
 

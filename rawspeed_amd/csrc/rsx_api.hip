@@ -38,6 +38,9 @@
 #include "rsx_jpeg_core.h"
 #include "rsx_encode.h"
 #include "rsx_encode_core.h"
+#include "rsx_fpwrite.h"
+#include "rsx_fpwrite_core.h"
+#include "rsx_deflate_core.h"
 
 #include <algorithm>
 #include <map>
@@ -5044,6 +5047,266 @@ extern "C" int rsx_encode_ljpeg_histogram(rsx_ctx* ctx, const rsx_ljpeg_desc* d,
   if (int st = rsx_plan_run(call.plan, lane.lane->d_in.ptr, lane.lane->d_out.ptr, lane.lane->stream))
     return st;
   return download_bytes(ctx, lane.lane, reinterpret_cast<uint8_t*>(counts), BYTES);
+}
+
+// ---------------------------------------------------------------------------
+// Writers of F32 images: exact narrowing, packed strips, the width of windows (rsx.h section 7d)
+// ---------------------------------------------------------------------------
+extern "C" int rsx_fpwrite_pack_validate(const rsx_unpack_desc* d, const rsx_image* img,
+                                         size_t out_cap) {
+  return rsx_fpwrite::validate_pack(d, img, out_cap);
+}
+
+extern "C" int rsx_fpwrite_pack_plan_create(rsx_ctx* ctx, int n_jobs,
+                                            const rsx_fpwrite_pack_job* jobs, rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, fpwrite_pack_plan_create);
+}
+
+extern "C" int rsx_fpwrite_pack_plan_result(rsx_plan* plan, int job, rsx_fpwrite_pack_result* out) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->fpwrite_pack_result(job, out); });
+}
+
+// As rsx_encode_pack_u16: device pointers run in place on the context's stream, host pointers go
+// through a lane.  The stream comes back only when every sample had its narrow pattern.
+extern "C" int rsx_fpwrite_pack(rsx_ctx* ctx, const rsx_unpack_desc* d, const rsx_image* img,
+                                uint8_t* out, size_t out_cap, rsx_fpwrite_pack_result* result) {
+  if (result)
+    std::memset(result, 0, sizeof *result);
+  if (!ctx || !d || !img || !img->data || !out || !result)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_fpwrite::validate_pack(d, img, out_cap))
+    return st;
+  if (reinterpret_cast<uintptr_t>(img->data) % 4 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  bool dev = false;
+  if (int st = same_side(img->data, out, &dev))
+    return st;
+  rsx_fpwrite_pack_job job;
+  std::memset(&job, 0, sizeof job);
+  job.desc = *d;
+  job.img = *img;
+  job.img.data = nullptr;
+  job.out_cap = out_cap;
+  CallPlan call;
+  if (dev) {
+    // the lower of the two pointers on the samples' grid, and the offsets of both from it
+    const uintptr_t a = reinterpret_cast<uintptr_t>(img->data), b = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t base = (a < b ? a : b) & ~uintptr_t(3);
+    job.img_offset = a - base;
+    job.out_offset = b - base;
+    if (int st = rsx_fpwrite_pack_plan_create(ctx, 1, &job, &call.plan))
+      return st;
+    if (int st = rsx_plan_run(call.plan, reinterpret_cast<const void*>(base),
+                              reinterpret_cast<void*>(base), nullptr))
+      return st;
+    (void)rsx_plan_results(call.plan, nullptr, nullptr); // (waits; the status follows)
+    return rsx_fpwrite_pack_plan_result(call.plan, 0, result);
+  }
+  job.desc.crop_y = 0;
+  job.img.dim_y = d->crop_h;
+  if (int st = rsx_fpwrite_pack_plan_create(ctx, 1, &job, &call.plan))
+    return st;
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  rsx_ctx::HostLane* L = lane.lane;
+  const size_t row_bytes = size_t(img->dim_x) * size_t(img->cpp) * 4;
+  const size_t up_bytes = size_t(img->pitch_bytes) * size_t(d->crop_h - 1) + row_bytes;
+  const size_t written = size_t(rsx_fpwrite::round_up4(uint64_t(d->crop_h) * uint64_t(d->input_pitch_bytes)));
+  if (int e = L->d_in.ensure(up_bytes + 64))
+    return e;
+  if (int e = L->d_out.ensure(written + 64))
+    return e;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr,
+                                      static_cast<const uint8_t*>(img->data) +
+                                          size_t(d->crop_y) * img->pitch_bytes,
+                                      up_bytes, hipMemcpyHostToDevice, L->stream));
+  }
+  if (int st = rsx_plan_run(call.plan, L->d_in.ptr, L->d_out.ptr, L->stream))
+    return st;
+  (void)rsx_plan_results(call.plan, nullptr, nullptr);
+  const int st = rsx_fpwrite_pack_plan_result(call.plan, 0, result);
+  if (st != RSX_OK)
+    return st;
+  return download_bytes(ctx, L, out, written);
+}
+
+extern "C" int rsx_fpwrite_deflate_validate(const rsx_dng_deflate_desc* desc,
+                                            const rsx_fpwrite_deflate_tile* t, const rsx_image* img) {
+  if (!desc || !t || !img)
+    return RSX_ERR_INVALID_ARG;
+  return fpwrite_deflate_validate(*desc, t->tile_w, t->tile_h, t->off_x, t->off_y, t->width, t->height,
+                                  *img);
+}
+
+extern "C" uint64_t rsx_fpwrite_deflate_bound(const rsx_dng_deflate_desc* desc,
+                                              const rsx_fpwrite_deflate_tile* t,
+                                              const rsx_image* img) {
+  if (rsx_fpwrite_deflate_validate(desc, t, img) != RSX_OK)
+    return 0;
+  return rsx_deflate::bound_of(uint64_t(desc->bps / 8) * t->tile_w * t->tile_h);
+}
+
+extern "C" int rsx_fpwrite_deflate_plan_create(rsx_ctx* ctx, int n_jobs,
+                                               const rsx_fpwrite_deflate_job* jobs,
+                                               rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, fpwrite_deflate_plan_create);
+}
+
+extern "C" int rsx_fpwrite_deflate_plan_result(rsx_plan* plan, int job,
+                                               rsx_fpwrite_deflate_result* out) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->fpwrite_deflate_result(job, out); });
+}
+
+// The tiles of one image as the jobs of one plan.  Device pointers: the plan runs on the lowest of
+// them, on the context's stream behind the null stream's work so far.  Host pointers: the image
+// goes up as one copy into a lane, the streams lie one behind the other in the lane's output (each
+// in room for the lesser of its out_cap and its bound) and come back as one copy.
+extern "C" int rsx_fpwrite_deflate(rsx_ctx* ctx, const rsx_dng_deflate_desc* desc, int n_tiles,
+                                   const rsx_fpwrite_deflate_tile* tiles, const rsx_image* img,
+                                   rsx_fpwrite_deflate_result* results) {
+  if (!ctx || !desc || !tiles || n_tiles < 1 || !img || !img->data || !results)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  std::memset(results, 0, sizeof *results * size_t(n_tiles));
+  if (reinterpret_cast<uintptr_t>(img->data) % 4 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool dev = is_device_pointer(img->data);
+  uintptr_t base = reinterpret_cast<uintptr_t>(img->data);
+  for (int i = 0; i < n_tiles; ++i) {
+    if (!tiles[i].out || is_device_pointer(tiles[i].out) != dev)
+      return RSX_ERR_INVALID_ARG;
+    base = std::min(base, reinterpret_cast<uintptr_t>(tiles[i].out));
+  }
+  base &= ~uintptr_t(3);
+  std::vector<rsx_fpwrite_deflate_job> jobs(static_cast<size_t>(n_tiles));
+  std::vector<uint64_t> room(static_cast<size_t>(n_tiles), 0);
+  uint64_t staged = 0;
+  for (int i = 0; i < n_tiles; ++i) {
+    const rsx_fpwrite_deflate_tile& t = tiles[i];
+    rsx_fpwrite_deflate_job& j = jobs[i];
+    std::memset(&j, 0, sizeof j);
+    j.desc = *desc;
+    j.tile_w = t.tile_w, j.tile_h = t.tile_h, j.off_x = t.off_x, j.off_y = t.off_y;
+    j.width = t.width, j.height = t.height;
+    j.out_cap = t.out_cap;
+    j.img = *img;
+    j.img.data = nullptr;
+    if (dev) {
+      j.img_offset = reinterpret_cast<uintptr_t>(img->data) - base;
+      j.out_offset = reinterpret_cast<uintptr_t>(t.out) - base;
+    } else {
+      room[i] = std::min<uint64_t>(t.out_cap, rsx_fpwrite_deflate_bound(desc, &t, img));
+      j.out_offset = staged;
+      staged += (room[i] + 15u) & ~uint64_t(15);
+    }
+  }
+  CallPlan call;
+  if (int st = rsx_fpwrite_deflate_plan_create(ctx, n_tiles, jobs.data(), &call.plan))
+    return st;
+  auto collect = [&]() {
+    int rc = RSX_OK;
+    for (int i = 0; i < n_tiles; ++i)
+      if (rsx_fpwrite_deflate_plan_result(call.plan, i, &results[i]) != RSX_OK)
+        rc = RSX_ERR_TILE_ERRORS;
+    return rc;
+  };
+  if (dev) {
+    if (int st = rsx_plan_run(call.plan, reinterpret_cast<const void*>(base),
+                              reinterpret_cast<void*>(base), nullptr))
+      return st;
+    (void)rsx_plan_results(call.plan, nullptr, nullptr); // (waits; the tiles' statuses follow)
+    return collect();
+  }
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  rsx_ctx::HostLane* L = lane.lane;
+  const size_t up_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y > 0 ? img->dim_y - 1 : 0) +
+                          size_t(img->dim_x > 0 ? img->dim_x : 0) * size_t(img->cpp > 0 ? img->cpp : 0) * 4;
+  if (int e = L->d_in.ensure(up_bytes + 64))
+    return e;
+  if (int e = L->d_out.ensure(size_t(staged) + 64))
+    return e;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr, img->data, up_bytes, hipMemcpyHostToDevice,
+                                      L->stream));
+  }
+  if (int st = rsx_plan_run(call.plan, L->d_in.ptr, L->d_out.ptr, L->stream))
+    return st;
+  (void)rsx_plan_results(call.plan, nullptr, nullptr);
+  const int rc = collect();
+  std::vector<uint8_t> back(static_cast<size_t>(staged));
+  if (int e = download_bytes(ctx, L, back.data(), back.size()))
+    return e;
+  for (int i = 0; i < n_tiles; ++i)
+    if (results[i].status == RSX_OK)
+      std::memcpy(tiles[i].out, back.data() + jobs[i].out_offset, size_t(results[i].bytes));
+  return rc;
+}
+
+extern "C" int rsx_fpwrite_fit(rsx_ctx* ctx, const rsx_image* img, int n_windows,
+                               const rsx_fpwrite_window* windows, int32_t* min_bps_out) {
+  if (!ctx || !img || !img->data || !windows || !min_bps_out)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  if (int st = rsx_fpwrite::validate_fit(img, n_windows, windows))
+    return st;
+  if (reinterpret_cast<uintptr_t>(img->data) % 4 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  FpFitJob job{*img, n_windows, windows};
+  job.img.data = nullptr;
+  CallPlan call;
+  if (int st = decoder_plan_create(ctx, 1, &job, &call.plan, fpwrite_fit_plan_create))
+    return st;
+  const size_t back_bytes = size_t(n_windows) * 4;
+  std::vector<uint32_t> cls(static_cast<size_t>(n_windows), 0u);
+  if (is_device_pointer(img->data)) {
+    // the words come back through a lane's output buffer (kept between calls: nothing is allocated
+    // or freed here); the run itself is on the context's stream, behind the null stream's work
+    LaneGuard lane(ctx);
+    if (!lane.lane)
+      return RSX_ERR_DEVICE;
+    if (int e = lane.lane->d_out.ensure(back_bytes + 64))
+      return e;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    if (int st = rsx_plan_run(call.plan, img->data, lane.lane->d_out.ptr, nullptr))
+      return st;
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(cls.data(), lane.lane->d_out.ptr, back_bytes,
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    if (int st = rsx_plan_results(call.plan, nullptr, nullptr)) // (waits for the stream)
+      return st;
+  } else {
+    LaneGuard lane(ctx);
+    if (!lane.lane)
+      return RSX_ERR_DEVICE;
+    rsx_ctx::HostLane* L = lane.lane;
+    const size_t bytes = size_t(img->pitch_bytes) * size_t(img->dim_y - 1) +
+                         size_t(img->dim_x) * size_t(img->cpp) * 4;
+    if (int e = L->d_in.ensure(bytes + 64))
+      return e;
+    if (int e = L->d_out.ensure(back_bytes + 64))
+      return e;
+    {
+      std::lock_guard<std::mutex> up(ctx->upload_mu);
+      RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr, img->data, bytes, hipMemcpyHostToDevice,
+                                        L->stream));
+    }
+    if (int st = rsx_plan_run(call.plan, L->d_in.ptr, L->d_out.ptr, L->stream))
+      return st;
+    if (int e = download_bytes(ctx, L, reinterpret_cast<uint8_t*>(cls.data()), back_bytes))
+      return e;
+  }
+  for (int i = 0; i < n_windows; ++i)
+    min_bps_out[i] = rsx_fpwrite::fit_bps_of_class(cls[i]);
+  return RSX_OK;
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

@@ -205,6 +205,15 @@ struct DecoderPlan {
   virtual int scale_result(int /*job*/, rsx_scale_result* /*out*/) { return RSX_ERR_INVALID_ARG; }
   // status, bytes and symbol bits of job `job` of the last run, after results (LJPEG writer plans)
   virtual int encode_result(int /*job*/, rsx_encode_result* /*out*/) { return RSX_ERR_INVALID_ARG; }
+  // status, bytes and the count of inexact samples of job `job` of the last run, after results
+  // (F32 pack plans)
+  virtual int fpwrite_pack_result(int /*job*/, rsx_fpwrite_pack_result* /*out*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
+  // the whole result of tile `job` of the last run, after results (F32 deflate writer plans)
+  virtual int fpwrite_deflate_result(int /*job*/, rsx_fpwrite_deflate_result* /*out*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };
