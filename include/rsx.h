@@ -2828,6 +2828,111 @@ int rsx_fpwrite_deflate_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_fpwrite_
                                     rsx_plan** out_plan);
 int rsx_fpwrite_deflate_plan_result(rsx_plan* plan, int job, rsx_fpwrite_deflate_result* out);
 
+/* 7e. Lossy (baseline DCT) JPEG tiles, compression 0x884c: the inverse of section 4e.  All names
+ * begin with rsx_dctwrite_.  The stream is byte for byte what libjpeg-turbo's default compressor
+ * writes, through Pillow, for save(frame, "JPEG", quality= | qtables=, subsampling=0|1|2,
+ * restart_marker_blocks=) with every other option left alone (JDCT_ISLOW, the Huffman tables of
+ * Annex K.3, no optimisation, one sequential scan).
+ *
+ * Input.  The frame is the window (off_x, off_y, width, height) of a uint16 image with cpp 1
+ * (grey) or 3 (RGB in, YCbCr stored).  The frame may reach past the image's right and bottom edge
+ * (DNG edge tiles are full-size): a frame pixel outside the image is the nearest image pixel.  A
+ * sample above 255 is RSX_ERR_VALUE_RANGE for the tile; nothing is clamped.
+ *
+ * Arithmetic, all integers.  jccolor: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ * Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16, Cr = (32768 R - 27439 G - 5329 B + 8421375)
+ * >> 16.  Sampling of luma against chroma is (1,1), (2,1) or (2,2); grey is (1,1).  A component of
+ * w x h samples (w = ceil(width / h_samp), h = ceil(height / v_samp) for chroma) has
+ * ceil(w / 8) x ceil(h / 8) real blocks.  jcsample: chroma sample (x, y), x below 8 ceil(w / 8), is
+ * the box over frame columns min(2 x + i, width - 1) and, with y' = min(y, h - 1), frame rows
+ * min(v_samp y' + j, height - 1): (a + b + bias) >> 1 with bias 0, 1 alternating by x for (2,1),
+ * (a + b + c + d + bias) >> 2 with bias 1, 2 for (2,2).  (Columns are replicated at full
+ * resolution, rows at the component's: what libjpeg's expand_right_edge and its padding to a full
+ * iMCU row do.)  Luma and unsampled chroma take frame pixel (min(x, width - 1), min(y, height - 1)).
+ * jfdctint (CONST_BITS 13, PASS1_BITS 2) on the samples minus 128, rows then columns; coefficient x
+ * with table entry q becomes sign(x) ((|x| + 4 q) / (8 q)).
+ * A block of an interleaved MCU at or past the component's width or height in blocks is a dummy:
+ * 63 zero ACs and the DC of the block before it in the MCU, so its DC difference is 0.
+ *
+ * Entropy coding: T.81 F.1.2 with Annex K.3's four tables; DC predictors restart at 0 in every
+ * restart interval of restart_interval MCUs (0: one interval; the last may be short); every data
+ * FF is followed by 00; an interval is closed with 1-bits to a byte (an FF of the padding stuffed
+ * like any other); FF D0+(i mod 8) follows interval i but the last, FF D9 the last.
+ *
+ * Container: SOI, APP0 (JFIF 1.01, units 0, density 1 x 1; only with RSX_DCTWRITE_JFIF), one DQT
+ * per table in use (zig-zag order, 8 bits), SOF0 (ids 1, 2, 3; tables 0, 1, 1), one DHT per table
+ * (DC0, AC0, then DC1, AC1 for three components), DRI if restart_interval != 0, SOS.  Without APP0
+ * the ids still say YCbCr to the reader (section 4e).
+ *
+ * rsx_dctwrite_validate, in this order: no descriptor or image; an image that cannot hold 16-bit
+ * samples (no pixels, cpp < 1, an odd pitch_bytes, pitch_bytes < 2 cpp dim_x); components != cpp;
+ * off_x >= dim_x or off_y >= dim_y; width or height 0 or above 65535; restart_interval above
+ * 65535; an unknown flag or reserved != 0 (kept for caller-supplied Huffman tables); an entry of a
+ * table in use outside 1..255 -> RSX_ERR_INVALID_ARG; then components other than 1 or 3, sampling
+ * other than (1,1), (2,1), (2,2), or grey that is not (1,1) -> RSX_ERR_UNSUPPORTED.
+ * Per tile of a run: RSX_ERR_VALUE_RANGE (a sample above 255), RSX_ERR_INPUT_OVERFLOW (the stream
+ * would pass out_cap); in both cases 0 bytes are reported and nothing of the tile is written.  The
+ * call returns RSX_ERR_TILE_ERRORS if any tile failed; the others are written.  Nothing outside
+ * a tile's reported bytes is touched, and two runs give the same bytes.
+ *
+ * rsx_dctwrite_bound is a host closed form (0 for a refused descriptor): the header's bytes
+ * + 416 for every block of every MCU (dummies included) + 4 for every interval + 2.  A block is
+ * at most 9 + 11 bits of DC and 63 (16 + 10) bits of AC = 1658 bits < 208 bytes, twice that if
+ * every byte were FF; an interval adds up to 7 bits of padding, that byte's 00 and its marker.
+ *
+ * rsx_dctwrite_quality_tables (host only) is jpeg_quality_scaling over Annex K.1's tables with
+ * force_baseline, quality 1..100 (else RSX_ERR_INVALID_ARG): what quality= selects. */
+#define RSX_DCTWRITE_JFIF 1u
+
+typedef struct rsx_dctwrite_desc {
+  uint32_t off_x, off_y, width, height; /* the frame: pixels of the image */
+  int32_t components;                   /* 1 or 3, = img->cpp */
+  int32_t h_samp, v_samp;               /* luma against chroma */
+  uint32_t restart_interval;            /* MCUs; 0: none */
+  uint32_t flags;                       /* RSX_DCTWRITE_JFIF */
+  uint32_t reserved;                    /* 0: the Huffman tables are Annex K.3's */
+  uint16_t qtables[2][64];              /* luma, chroma: natural order, 1..255 */
+} rsx_dctwrite_desc;
+
+typedef struct rsx_dctwrite_tile {
+  rsx_dctwrite_desc desc;
+  uint8_t* out;
+  size_t out_cap;
+} rsx_dctwrite_tile;
+
+typedef struct rsx_dctwrite_result {
+  int32_t status;
+  uint32_t reserved;
+  uint64_t bytes;       /* SOI..EOI (0 unless status is RSX_OK) */
+  uint64_t scan_bytes;  /* behind the SOS segment, up to and without EOI */
+  uint64_t symbol_bits; /* Huffman codes and value bits, without padding and stuffing */
+} rsx_dctwrite_result;
+
+int rsx_dctwrite_quality_tables(int quality, uint16_t* luma, uint16_t* chroma);
+int rsx_dctwrite_validate(const rsx_dctwrite_desc* desc, const rsx_image* img);
+uint64_t rsx_dctwrite_bound(const rsx_dctwrite_desc* desc, const rsx_image* img);
+/* img->data and every tile's out: all host pointers or all device pointers; results: host.  One
+ * upload, one launch sequence, one download; one host call in rsx_ctx_host_calls. */
+int rsx_dctwrite(rsx_ctx* ctx, int n_tiles, const rsx_dctwrite_tile* tiles, const rsx_image* img,
+                 rsx_dctwrite_result* results);
+
+/* a tile of a plan: the image at img_offset (even) of the run's input buffer, the stream at
+ * out_offset (any) of its output buffer; tiles of any geometry share a plan.  A job that
+ * rsx_dctwrite_validate refuses keeps that status and writes nothing.  rsx_plan_results reports
+ * per-job status and the stream's bytes as bytes consumed; rsx_dctwrite_plan_result, after it, the
+ * whole result of job `job` of the last run. */
+typedef struct rsx_dctwrite_job {
+  rsx_dctwrite_desc desc;
+  uint64_t img_offset;
+  uint64_t out_offset;
+  uint64_t out_cap;
+  rsx_image img; /* .data ignored */
+} rsx_dctwrite_job;
+
+int rsx_dctwrite_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dctwrite_job* jobs,
+                             rsx_plan** out_plan);
+int rsx_dctwrite_plan_result(rsx_plan* plan, int job, rsx_dctwrite_result* out);
+
 /* Measurement aid, not part of the decode path: runs a plain streaming kernel
  * (16-byte loads of in_bytes, 16-byte stores of out_bytes, device pointers) `reps`
  * times on `stream` and returns the average duration in ms, measured with

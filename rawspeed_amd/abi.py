@@ -990,3 +990,48 @@ class FpWriteDeflateJob(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32),
                 ("img_offset", C.c_uint64), ("out_offset", C.c_uint64), ("out_cap", C.c_uint64),
                 ("img", Image)]
+
+
+# include/rsx.h section 7e: the baseline-DCT JPEG tile writer
+DCTWRITE_JFIF = 1
+
+
+class DctWriteDesc(C.Structure):
+    """rsx_dctwrite_desc: the frame in pixels, luma sampling against chroma, two tables in natural
+    order"""
+    _fields_ = [("off_x", C.c_uint32), ("off_y", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("components", C.c_int32), ("h_samp", C.c_int32),
+                ("v_samp", C.c_int32), ("restart_interval", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("qtables", (C.c_uint16 * 64) * 2)]
+
+
+class DctWriteTile(C.Structure):
+    """rsx_dctwrite_tile"""
+    _fields_ = [("desc", DctWriteDesc), ("out", C.c_void_p), ("out_cap", C.c_size_t)]
+
+
+class DctWriteResult(C.Structure):
+    """rsx_dctwrite_result"""
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_uint32), ("bytes", C.c_uint64),
+                ("scan_bytes", C.c_uint64), ("symbol_bits", C.c_uint64)]
+
+
+class DctWriteJob(C.Structure):
+    """rsx_dctwrite_job: the image in the run's input buffer, the stream in its output buffer"""
+    _fields_ = [("desc", DctWriteDesc), ("img_offset", C.c_uint64), ("out_offset", C.c_uint64),
+                ("out_cap", C.c_uint64), ("img", Image)]
+
+
+def dctwrite_desc(off_x, off_y, width, height, components, h_samp, v_samp, luma, chroma,
+                  restart_interval=0, flags=DCTWRITE_JFIF):
+    d = DctWriteDesc(off_x, off_y, width, height, components, h_samp, v_samp, restart_interval,
+                     flags, 0)
+    for i in range(64):
+        d.qtables[0][i] = int(luma[i])
+        d.qtables[1][i] = int(chroma[i])
+    return d
+
+
+def dctwrite_job(desc, img_offset, out_offset, out_cap, dim_x, dim_y, cpp, pitch_bytes):
+    return DctWriteJob(desc, img_offset, out_offset, out_cap,
+                       Image(None, pitch_bytes, dim_x, dim_y, cpp, 0))

@@ -35,6 +35,8 @@
   rawspeed_amd/librsx_fpwrite_host.so, rawspeed_amd/rsx_fpwrite_host_check
                                 the F32 writers' core (rsx_fpwrite_core.h, rsx_fp_narrow.h) as host
                                 C++ (g++)
+  rawspeed_amd/librsx_dctwrite_host.so, rawspeed_amd/rsx_dctwrite_host_check
+                                the baseline-JPEG writer's core (rsx_dctwrite_core.h) as host C++ (g++)
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container
 as well as on the MI355X box.  A library is rebuilt only when a source is newer.
@@ -82,6 +84,8 @@ LIB_ENCODE_HOST = os.path.join(PKG, "librsx_encode_host.so")
 BIN_ENCODE_CHECK = os.path.join(PKG, "rsx_encode_host_check")
 LIB_FPWRITE_HOST = os.path.join(PKG, "librsx_fpwrite_host.so")
 BIN_FPWRITE_CHECK = os.path.join(PKG, "rsx_fpwrite_host_check")
+LIB_DCTWRITE_HOST = os.path.join(PKG, "librsx_dctwrite_host.so")
+BIN_DCTWRITE_CHECK = os.path.join(PKG, "rsx_dctwrite_host_check")
 
 CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_direct.hip",
                 "rsx_ljpeg_fast.hip", "rsx_ljpeg_recon.hip", "rsx_sraw.hip", "rsx_samsung_v2.hip",
@@ -91,7 +95,7 @@ CORE_SOURCES = ["rsx_api.hip", "rsx_unpack.hip", "rsx_ljpeg.hip", "rsx_ljpeg_dir
                 "rsx_dng_jpeg.hip", "rsx_fuji.hip", "rsx_olympus.hip", "rsx_kodak.hip",
                 "rsx_crw.hip", "rsx_fuji_rotate.hip", "rsx_sony_srf.hip",
                 "rsx_image_hash.hip", "rsx_encode_pack.hip", "rsx_encode_ljpeg.hip",
-                "rsx_fpwrite_pack.hip", "rsx_fpwrite_deflate.hip", "rsx_host.cpp"]
+                "rsx_fpwrite_pack.hip", "rsx_fpwrite_deflate.hip", "rsx_dctwrite.hip", "rsx_host.cpp"]
 CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.h", "rsx_ljpeg.h", "rsx_ljpeg_dev.h",
                 "rsx_ljpeg_bits.h", "rsx_samsung_v2.h", "rsx_phase_one.h",
                 "rsx_sony_arw2.h", "rsx_panasonic.h", "rsx_samsung_v0.h",
@@ -106,7 +110,7 @@ CORE_HEADERS = ["rsx_internal.h", "rsx_plan_host.h", "rsx_device.h", "rsx_stamp.
                 "rsx_fuji_rotate_core.h", "rsx_sony_srf.h", "rsx_sony_srf_core.h",
                 "rsx_image_hash.h", "rsx_image_hash_core.h", "rsx_encode.h", "rsx_encode_core.h",
                 "rsx_fpwrite.h", "rsx_fpwrite_core.h", "rsx_fp_narrow.h",
-                "rsx_deflate_core.h"]
+                "rsx_deflate_core.h", "rsx_dctwrite.h", "rsx_dctwrite_core.h"]
 
 
 def _hipcc():
@@ -288,6 +292,13 @@ def build_fpwrite_host(force=False):
                             "RSX_FPWRITE_HOST_MAIN", ["-I" + INCLUDE], force)
 
 
+def build_dctwrite_host(force=False):
+    """rsx_dctwrite_core.h: integers only, one thread a tile"""
+    return _build_host_core(LIB_DCTWRITE_HOST, BIN_DCTWRITE_CHECK, "rsx_dctwrite_host.cpp",
+                            ["rsx_dctwrite_core.h", _RSX_H], "RSX_DCTWRITE_HOST_MAIN",
+                            ["-I" + INCLUDE], force)
+
+
 def _compile_objects(objdir, extra_flags, force=False):
     """One object per source under `objdir`, rebuilt when the source or any header is newer;
     the stale ones in parallel (the sources are independent translation units: one hipcc run
@@ -347,7 +358,7 @@ def build_all(force=False):
             build_fuji_host(force), build_olympus_host(force), build_kodak_host(force),
             build_crw_host(force), build_fuji_rotate_host(force), build_sony_srf_host(force),
             build_image_hash_host(force), build_encode_host(force),
-            build_fpwrite_host(force))
+            build_fpwrite_host(force), build_dctwrite_host(force))
 
 
 if __name__ == "__main__":

@@ -71,6 +71,8 @@ EXPORTS = [
     "rsx_fpwrite_pack_plan_create", "rsx_fpwrite_pack_plan_result",
     "rsx_fpwrite_deflate_validate", "rsx_fpwrite_deflate_bound", "rsx_fpwrite_deflate",
     "rsx_fpwrite_deflate_plan_create", "rsx_fpwrite_deflate_plan_result",
+    "rsx_dctwrite_quality_tables", "rsx_dctwrite_validate", "rsx_dctwrite_bound", "rsx_dctwrite",
+    "rsx_dctwrite_plan_create", "rsx_dctwrite_plan_result",
     "rsx_unpack_plan_create", "rsx_ljpeg_plan_create", "rsx_cr2_plan_create",
     "rsx_plan_run", "rsx_plan_results", "rsx_plan_set_timing",
     "rsx_plan_kernel_time", "rsx_plan_kernel_table", "rsx_plan_destroy", "rsx_probe_stream_copy",
@@ -257,6 +259,12 @@ def lib():
         L.rsx_fpwrite_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
         L.rsx_fpwrite_deflate_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rsx_dctwrite_quality_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.rsx_dctwrite_validate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_dctwrite_bound.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsx_dctwrite_bound.restype = C.c_uint64
+        L.rsx_dctwrite.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsx_dctwrite_plan_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.rsx_samsung_v2_validate.argtypes = [C.c_void_p, C.c_void_p]
         L.rsx_samsung_v2_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]
@@ -288,7 +296,7 @@ def lib():
                      "rsx_raf_rotate_plan_create", "rsx_sony_srf_plan_create",
                      "rsx_image_hash_plan_create", "rsx_encode_pack_plan_create",
                      "rsx_encode_ljpeg_plan_create", "rsx_fpwrite_pack_plan_create",
-                     "rsx_fpwrite_deflate_plan_create"):
+                     "rsx_fpwrite_deflate_plan_create", "rsx_dctwrite_plan_create"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p,
                                          C.POINTER(C.c_void_p)]
         L.rsx_plan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -500,6 +508,22 @@ def fpwrite_deflate_validate(desc, tile, img_view):
 
 def fpwrite_deflate_bound(desc, tile, img_view):
     return int(lib().rsx_fpwrite_deflate_bound(_ref(desc), _ref(tile), _ref(img_view)))
+
+
+def dctwrite_quality_tables(quality):
+    """rsx_dctwrite_quality_tables -> (status, luma[64], chroma[64]) in natural order"""
+    lu, ch = (C.c_uint16 * 64)(), (C.c_uint16 * 64)()
+    st = lib().rsx_dctwrite_quality_tables(quality, lu, ch)
+    return st, list(lu), list(ch)
+
+
+def dctwrite_validate(desc, img_view):
+    """rsx_dctwrite_validate; None passes NULL"""
+    return lib().rsx_dctwrite_validate(_ref(desc), _ref(img_view))
+
+
+def dctwrite_bound(desc, img_view):
+    return int(lib().rsx_dctwrite_bound(_ref(desc), _ref(img_view)))
 
 
 def fpwrite_pack_validate(desc, img_view, out_cap):
@@ -1185,6 +1209,19 @@ class Context:
         st = lib().rsx_fpwrite_deflate(self._h, C.byref(desc), n, arr, C.byref(img_view), res)
         return st, list(res)
 
+    def dctwrite(self, tiles, img_view):
+        """rsx_dctwrite: tiles are abi.DctWriteTile (out pointers on the image's side).
+        Returns (status, [abi.DctWriteResult])."""
+        n = len(tiles)
+        arr = (abi.DctWriteTile * n)(*tiles)
+        res = (abi.DctWriteResult * n)()
+        st = lib().rsx_dctwrite(self._h, n, arr, C.byref(img_view), res)
+        return st, list(res)
+
+    def dctwrite_plan(self, jobs):
+        """jobs: abi.DctWriteJob, tiles of any geometry; run(images_base, streams_base)"""
+        return DctWritePlan(self, "rsx_dctwrite_plan_create", abi.DctWriteJob, jobs)
+
     def fpwrite_deflate_plan(self, jobs):
         """jobs: abi.FpWriteDeflateJob, the tiles of one or more images; run(images_base,
         streams_base)"""
@@ -1307,6 +1344,14 @@ class FpWriteDeflatePlan(Plan):
         """after results(): (status, abi.FpWriteDeflateResult) of job `job`"""
         r = abi.FpWriteDeflateResult()
         st = lib().rsx_fpwrite_deflate_plan_result(self._h, job, C.byref(r))
+        return st, r
+
+
+class DctWritePlan(Plan):
+    def result(self, job):
+        """after results(): (status, abi.DctWriteResult) of job `job`"""
+        r = abi.DctWriteResult()
+        st = lib().rsx_dctwrite_plan_result(self._h, job, C.byref(r))
         return st, r
 
 

@@ -40,6 +40,8 @@
 #include "rsx_encode_core.h"
 #include "rsx_fpwrite.h"
 #include "rsx_fpwrite_core.h"
+#include "rsx_dctwrite.h"
+#include "rsx_dctwrite_core.h"
 #include "rsx_deflate_core.h"
 
 #include <algorithm>
@@ -5307,6 +5309,116 @@ extern "C" int rsx_fpwrite_fit(rsx_ctx* ctx, const rsx_image* img, int n_windows
   for (int i = 0; i < n_windows; ++i)
     min_bps_out[i] = rsx_fpwrite::fit_bps_of_class(cls[i]);
   return RSX_OK;
+}
+
+extern "C" int rsx_dctwrite_quality_tables(int quality, uint16_t* luma, uint16_t* chroma) {
+  return rsx_dctw::quality_tables(quality, luma, chroma);
+}
+
+extern "C" int rsx_dctwrite_validate(const rsx_dctwrite_desc* desc, const rsx_image* img) {
+  return rsx_dctw::validate(desc, img);
+}
+
+extern "C" uint64_t rsx_dctwrite_bound(const rsx_dctwrite_desc* desc, const rsx_image* img) {
+  if (rsx_dctw::validate(desc, img) != RSX_OK)
+    return 0;
+  rsx_dctw::Geom g;
+  rsx_dctw::geom_of(*desc, *img, 0, 0, 0, &g);
+  return rsx_dctw::bound_of(g);
+}
+
+extern "C" int rsx_dctwrite_plan_create(rsx_ctx* ctx, int n_jobs, const rsx_dctwrite_job* jobs,
+                                        rsx_plan** out_plan) {
+  return decoder_plan_create(ctx, n_jobs, jobs, out_plan, dctwrite_plan_create);
+}
+
+extern "C" int rsx_dctwrite_plan_result(rsx_plan* plan, int job, rsx_dctwrite_result* out) {
+  return decoder_plan_get(plan, [&](DecoderPlan* d) { return d->dctwrite_result(job, out); });
+}
+
+// The tiles of one image as the jobs of one plan.  Device pointers: the plan runs on the lowest of
+// them, on the context's stream behind the null stream's work so far.  Host pointers: the image
+// goes up as one copy into a lane, the streams lie one behind the other in the lane's output (each
+// in room for the lesser of its out_cap and its bound) and come back as one copy.
+extern "C" int rsx_dctwrite(rsx_ctx* ctx, int n_tiles, const rsx_dctwrite_tile* tiles,
+                            const rsx_image* img, rsx_dctwrite_result* results) {
+  if (!ctx || !tiles || n_tiles < 1 || !img || !img->data || !results)
+    return RSX_ERR_INVALID_ARG;
+  ++ctx->host_calls;
+  std::memset(results, 0, sizeof *results * size_t(n_tiles));
+  if (reinterpret_cast<uintptr_t>(img->data) % 2 != 0)
+    return RSX_ERR_INVALID_ARG;
+  RSX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const bool dev = is_device_pointer(img->data);
+  uintptr_t base = reinterpret_cast<uintptr_t>(img->data);
+  for (int i = 0; i < n_tiles; ++i) {
+    if (!tiles[i].out || is_device_pointer(tiles[i].out) != dev)
+      return RSX_ERR_INVALID_ARG;
+    base = std::min(base, reinterpret_cast<uintptr_t>(tiles[i].out));
+  }
+  base &= ~uintptr_t(1);
+  std::vector<rsx_dctwrite_job> jobs(static_cast<size_t>(n_tiles));
+  uint64_t staged = 0;
+  for (int i = 0; i < n_tiles; ++i) {
+    const rsx_dctwrite_tile& t = tiles[i];
+    rsx_dctwrite_job& j = jobs[i];
+    std::memset(&j, 0, sizeof j);
+    j.desc = t.desc;
+    j.out_cap = t.out_cap;
+    j.img = *img;
+    j.img.data = nullptr;
+    if (dev) {
+      j.img_offset = reinterpret_cast<uintptr_t>(img->data) - base;
+      j.out_offset = reinterpret_cast<uintptr_t>(t.out) - base;
+    } else {
+      const uint64_t room = std::min<uint64_t>(t.out_cap, rsx_dctwrite_bound(&t.desc, img));
+      j.out_offset = staged;
+      staged += (room + 15u) & ~uint64_t(15);
+    }
+  }
+  CallPlan call;
+  if (int st = rsx_dctwrite_plan_create(ctx, n_tiles, jobs.data(), &call.plan))
+    return st;
+  auto collect = [&]() {
+    int rc = RSX_OK;
+    for (int i = 0; i < n_tiles; ++i)
+      if (rsx_dctwrite_plan_result(call.plan, i, &results[i]) != RSX_OK || results[i].status != RSX_OK)
+        rc = RSX_ERR_TILE_ERRORS;
+    return rc;
+  };
+  if (dev) {
+    if (int st = rsx_plan_run(call.plan, reinterpret_cast<const void*>(base),
+                              reinterpret_cast<void*>(base), nullptr))
+      return st;
+    (void)rsx_plan_results(call.plan, nullptr, nullptr); // (waits; the tiles' statuses follow)
+    return collect();
+  }
+  LaneGuard lane(ctx);
+  if (!lane.lane)
+    return RSX_ERR_DEVICE;
+  rsx_ctx::HostLane* L = lane.lane;
+  const size_t up_bytes = size_t(img->pitch_bytes) * size_t(img->dim_y > 0 ? img->dim_y - 1 : 0) +
+                          size_t(img->dim_x > 0 ? img->dim_x : 0) * size_t(img->cpp > 0 ? img->cpp : 0) * 2;
+  if (int e = L->d_in.ensure(up_bytes + 64))
+    return e;
+  if (int e = L->d_out.ensure(size_t(staged) + 64))
+    return e;
+  {
+    std::lock_guard<std::mutex> up(ctx->upload_mu);
+    RSX_HIP_CHECK(ctx, hipMemcpyAsync(L->d_in.ptr, img->data, up_bytes, hipMemcpyHostToDevice,
+                                      L->stream));
+  }
+  if (int st = rsx_plan_run(call.plan, L->d_in.ptr, L->d_out.ptr, L->stream))
+    return st;
+  (void)rsx_plan_results(call.plan, nullptr, nullptr);
+  const int rc = collect();
+  std::vector<uint8_t> back(static_cast<size_t>(staged));
+  if (int e = download_bytes(ctx, L, back.data(), back.size()))
+    return e;
+  for (int i = 0; i < n_tiles; ++i)
+    if (results[i].status == RSX_OK)
+      std::memcpy(tiles[i].out, back.data() + jobs[i].out_offset, size_t(results[i].bytes));
+  return rc;
 }
 
 extern "C" int rsx_probe_stream_copy(rsx_ctx* ctx, const void* in_dev, size_t in_bytes,

@@ -214,6 +214,11 @@ struct DecoderPlan {
   virtual int fpwrite_deflate_result(int /*job*/, rsx_fpwrite_deflate_result* /*out*/) {
     return RSX_ERR_INVALID_ARG;
   }
+  // status, bytes, scan bytes and symbol bits of job `job` of the last run, after results
+  // (baseline-DCT JPEG writer plans)
+  virtual int dctwrite_result(int /*job*/, rsx_dctwrite_result* /*out*/) {
+    return RSX_ERR_INVALID_ARG;
+  }
   // the plan as an LJPEG-family plan (the chunked host path), or nullptr
   virtual LJpegPlan* ljpeg() { return nullptr; }
 };
